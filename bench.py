@@ -9,8 +9,14 @@ Workload per rank: one 4096x4096 synthetic RGB image (seed 0x5EE
 the reference CPU baseline (8.53 s) is quoted on.  N ranks train ONE joint codebook over
 N images (weak scaling: per-GPU work fixed, one all-reduce per level).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the headline line; --full adds the
+roofline and the sub-objects below, each from runs of its own after the timed steps.
+--dump-outputs DIR writes what the last timed step returned (codebook.npy, 2**bits x D float64,
+and distortion.npy, 1 float64) to DIR; the inputs are seeded, so two builds can be compared
+output for output.
 
 With --gpus N > 1 and no launcher environment (WORLD_SIZE unset), this script starts the N
 rank processes itself (one per GPU, LOCAL_RANK = device index) before anything touches a GPU,
@@ -21,7 +27,7 @@ rank 0 prints what it would run, without touching a GPU.
 Rank 0 prints one JSON line.  value = Mblocks/s = (blocks on all ranks) x levels x steps
 / max-over-ranks wall time / 1e6 (BASELINE.md section 2 definition).
 
-Sub-objects of the same line (each timed the same way, barrier + synchronize around K steps,
+Sub-objects of the same line under --full (each timed the same way, barrier + synchronize around K steps,
 max over ranks):
   c5   BASELINE.json config 5 -- the fixed 64-image 4096^2 batch, 2x2, K=1024, split over
        the N ranks (64/N images each) with the per-level RCCL all-reduce: STRONG scaling, the
@@ -74,7 +80,15 @@ def parse():
     ap.add_argument("--exact-reps", type=int, default=2,
                     help="0 disables the exact_cie1931 sub-object (exact mode on the C3 raster's CIE1931 blocks)")
     ap.add_argument("--dry-run", action="store_true", help="CPU only: start the ranks, join gloo, print the plan")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the roofline (per-level search events, the mean), "
+                         "c5, c4, c5_rank_share, end_to_end, exact_cie1931 and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/codebook.npy and DIR/distortion.npy (float64)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (ms_per_step is the timed wall over the steps)")
+    return args
 
 
 def _free_port():
@@ -231,58 +245,11 @@ def exact_cie(args, eng, cpu):
     return out
 
 
-def main():
-    args = parse()
-    if "WORLD_SIZE" not in os.environ and args.gpus > 1:
-        sys.exit(launch_ranks(args.gpus))   # before anything touches a GPU
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = int(os.environ.get("RANK", "0"))
-    local = int(os.environ.get("LOCAL_RANK", "0"))
-    if world != args.gpus:
-        sys.exit("bench.py: WORLD_SIZE=%d but --gpus %d: launch one rank per GPU" % (world, args.gpus))
-    if args.dry_run:
-        return dry_run(args, world, rank)
-    import torch
-    import torch.distributed as dist
-    import quant_amd
-
-    if world > 1:
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        dist.init_process_group("gloo", rank=rank, world_size=world)   # control plane only
-    torch.cuda.set_device(local)
-
-    def barrier():
-        if world > 1:
-            dist.barrier()
-
-    eng = quant_amd.Engine(local)
-    if world > 1:
-        uid = [quant_amd.Engine.comm_unique_id() if rank == 0 else None]
-        dist.broadcast_object_list(uid, src=0)
-        eng.comm_init(world, rank, uid[0])   # RCCL over xGMI for the per-level sums
-    comm_n, _, comm_kind = eng.comm_info()
-    rccl_ranks = comm_n if comm_kind == quant_amd.COMM_RCCL else 0
-    if world > 1 and rccl_ranks != world:
-        sys.exit("bench.py: the engine joined %d RCCL ranks, expected %d" % (rccl_ranks, world))
-    ipr = args.images_per_rank
-    eng.set_synthetic(args.size, 0x5EED + rank * ipr, ipr, args.block, args.block, quant_amd.SCALED)
-    n_local = eng.n
-    D = eng.dim
-
-    out = (np.empty((1 << args.bits, D), np.float64), np.zeros(1, np.float64))   # reused by every step
-    for _ in range(args.warmup):
-        eng.lbg(args.bits, want_assign=False, out=out)
-    barrier()
-    torch.cuda.synchronize()
-    # The timed steps carry no instrumentation (an event record idles the GPU for a few us).
-    eng.set_timing(-2)
-    t0 = time.perf_counter()
-    for step in range(args.steps):
-        eng.lbg(args.bits, want_assign=False, out=out)
-    torch.cuda.synchronize()
-    barrier()
-    elapsed = time.perf_counter() - t0
-    # Then, outside the timed region, the same quantize again with HIP events around ONE
+def roofline_report(args, eng, out, n_local, D, sync):
+    """--full: the roofline, update_kernel, flagged_rows_per_step and kahan_checks entries of the
+    result line, from quantizes of their own after the timed steps (sync: device synchronize +
+    barrier over the ranks)."""
+    # After the timed steps, the same quantize again with HIP events around ONE
     # level's search launch per call (on the engine's stream), cycling through the levels:
     # the per-launch durations of the roofline below.
     launches, update_ms, flagged = [], [], []
@@ -296,22 +263,7 @@ def main():
         flagged.append(f_rows)
     eng.set_timing(-2)
     tm_last = eng.timings()   # the last quantize's Kahan-rule statistics
-    torch.cuda.synchronize()
-    barrier()
-    if world > 1:
-        t = torch.tensor([elapsed], dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t[0])
-        n = torch.tensor([n_local], dtype=torch.int64)
-        dist.all_reduce(n)
-        n_total = int(n[0])
-    else:
-        n_total = n_local
-
-    levels = args.bits
-    value = n_total * levels * args.steps / elapsed / 1e6
-    ms_per_step = elapsed * 1e3 / args.steps
-
+    sync()
     # Roofline of the dominant kernel, the search (assign_mf32_kernel: v_mfma_f32_32x32x16_f16
     # for K >= 64, assign_small_kernel: expanded fp32 scores for K <= 32; centroid sums fused),
     # from HIP events around the launches on the engine's stream.  Algorithmic work per launch
@@ -379,25 +331,7 @@ def main():
     mean_gbs = n_local * Dp / mean_t / 1e9
     upd_secs = sum(update_ms) * 1e-3
     upd_bytes = len(update_ms) * n_local * (((D + 3) & ~3) + 4)
-    result = {
-        "metric": "Mblocks/s (assign+update)",
-        "value": round(value, 3),
-        "unit": "Mblocks/s",
-        "n_gpus": world,
-        "rccl_ranks": rccl_ranks,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f16 MFMA search on exact integer byte operands + fp64 recheck, exact integer centroid sums",
-        "data": "synthetic (SURVEY.md 8(d) generator, seed 0x5EED+image), resident in HBM",
-        "config": {"workload": "C3: %dx%d synthetic RGB per image, %dx%d blocks (D=%d), %d code vectors, "
-                               "%d image(s) per rank, joint codebook" % (args.size, args.size, args.block,
-                                                                         args.block, D, 1 << args.bits, ipr),
-                   "blocks_per_rank": n_local, "levels": levels, "parallelism": "dp%d" % world},
-        "lbg_iters_per_s": round(levels * args.steps / elapsed, 3),
+    return {
         # the dominant kernel: the largest level's search (K = 1024 at C3), one launch per quantize
         "roofline": {"bound": "mfma", "kernel": "qvq::assign_mf32_kernel (v_mfma_f32_32x32x16_f16, pruned, fused "
                                                  "exact sums), the K=%d level's search" % Kdom,
@@ -418,12 +352,108 @@ def main():
                            "achieved_GBps": round(upd_bytes / upd_secs / 1e9, 1), "peak_GBps": PEAK_HBM_GBS}
                           if upd_secs else "fused into the search (LDS u64 atomics of exact integer terms)"),
         "flagged_rows_per_step": flagged[-1],
-        # the indices' rule: the reference's (Kahan centroid bits decide the tie rows, on every
-        # rank count, DESIGN.md 3.8-3.9 and 5) unless QVQ_KAHAN=0 selects the exact-sum rule (A/B)
-        "index_rule": "exact-sum" if os.environ.get("QVQ_KAHAN") == "0" else "kahan (reference)",
         "kahan_checks": {"redo": tm_last["kahan_redo"], "cross_rank_cell_sums": tm_last["kahan_relays"],
                          "tie_export_overflow": tm_last["tie_overflow"]},
     }
+
+
+def main():
+    args = parse()
+    if "WORLD_SIZE" not in os.environ and args.gpus > 1:
+        sys.exit(launch_ranks(args.gpus))   # before anything touches a GPU
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    rank = int(os.environ.get("RANK", "0"))
+    local = int(os.environ.get("LOCAL_RANK", "0"))
+    if world != args.gpus:
+        sys.exit("bench.py: WORLD_SIZE=%d but --gpus %d: launch one rank per GPU" % (world, args.gpus))
+    if args.dry_run:
+        return dry_run(args, world, rank)
+    import torch
+    import torch.distributed as dist
+    import quant_amd
+
+    if world > 1:
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        dist.init_process_group("gloo", rank=rank, world_size=world)   # control plane only
+    torch.cuda.set_device(local)
+
+    def barrier():
+        if world > 1:
+            dist.barrier()
+
+    eng = quant_amd.Engine(local)
+    if world > 1:
+        uid = [quant_amd.Engine.comm_unique_id() if rank == 0 else None]
+        dist.broadcast_object_list(uid, src=0)
+        eng.comm_init(world, rank, uid[0])   # RCCL over xGMI for the per-level sums
+    comm_n, _, comm_kind = eng.comm_info()
+    rccl_ranks = comm_n if comm_kind == quant_amd.COMM_RCCL else 0
+    if world > 1 and rccl_ranks != world:
+        sys.exit("bench.py: the engine joined %d RCCL ranks, expected %d" % (rccl_ranks, world))
+    ipr = args.images_per_rank
+    eng.set_synthetic(args.size, 0x5EED + rank * ipr, ipr, args.block, args.block, quant_amd.SCALED)
+    n_local = eng.n
+    D = eng.dim
+
+    out = (np.empty((1 << args.bits, D), np.float64), np.zeros(1, np.float64))   # reused by every step
+    for _ in range(args.warmup):
+        eng.lbg(args.bits, want_assign=False, out=out)
+    barrier()
+    torch.cuda.synchronize()
+    # The timed steps carry no instrumentation (an event record idles the GPU for a few us).
+    eng.set_timing(-2)
+    t0 = time.perf_counter()
+    for step in range(args.steps):
+        eng.lbg(args.bits, want_assign=False, out=out)
+    torch.cuda.synchronize()
+    barrier()
+    elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # what the last timed step returned (every rank holds the same joint codebook)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "codebook.npy"), out[0])
+        np.save(os.path.join(args.dump_outputs, "distortion.npy"), out[1])
+    if world > 1:
+        t = torch.tensor([elapsed], dtype=torch.float64)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t[0])
+        n = torch.tensor([n_local], dtype=torch.int64)
+        dist.all_reduce(n)
+        n_total = int(n[0])
+    else:
+        n_total = n_local
+
+    levels = args.bits
+    value = n_total * levels * args.steps / elapsed / 1e6
+    ms_per_step = elapsed * 1e3 / args.steps
+
+    result = {
+        "metric": "Mblocks/s (assign+update)",
+        "value": round(value, 3),
+        "unit": "Mblocks/s",
+        "n_gpus": world,
+        "rccl_ranks": rccl_ranks,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f16 MFMA search on exact integer byte operands + fp64 recheck, exact integer centroid sums",
+        "data": "synthetic (SURVEY.md 8(d) generator, seed 0x5EED+image), resident in HBM",
+        "config": {"workload": "C3: %dx%d synthetic RGB per image, %dx%d blocks (D=%d), %d code vectors, "
+                               "%d image(s) per rank, joint codebook" % (args.size, args.size, args.block,
+                                                                         args.block, D, 1 << args.bits, ipr),
+                   "blocks_per_rank": n_local, "levels": levels, "parallelism": "dp%d" % world},
+        "lbg_iters_per_s": round(levels * args.steps / elapsed, 3),
+        # the indices' rule: the reference's (Kahan centroid bits decide the tie rows, on every
+        # rank count, DESIGN.md 3.8-3.9 and 5) unless QVQ_KAHAN=0 selects the exact-sum rule (A/B)
+        "index_rule": "exact-sum" if os.environ.get("QVQ_KAHAN") == "0" else "kahan (reference)",
+    }
+    if args.full:
+        result.update(roofline_report(args, eng, out, n_local, D,
+                                      lambda: (torch.cuda.synchronize(), barrier())))
+
     def timed(fn, steps, warmup):
         """Max-over-ranks wall of `steps` calls of fn after `warmup`, barrier + sync on both sides."""
         for _ in range(warmup):
@@ -443,7 +473,7 @@ def main():
         return el
 
     # C5: the fixed 64-image batch split over the ranks, one joint codebook (strong scaling)
-    if args.c5_steps > 0:
+    if args.full and args.c5_steps > 0:
         n_img = args.c5_images
         share = [n_img // world + (1 if r < n_img % world else 0) for r in range(world)]
         start = sum(share[:rank])
@@ -460,7 +490,7 @@ def main():
                         "ms_per_step": round(el * 1e3 / args.c5_steps, 3), "steps": args.c5_steps, "warmup": 1,
                         "n_gpus": world, "scaling": "strong", "blocks_total": n5,
                         "images_per_rank": share, "collective": "RCCL all-reduce per level" if world > 1 else "none"}
-    if world == 1 and args.c4_steps > 0:
+    if args.full and world == 1 and args.c4_steps > 0:
         eng.set_synthetic(args.size, 0x5EED, 1, 4, 4, quant_amd.SCALED)
         eng.set_timing(-2)
         out4 = (np.empty((1 << 12, eng.dim), np.float64), np.zeros(1, np.float64))
@@ -469,7 +499,7 @@ def main():
         result["c4"] = {"workload": "C4: %dx%d synthetic, 4x4 blocks (D=48), 4096 code vectors" % (args.size, args.size),
                         "value": round(eng.n * 12 * args.c4_steps / el / 1e6, 3), "unit": "Mblocks/s",
                         "ms_per_step": round(el * 1e3 / args.c4_steps, 3), "steps": args.c4_steps, "warmup": 3}
-    if world == 1 and args.share_steps > 0:
+    if args.full and world == 1 and args.share_steps > 0:
         # one rank's share of C5 at N=8, under the communicator schedule (a 1-rank RCCL
         # communicator: the all-reduce per level, kd ties and reduce as with N ranks) and under
         # the one-rank schedule: the per-rank workload of the 8-GPU run, not a scaling curve
@@ -496,7 +526,7 @@ def main():
                                                % (n_share, args.size, args.size, 1 << args.bits),
                                    "steps": args.share_steps, "warmup": 1, **share_res,
                                    "rccl_over_one_rank": round(rc / r1, 4)}
-    if world == 1 and args.e2e_reps > 0:
+    if args.full and world == 1 and args.e2e_reps > 0:
         # the drop-in's compress region from a host raster: H2D + tiling + quantize + indices D2H
         rgb = synthetic_raster(args.size, 0x5EED)
         Cb = np.empty((1 << args.bits, 3 * args.block * args.block), np.float64)
@@ -514,13 +544,13 @@ def main():
                                 "ms": round(med * 1e3, 3), "Mblocks_per_s": round(n_local * args.bits / med / 1e6, 3),
                                 "reps": args.e2e_reps}
         result["end_to_end_ms"] = round(med * 1e3, 3)
-    if world == 1 and args.exact_reps > 0:
+    if args.full and world == 1 and args.exact_reps > 0:
         e3 = quant_amd.Engine(local)
         try:
             result["exact_cie1931"] = exact_cie(args, e3, not args.no_cpu_baseline)
         finally:
             e3.close()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             cb = cpu_baseline(args)
             result["cpu_baseline"] = cb

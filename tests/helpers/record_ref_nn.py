@@ -1,0 +1,39 @@
+"""Records tests/golden/ref_nn.json: what the compiled reference kd-tree (oracle/_ref/libref_nn.so,
+`make -C oracle ref` where the reference checkout is present) answers for the inputs of
+tests/test_oracle_golden.py's kd-tree tests, as fingerprints of its index arrays beside those of the
+codebooks it was given.  Run from the repository root after a change of those inputs:
+
+    python tests/helpers/record_ref_nn.py
+"""
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))   # tests/: conftest, the test module
+
+import numpy as np   # noqa: E402
+
+import test_oracle_golden as t   # noqa: E402
+
+
+def record(C, X):
+    ref = t._ref_nn(C, X)
+    if ref is None:
+        sys.exit("oracle/_ref/libref_nn.so is not built: make -C oracle ref")
+    return {"C": t.sha(np.ascontiguousarray(C, np.float64)), "A": t.sha(ref.astype("<u4"))}
+
+
+def main():
+    out = {"what": "sha-256[:16] of the compiled reference kd-tree's indices (A, little-endian u32) for the codebook "
+                   "with fingerprint C (float64), over every row of the case's training set",
+           "tie_heavy": {str(K): record(C, X) for K, C, X in t.tie_heavy_codebooks()}, "levels": {}}
+    for case in t.LEVEL_CASES:
+        X, splits, _ = t.level_case(case)
+        out["levels"][case] = [record(Cs, X) for Cs in splits]
+    with open(os.path.join(t.GOLDEN, "ref_nn.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -4,8 +4,8 @@
 # gpurun_out/TAG/.  Steps:
 #   suite               pytest -m gpu (log: gpu_tests.log)
 #   suite:EXPR          only the tests matching -k EXPR
-#   record              bench.py defaults + kernel stats of the same command + FETCH/WRITE PMC passes
-#   bench[:ARGS]        bench.py with ARGS (commas for spaces), JSON to bench_N.json
+#   record              bench.py --full + kernel stats of the same command + FETCH/WRITE PMC passes
+#   bench[:ARGS]        bench.py with ARGS (commas for spaces; --full for the roofline and sub-objects), JSON to bench_N.json
 #   ab:N:SPEC;SPEC...   N interleaved C3 runs per SPEC "name=VAR=v,VAR2=v" (20 steps, per-level events)
 #   timeline:CASE       kernel trace of tools/quick_timing.py CASE (e.g. 4096,4,12), no timing events -> levels_CASE.txt
 #   host:CASE           QVQ_HOST_TRACE=1 host timeline of CASE -> host_CASE.log
@@ -38,7 +38,7 @@ for step in "$@"; do
     tail -c 600 $O/bench_$n.json ;;
   ab)
     reps=${arg%%:*}; specs=${arg#*:}
-    B="--steps 20 --warmup 3 --c4-steps 0 --c5-steps 0 --e2e-reps 0 --share-steps 0 --exact-reps 0 --no-cpu-baseline"
+    B="--full --steps 20 --warmup 3 --c4-steps 0 --c5-steps 0 --e2e-reps 0 --share-steps 0 --exact-reps 0 --no-cpu-baseline"
     for i in $(seq 1 $reps); do
       IFS=';' read -ra SP <<< "$specs"
       for s in "${SP[@]}"; do
@@ -76,7 +76,7 @@ print('${name}_$i', 'C3', d['ms_per_step'], 'search us', {k: round(p[k]['avg_lau
     done
     cat $O/callab.txt ;;
   libab)
-    B="--steps 20 --warmup 3 --c4-steps 10 --c5-steps 0 --e2e-reps 0 --share-steps 0 --exact-reps 0 --no-cpu-baseline"
+    B="--full --steps 20 --warmup 3 --c4-steps 10 --c5-steps 0 --e2e-reps 0 --share-steps 0 --exact-reps 0 --no-cpu-baseline"
     for i in $(seq 1 ${arg:-4}); do   # (order alternating, ABBA: a drift over the call cancels)
       for k in $( [ $((i % 2)) = 1 ] && echo "base new" || echo "new base" ); do
         L=""; [ $k = base ] && L=$R/quant_amd/lib_base/libqvq.so

@@ -3,6 +3,7 @@
 # usage: bash tools/gpu_bench.sh TAG [bench args...]
 set -o pipefail
 TAG=$1; shift
+set -- --full "$@"   # every pass below takes the full report (roofline and sub-objects), not the plain headline run
 R=$GRAFT_REPO_ROOT
 mkdir -p $R/gpurun_out/$TAG
 cd /tmp && export TMPDIR=/tmp
