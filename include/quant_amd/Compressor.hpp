@@ -39,6 +39,11 @@ public:
     static std::pair<CompressedImage, CompressionRaport> compress(const RGBImage &image, Quantizers quantizer,
                                                                   ColorSpaces colorSpace, int blockWidth,
                                                                   int blockHeight, VectorType eps, int N);
+    // The same with the caller's quantizer object (e.g. getRefinedLBGQuantizer, Quantizer.hpp): the
+    // blocks are tiled on the host and its codebook is converted to bytes as it is.
+    static std::pair<CompressedImage, CompressionRaport> compress(const RGBImage &image, AbstractQuantizer &quantizer,
+                                                                  ColorSpaces colorSpace, int blockWidth,
+                                                                  int blockHeight, VectorType eps, int N);
     static RGBImage decompress(const CompressedImage &);
 
     std::vector<CharVector> codeVectors;
@@ -47,6 +52,12 @@ public:
     size_t blockWidth = 0, blockHeight = 0;
     ColorSpaces colorSpace = ColorSpaces::SCALED;
     Quantizers quantizer = Quantizers::LBG;
+
+private:
+    static std::pair<CompressedImage, CompressionRaport> pack_compressed(
+        const RGBImage &image, const std::vector<Vector> &codebook, std::vector<size_t> assigned,
+        const ColorSpacePtr &cs, ColorSpaces colorSpace, Quantizers quantizer, int blockWidth, int blockHeight,
+        std::chrono::duration<double> elapsed);
 };
 
 std::vector<CharVector> vectorsToCharVectorsColorSpaced(const std::vector<Vector> &vectors,

@@ -23,3 +23,8 @@ typedef std::unique_ptr<AbstractQuantizer> QuantizerPtr;
 // LBG -> the engine's split-LBG on HIP device QVQ_DEVICE (default 0); the other
 // enumerators have no implementation, as in the reference, and give nullptr.
 QuantizerPtr getQuantizer(Quantizers);
+// The LBG quantizer followed by Lloyd refinement at the final K on the device (qvq_refine,
+// include/qvq.h): up to maxIters iterations, stopped when no index changes or when the
+// distortion's relative change falls to quantize()'s eps; fresh: the returned indices are the
+// nearest code vectors of the returned codebook (one more assignment).  (0, false) is getQuantizer(LBG).
+QuantizerPtr getRefinedLBGQuantizer(size_t maxIters, bool fresh);

@@ -116,7 +116,8 @@ QVQ_API uint32_t qvq_dim(const qvq_ctx *ctx);
 /*
  * Full split-LBG (LBGQuantizer::quantize, src/Quantizer.cpp:122-143) over the training
  * set: n = bits levels, K = 2^bits code vectors.  eps is accepted for signature parity;
- * it cannot change the outputs (one Lloyd step per level).
+ * it cannot change the outputs (one Lloyd step per level); qvq_refine
+ * continues from this call's result with eps as a real stopping rule.
  * Outputs (caller-owned host memory, any may be NULL):
  *   codebook   : K x dim fp64
  *   assign     : n u32 (this rank's rows)
@@ -128,8 +129,51 @@ QVQ_API uint32_t qvq_dim(const qvq_ctx *ctx);
  */
 QVQ_API qvq_status qvq_lbg(qvq_ctx *ctx, uint32_t bits, double eps, double *codebook, uint32_t *assign,
                            double *distortion);
-/* Device pointer to the last qvq_lbg's assignment (u32, qvq_num_vectors entries). */
+/* Device pointer to the last qvq_lbg's or qvq_refine's assignment (u32, qvq_num_vectors entries). */
 QVQ_API const uint32_t *qvq_assign_device(const qvq_ctx *ctx);
+
+/*
+ * Lloyd refinement at fixed K, resident on the device: iterate assignment and centroid steps from
+ * a codebook until the assignment stops changing, the distortion settles, or max_iters.
+ *
+ * For t = 1 .. max_iters:
+ *   A_t = the assignment qvq_assign gives for C_{t-1} (the reference's kd-tree answer over that
+ *         codebook, ties included);
+ *   C_t = the centroids qvq_update gives for A_t (exact sums, empty cells 0);
+ *   d_t = the mean squared error of (C_t, A_t), as updateDistortion;
+ *   changed[t-1] = rows with A_t != A_{t-1};  dist_trace[t-1] = d_t.
+ * After iteration t, in this order:
+ *   changed == 0                        -> QVQ_STOP_FIXED (C_t = C_{t-1}: a Lloyd fixed point)
+ *   |d_{t-1} - d_t| / d_{t-1} <= eps    -> QVQ_STOP_EPS   (the reference's test, src/Quantizer.cpp:105)
+ *   t == max_iters                      -> QVQ_STOP_MAXIT
+ *
+ * C_start == NULL continues from this context's last successful qvq_lbg or qvq_refine on the
+ * current training set: A_0, C_0, d_0 are that call's results and K must be its K (QVQ_EINVAL
+ * otherwise); QVQ_ESTATE if there is none, or if a qvq_set_*, qvq_assign or qvq_update* call came
+ * in between.  C_start != NULL (K x dim, e.g. another image's codebook) is a warm start: C_0 =
+ * C_start, there is no A_0, iteration 1 reports changed = N and takes no eps test; every component
+ * must lie within the colour space's value range (QVQ_EINVAL otherwise).
+ *
+ * QVQ_REFINE_FRESH: after the loop one more assignment A* = assign(C_t) is returned in place of
+ * A_t, and distortion is that of (C_t, A*) (closed form from A*'s sums: sum ||x||^2 - 2 sum_k
+ * c_k.S_k + sum_k n_k ||c_k||^2); the codebook is not updated again.  max_iters = 0 is legal with
+ * this flag only (QVQ_EINVAL without): fresh indices for the starting codebook.
+ *
+ * Outputs (caller-owned host memory, any may be NULL): codebook K x dim, assign n u32, distortion,
+ * changed and dist_trace (max_iters entries each, the first info->iters written), info.
+ * qvq_assign_device points at the returned assignment.  A later qvq_lbg on the context gives
+ * exactly what it gave before.  Exact mode (qvq_set_vectors_exact, or its fallback inside
+ * qvq_set_vectors) and a joined communicator return QVQ_EUNSUPPORTED.
+ */
+enum { QVQ_REFINE_FRESH = 1 };                    /* flags */
+enum { QVQ_STOP_FIXED = 0, QVQ_STOP_EPS = 1, QVQ_STOP_MAXIT = 2 };
+typedef struct { uint32_t iters, stop; } qvq_refine_info;
+QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start /* K x dim, or NULL */,
+                              uint32_t max_iters, double eps, uint32_t flags,
+                              double *codebook, uint32_t *assign, double *distortion,
+                              uint64_t *changed /* max_iters, may be NULL */,
+                              double *dist_trace /* max_iters, may be NULL */,
+                              qvq_refine_info *info /* may be NULL */);
 
 /* Single steps over the current training set, for tests and benchmarks.
  * qvq_assign: nearest code vector of every row for codebook C (K x dim fp64, host),

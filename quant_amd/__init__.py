@@ -45,9 +45,11 @@ EXPORTED = ["qvq_create", "qvq_destroy", "qvq_last_error", "qvq_version", "qvq_s
             "qvq_host_finalize", "qvq_host_row_terms", "qvq_decode", "qvq_decode_mse", "qvq_decode_device",
             "qvq_set_timeout", "qvq_host_wait_probe", "qvq_comm_init_host", "qvq_comm_info", "qvq_set_vectors_exact",
             "qvq_update_kahan_split", "qvq_host_pool_stress", "qvq_kdtree_device_check",
-            "qvq_host_kdtree_image"]
+            "qvq_host_kdtree_image", "qvq_refine"]
 
 COMM_NONE, COMM_RCCL, COMM_HOST = 0, 1, 2
+REFINE_FRESH = 1                              # qvq_refine flags
+STOP_FIXED, STOP_EPS, STOP_MAXIT = 0, 1, 2    # qvq_refine_info.stop
 # int fn(void *buf, uint64_t count, int dtype, void *user) (qvq.h, qvq_comm_init_host)
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p)
 
@@ -95,6 +97,7 @@ def lib():
             "qvq_host_wait_probe": ([i, ctypes.c_double, P], i),
             "qvq_comm_init_host": ([P, i, i, ALLREDUCE_FN, P], i),
             "qvq_comm_info": ([P, ctypes.POINTER(i), ctypes.POINTER(i), ctypes.POINTER(i)], i),
+            "qvq_refine": ([P, u32, P, u32, ctypes.c_double, u32, P, P, P, P, P, P], i),
         }
         for name, (args, res) in sig.items():
             if os.environ.get("QVQ_LIB") and not hasattr(L, name):
@@ -201,7 +204,37 @@ class Engine:
             assert d.shape == (1,) and d.dtype == np.float64
         A = np.empty(self.n, np.uint32) if want_assign else None
         _check(lib().qvq_lbg(self._h, bits, eps, _p(C), _p(A) if want_assign else None, _p(d)), self._h)
+        self._last_k = K
         return C, A, float(d[0])
+
+    def refine(self, K=None, C=None, max_iters=100, eps=1e-6, fresh=False, want_assign=True):
+        """Lloyd refinement at fixed K on the device (qvq_refine): (C, A, distortion, info).
+        C=None continues from this engine's last lbg() or refine() (K defaults to that call's K);
+        a K x dim array C is a warm start.  fresh=True returns the indices of the final codebook
+        (one more assignment) and their distortion.  info: iters, stop (STOP_FIXED / STOP_EPS /
+        STOP_MAXIT), changed (rows that moved, per iteration), distortion (per iteration).
+        want_assign=False leaves the indices on the device (A is None)."""
+        if C is not None:
+            C = np.ascontiguousarray(C, np.float64)
+            if C.ndim != 2 or C.shape[1] != self.dim or (K is not None and K != C.shape[0]):
+                raise QVQError(1, "starting codebook must be K x dim")
+            K = C.shape[0]
+        elif K is None:
+            K = getattr(self, "_last_k", 0)
+        max_iters = int(max_iters)
+        out = np.empty((K, self.dim), np.float64)
+        A = np.empty(self.n, np.uint32) if want_assign else None
+        d = np.zeros(1, np.float64)
+        chg = np.zeros(max(max_iters, 1), np.uint64)
+        trace = np.zeros(max(max_iters, 1), np.float64)
+        inf = np.zeros(2, np.uint32)
+        _check(lib().qvq_refine(self._h, K, _p(C) if C is not None else None, max_iters, float(eps),
+                                REFINE_FRESH if fresh else 0, _p(out), _p(A) if want_assign else None, _p(d), _p(chg), _p(trace), _p(inf)),
+               self._h)
+        self._last_k = K
+        it = int(inf[0])
+        return out, A, float(d[0]), {"iters": it, "stop": int(inf[1]), "changed": [int(x) for x in chg[:it]],
+                                     "distortion": [float(x) for x in trace[:it]]}
 
     def assign(self, C):
         C = np.ascontiguousarray(C, np.float64)
@@ -424,15 +457,22 @@ class AbstractQuantizer:
 class LBGQuantizer(AbstractQuantizer):
     """LBGQuantizer (src/Quantizer.cpp:119-144) on the MI355X engine."""
 
-    def __init__(self, device=0):
+    def __init__(self, device=0, refine_iters=0, fresh=False):
+        """refine_iters > 0: up to that many Lloyd iterations at the final K after the split
+        levels, stopped by eps (Engine.refine); fresh: the indices of the returned codebook."""
         self._device = device
         self._engine = None
+        self._refine_iters = int(refine_iters)
+        self._fresh = bool(fresh)
 
     def quantize(self, trainingSet, n, eps):
         if self._engine is None:
             self._engine = Engine(self._device)
         self._engine.set_vectors(np.asarray(trainingSet, np.float64))
-        return self._engine.lbg(int(n), eps)
+        res = self._engine.lbg(int(n), eps)
+        if self._refine_iters > 0 or self._fresh:
+            res = self._engine.refine(max_iters=self._refine_iters, eps=eps, fresh=self._fresh)[:3]
+        return res
 
 
 def getQuantizer(q):

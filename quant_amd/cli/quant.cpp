@@ -3,13 +3,16 @@
 //
 //   quant FILE -o OUT [-n bits=8] [-e eps=1e-6] [-w width=2] [-h height=2] [-r raport=0]
 //                     [-q quantizer=0 (LBG)] [-c colorspace=1 (SCALED)] [--device N]
+//                     [--refine N=0] [--fresh]
 //
 // FILE.ppm -> OUT.quant compresses, FILE.quant -> OUT.ppm decompresses, FILE.ppm -> OUT.ppm
 // compresses and writes the decoded image (src/main.cpp:73-111); anything else prints "File
 // type not supported" and exits 1.  Options take a value as "-n 8", "-n8", "--saveto OUT" or
 // "--saveto=OUT" (program_options' short and long forms); -r takes a value ("-r 1"), -h is the
 // block height and --help the help text, as in the reference.  The quantization itself runs
-// on the GPU through libquant_amd.so / libqvq.so.
+// on the GPU through libquant_amd.so / libqvq.so.  --refine N runs up to N Lloyd iterations at the
+// final codebook size after the split levels (stopped by eps) and --fresh writes the indices of
+// the codebook in the file (getRefinedLBGQuantizer); with neither the output is the reference's.
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
@@ -41,6 +44,8 @@ struct Params {   // include/ProgramParameters.hpp:5-19, defaults of src/main.cp
     int n = 8, width = 2, height = 2, quantizer = (int)Quantizers::LBG, colorspace = (int)ColorSpaces::SCALED;
     float eps = 0.000001f;
     bool raport = false;
+    int refine = 0;       // --refine: Lloyd iterations at the final K (0: none)
+    bool fresh = false;   // --fresh: indices of the written codebook
     std::string file, saveto;
 };
 
@@ -56,7 +61,9 @@ const char *kHelp =
     "  -r arg (=0)            Print raport to std::out\n"
     "  -q [ --quantizer ] arg (=0) Pick quantizer\n"
     "  -c [ --colorspace ] arg (=1) Pick ColorSpace\n"
-    "  --device arg (=0)      HIP device of the engine (MI355X build)\n";
+    "  --device arg (=0)      HIP device of the engine (MI355X build)\n"
+    "  --refine arg (=0)      Lloyd iterations at the final codebook size (LBG, stopped by -e)\n"
+    "  --fresh                Indices re-assigned to the written codebook\n";
 
 bool parse_bool(const std::string &v) {   // program_options' bool values
     if (v == "1" || v == "true" || v == "yes" || v == "on") return true;
@@ -77,11 +84,15 @@ bool parse(int argc, char **argv, Params &p) {
     const std::map<std::string, std::string> names = {
         {"-n", "n"}, {"-e", "e"}, {"-w", "w"}, {"-h", "h"}, {"-o", "o"}, {"--saveto", "o"}, {"-r", "r"},
         {"-q", "q"}, {"--quantizer", "q"}, {"-c", "c"}, {"--colorspace", "c"}, {"--c", "c"}, {"--file", "file"},
-        {"--device", "device"}};
+        {"--device", "device"}, {"--refine", "refine"}};
     bool have_file = false, have_out = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         if (a == "--help") return true;
+        if (a == "--fresh") {   // the one flag without a value
+            p.fresh = true;
+            continue;
+        }
         std::string key, val;
         bool has_val = false;
         if (a.size() > 1 && a[0] == '-') {
@@ -117,6 +128,10 @@ bool parse(int argc, char **argv, Params &p) {
         else if (key == "q") p.quantizer = parse_int(val, "--quantizer");
         else if (key == "c") p.colorspace = parse_int(val, "--colorspace");
         else if (key == "device") setenv("QVQ_DEVICE", val.c_str(), 1);
+        else if (key == "refine") {
+            p.refine = parse_int(val, "--refine");
+            if (p.refine < 0) throw std::invalid_argument("the argument ('" + val + "') for option '--refine' is invalid");
+        }
         else if (key == "o") {
             p.saveto = val;
             have_out = true;
@@ -128,6 +143,8 @@ bool parse(int argc, char **argv, Params &p) {
     }
     if (!have_file) throw std::invalid_argument("the option '--file' is required but missing");
     if (!have_out) throw std::invalid_argument("the option '--saveto' is required but missing");
+    if ((p.refine > 0 || p.fresh) && p.quantizer != (int)Quantizers::LBG)
+        throw std::invalid_argument("options '--refine' and '--fresh' need the LBG quantizer");
     return false;
 }
 
@@ -142,14 +159,20 @@ int main(int argc, char **argv) {
         }
     } catch (const std::exception &e) {
         std::cerr << "quant: " << e.what() << std::endl;
+        std::cerr << "usage: quant FILE -o OUT [options]; quant --help lists them" << std::endl;
         return 2;
     }
     const FileType from = file_type(par.file), to = file_type(par.saveto);
     try {
         auto run_compression = [&]() {   // src/main.cpp:76-84
             RGBImage img(par.file);
-            auto result = CompressedImage::compress(img, (Quantizers)par.quantizer, (ColorSpaces)par.colorspace,
-                                                    par.width, par.height, par.eps, par.n);
+            QuantizerPtr refined;
+            if (par.refine > 0 || par.fresh) refined = getRefinedLBGQuantizer((size_t)par.refine, par.fresh);
+            auto result = refined ? CompressedImage::compress(img, *refined, (ColorSpaces)par.colorspace, par.width,
+                                                              par.height, par.eps, par.n)
+                                  : CompressedImage::compress(img, (Quantizers)par.quantizer,
+                                                              (ColorSpaces)par.colorspace, par.width, par.height,
+                                                              par.eps, par.n);
             if (par.raport) std::cout << result.second;
             return result.first;
         };

@@ -106,7 +106,8 @@ bool codebook_near_byte_flip(const std::vector<double> &C) {
 // The image's blocks trained on the engine straight from the raster (device tiling).
 std::tuple<std::vector<Vector>, std::vector<size_t>, VectorType> quantize_raster(const RGBImage &image,
                                                                                  ColorSpaces cs, int bw, int bh,
-                                                                                 VectorType eps, int n) {
+                                                                                 VectorType eps, int n,
+                                                                                 const quant_amd::RefineOptions &opt = {}) {
     qvq_ctx *ctx = EngineHandle::get();
     EngineHandle::check(qvq_set_images(ctx, reinterpret_cast<const uint8_t *>(image.img.data()), 1,
                                        (uint32_t)image.xSize, (uint32_t)image.ySize, (uint32_t)bw, (uint32_t)bh,
@@ -121,8 +122,17 @@ std::tuple<std::vector<Vector>, std::vector<size_t>, VectorType> quantize_raster
     // at most a few ulps away.  Only a component within a few ulps of a point where
     // round((c - 128) * 255) changes can turn into another byte (src/ColorSpace.cpp:23-28), so the
     // reference's bits are fetched when any component sits that close (SCALED only: NORMAL values
-    // are integers, whose Kahan sums are exact).
-    if (cs == ColorSpaces::SCALED && codebook_near_byte_flip(C)) {
+    // are integers, whose Kahan sums are exact).  This substitution belongs to the unrefined
+    // reference path only: a refined codebook has no reference value to match and is converted to
+    // bytes as qvq_refine returns it.
+    const bool refined = opt.maxIters > 0 || opt.fresh;
+    if (refined) {
+        if (opt.maxIters > 0xFFFFFFFFull) throw std::runtime_error("compress: too many refinement iterations");
+        EngineHandle::check(qvq_refine(ctx, (uint32_t)K, nullptr, (uint32_t)opt.maxIters, eps,
+                                       opt.fresh ? QVQ_REFINE_FRESH : 0, C.data(), A.data(), &distortion, nullptr,
+                                       nullptr, nullptr),
+                            "qvq_refine");
+    } else if (cs == ColorSpaces::SCALED && codebook_near_byte_flip(C)) {
         EngineHandle::check(qvq_update_kahan(ctx, A.data(), (uint32_t)K, C.data()), "qvq_update_kahan");
     }
     std::vector<Vector> codebook(K, Vector(D));
@@ -179,7 +189,41 @@ std::pair<CompressedImage, CompressionRaport> CompressedImage::compress(const RG
             q->quantize(getBlocksAsVectorsFromImage(image, blockWidth, blockHeight, cs), (size_t)N, eps);
     }
     const std::chrono::duration<double> elapsed = std::chrono::system_clock::now() - t0;
+    return pack_compressed(image, codebook, std::move(assigned), cs, colorSpace, quantizer, blockWidth, blockHeight,
+                           elapsed);
+}
 
+// The caller's quantizer over the image's blocks.  The engine's own LBG quantizers (getQuantizer,
+// getRefinedLBGQuantizer) train straight from the raster as the enum overload does, with their
+// refinement; any other quantizer gets the host-built vectors.
+std::pair<CompressedImage, CompressionRaport> CompressedImage::compress(const RGBImage &image,
+                                                                        AbstractQuantizer &quantizer,
+                                                                        ColorSpaces colorSpace, int blockWidth,
+                                                                        int blockHeight, VectorType eps, int N) {
+    if (blockWidth <= 0 || blockHeight <= 0 || N < 0) throw std::invalid_argument("compress: bad block size or bits");
+    ColorSpacePtr cs = getColorSpace(colorSpace);
+    std::vector<Vector> codebook;
+    std::vector<size_t> assigned;
+    VectorType distortion = 0;
+    const auto t0 = std::chrono::system_clock::now();
+    quant_amd::RefineOptions opt;
+    if (quant_amd::engine_lbg_options(quantizer, opt) && engine_sums_exactly(colorSpace)) {
+        std::tie(codebook, assigned, distortion) =
+            quantize_raster(image, colorSpace, blockWidth, blockHeight, eps, N, opt);
+    } else {
+        std::tie(codebook, assigned, distortion) =
+            quantizer.quantize(getBlocksAsVectorsFromImage(image, blockWidth, blockHeight, cs), (size_t)N, eps);
+    }
+    const std::chrono::duration<double> elapsed = std::chrono::system_clock::now() - t0;
+    return pack_compressed(image, codebook, std::move(assigned), cs, colorSpace, Quantizers::LBG, blockWidth,
+                           blockHeight, elapsed);
+}
+
+// The rest of src/Compressor.cpp:107-154 after the quantizer: the file's fields and the raport.
+std::pair<CompressedImage, CompressionRaport> CompressedImage::pack_compressed(
+    const RGBImage &image, const std::vector<Vector> &codebook, std::vector<size_t> assigned, const ColorSpacePtr &cs,
+    ColorSpaces colorSpace, Quantizers quantizer, int blockWidth, int blockHeight,
+    std::chrono::duration<double> elapsed) {
     CompressedImage out;
     out.codeVectors = vectorsToCharVectorsColorSpaced(codebook, cs);
     out.assignedCodeVector = std::move(assigned);

@@ -43,8 +43,17 @@ namespace {
 // copied into one flat fp64 array.  Byte images of the NORMAL or SCALED colour space take the
 // byte engine; any other finite data (CIE1931 values, arbitrary doubles) the engine's exact
 // mode, the reference's arithmetic; non-finite values: std::runtime_error.
+// With refinement (getRefinedLBGQuantizer): qvq_refine continues at K = 2^n from the split levels'
+// result, up to maxIters Lloyd iterations stopped by eps, and with fresh returns the indices of the
+// returned codebook.
 class HipLBGQuantizer : public AbstractQuantizer {
+    size_t maxIters_ = 0;
+    bool fresh_ = false;
+
 public:
+    HipLBGQuantizer() = default;
+    HipLBGQuantizer(size_t maxIters, bool fresh) : maxIters_(maxIters), fresh_(fresh) {}
+    quant_amd::RefineOptions options() const { return {maxIters_, fresh_}; }
     std::tuple<std::vector<Vector>, std::vector<size_t>, VectorType> quantize(const std::vector<Vector> &trainingSet,
                                                                               size_t n, VectorType eps) override {
         using quant_amd::EngineHandle;
@@ -62,6 +71,13 @@ public:
         std::vector<uint32_t> A(N);
         double distortion = 0;
         EngineHandle::check(qvq_lbg(ctx, (uint32_t)n, eps, C.data(), A.data(), &distortion), "qvq_lbg");
+        if (maxIters_ > 0 || fresh_) {
+            if (maxIters_ > 0xFFFFFFFFull) throw std::runtime_error("LBG quantize: too many refinement iterations");
+            EngineHandle::check(qvq_refine(ctx, (uint32_t)K, nullptr, (uint32_t)maxIters_, eps,
+                                           fresh_ ? QVQ_REFINE_FRESH : 0, C.data(), A.data(), &distortion, nullptr,
+                                           nullptr, nullptr),
+                                "qvq_refine");
+        }
         std::vector<Vector> codebook(K, Vector(D));
         for (size_t k = 0; k < K; k++) std::copy(C.begin() + k * D, C.begin() + (k + 1) * D, codebook[k].begin());
         return std::make_tuple(std::move(codebook), std::vector<size_t>(A.begin(), A.end()), distortion);
@@ -70,7 +86,17 @@ public:
 
 }  // namespace
 
+bool quant_amd::engine_lbg_options(const AbstractQuantizer &q, RefineOptions &out) {
+    const HipLBGQuantizer *h = dynamic_cast<const HipLBGQuantizer *>(&q);
+    if (h) out = h->options();
+    return h != nullptr;
+}
+
 QuantizerPtr getQuantizer(Quantizers q) {
     if (q == Quantizers::LBG) return QuantizerPtr(new HipLBGQuantizer());
     return nullptr;
+}
+
+QuantizerPtr getRefinedLBGQuantizer(size_t maxIters, bool fresh) {
+    return QuantizerPtr(new HipLBGQuantizer(maxIters, fresh));
 }

@@ -3,6 +3,7 @@
 #include <stdexcept>
 #include <string>
 
+#include "quant_amd/Quantizer.hpp"
 #include "qvq.h"
 
 namespace quant_amd {
@@ -12,5 +13,14 @@ public:
     static qvq_ctx *get();   // creates the context on first use (device QVQ_DEVICE, default 0)
     static void check(qvq_status st, const char *what);   // throws std::runtime_error
 };
+
+// The refinement an engine LBG quantizer was made with (getRefinedLBGQuantizer; 0 / false for
+// getQuantizer(LBG)); false when q is not the engine's LBG quantizer.  Lets compress() train such
+// a quantizer straight from the raster (device tiling) instead of from host-built vectors.
+struct RefineOptions {
+    size_t maxIters = 0;
+    bool fresh = false;
+};
+bool engine_lbg_options(const AbstractQuantizer &q, RefineOptions &out);
 
 }  // namespace quant_amd

@@ -361,6 +361,45 @@ hipError_t launch_finalize_prep(hipStream_t s, const uint64_t *sums, uint32_t K,
 // 2KD + K apart; copy_gate: copies past the first are read and cleared only if *copy_gate != 0)
 hipError_t launch_finalize(hipStream_t s, const uint64_t *sums, uint32_t K, uint32_t D, int64_t R, int64_t bias,
                            int scale, double *C_cent);
+// Lloyd refinement at fixed K (k_refine.hip, qvq_refine).  One launch in place of
+// launch_finalize_prep, without the split:
+//   tables, sums:      C_cent = C_next = the exact centroids of sums (launch_finalize's rounding),
+//                      the search tables of C_next for the same K (Kpad rows) and, given perm / tint,
+//                      its pruned tile order; host_cb (mapped) gets the codebook;
+//   tables, no sums:   the same tables for the codebook C_src (C_next = C_src's values);
+//   no tables:         nothing written but the distortion term of (C_src, sums).
+// Every form then publishes pub[0] = *changed (launch_count_changed's total, cleared; null: 0),
+// pub[1] = the bits of sum_k (2 c_k.S_k - n_k ||c_k||^2) (0 without sums) and *ready = seq (pub
+// and ready in mapped host memory), and clears clear_cnt[0..1].  gate / cstride: copy 1 of the
+// sums (kd_reduce_kernel's moves), added when *gate != 0 and then cleared.  done: a block counter
+// at 0, left at 0; dist_part: 512 doubles of scratch.
+struct RefineArgs {
+    bool tables = true;
+    const uint64_t *sums = nullptr;
+    const double *C_src = nullptr;
+    uint32_t K = 0, Kpad = 0, D = 0, Dp = 0;
+    int64_t R = 0, bias = 0;
+    int scale = 0;
+    uint64_t cstride = 0;
+    const unsigned *gate = nullptr;
+    double *C_cent = nullptr, *C_next = nullptr;
+    double mu = 0, sx = 0;
+    int t = 0;
+    float *C32 = nullptr;
+    _Float16 *rows = nullptr;
+    float *E32 = nullptr;
+    double *host_cb = nullptr;
+    uint32_t *perm = nullptr;
+    int32_t *tint = nullptr;
+    double *dist_part = nullptr;
+    unsigned *done = nullptr, *changed = nullptr, *clear_cnt = nullptr;
+    uint64_t *pub = nullptr, *ready = nullptr;
+    uint64_t seq = 0;
+};
+hipError_t launch_refine_finalize(hipStream_t s, const RefineArgs &r);
+// *out += the rows i < N with A[i] != B[i] (A, B 16-byte aligned).
+hipError_t launch_count_changed(hipStream_t s, int num_cu, const uint32_t *A, const uint32_t *B, uint64_t N,
+                                unsigned *out);
 // f16 MFMA tables (D = 12) and fp32 VALU table from an fp64 codebook of K code vectors.
 // With E32 (D = 12) also the expanded fp32 table of launch_assign_mfma.
 hipError_t launch_prep(hipStream_t s, const double *C64, uint32_t K, uint32_t Kpad, uint32_t D, uint32_t Dp,

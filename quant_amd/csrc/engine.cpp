@@ -81,6 +81,8 @@ bool make_terms(int cs, Terms &t) {
 using namespace qvq;
 
 constexpr uint32_t SCHED_COUNTERS = 2 * 33 + 2, N_COUNTERS = SCHED_COUNTERS + 2;
+// ... and behind the counters a quantize clears: qvq_refine's rows-changed total (count_changed_kernel)
+constexpr uint32_t CHANGED_COUNTER = N_COUNTERS, N_COUNTERS_ALLOC = N_COUNTERS + 2;
 // Levels whose kd-tree the device builds (k_kdbuild.hip, beside the search): K * D from this up
 // (C4's 48-D levels from K = 512; C3's 12-D trees take the host well under 0.1 ms).
 constexpr uint64_t KDB_MIN_KD = 16384;
@@ -325,6 +327,18 @@ struct qvq_ctx {
     void *h_stage = nullptr;      // pinned staging of qvq_update's results
     uint64_t stage_bytes = 0;
 
+    // qvq_refine's starting point when it is given none: the last successful qvq_lbg or qvq_refine
+    // on the resident rows (K code vectors in d_C64_cent, their assignment in d_A, its distortion);
+    // any other call that touches those buffers ends it.  xsq / rows: sum ||x||^2 and the row count
+    // of the resident rows (from the byte histogram, once per training set)
+    struct RefineState {
+        bool valid = false;
+        uint32_t K = 0;
+        double dist = 0;
+        bool have_xsq = false;
+        double xsq = 0, rows = 0;
+    } rf;
+
     qvq_timings tm;
     HostTrace htrace;
     hipEvent_t ev[32][4];
@@ -555,6 +569,7 @@ void mfma_setup(qvq_ctx *ctx) {
 
 // Allocate the per-row buffers and upload the colour-space tables.
 qvq_status alloc_training(qvq_ctx *ctx, uint64_t N, uint32_t D, int cs) {
+    ctx->rf = qvq_ctx::RefineState();
     if (N == 0 || D == 0) return fail(ctx, QVQ_EINVAL, "empty training set");
     if (N >= (1ull << 32)) return fail(ctx, QVQ_EINVAL, "more than 2^32-1 rows per rank");
     const uint32_t Dp = (D + 3) & ~3u;
@@ -2201,8 +2216,8 @@ QVQ_API qvq_status qvq_create(int hip_device, qvq_ctx **out) {
     *ctx->h_ready = 0;
     if ((e = hipHostGetDevicePointer((void **)&ctx->dh_ready, ctx->h_ready, 0)) != hipSuccess)
         return bail(e, "hipHostGetDevicePointer");
-    if ((e = hipMalloc(&ctx->d_counters, N_COUNTERS * sizeof(unsigned))) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = hipMemset(ctx->d_counters, 0, N_COUNTERS * sizeof(unsigned))) != hipSuccess) return bail(e, "hipMemset");
+    if ((e = hipMalloc(&ctx->d_counters, N_COUNTERS_ALLOC * sizeof(unsigned))) != hipSuccess) return bail(e, "hipMalloc");
+    if ((e = hipMemset(ctx->d_counters, 0, N_COUNTERS_ALLOC * sizeof(unsigned))) != hipSuccess) return bail(e, "hipMemset");
     if ((e = hipMalloc(&ctx->d_hist, 512 * 8)) != hipSuccess) return bail(e, "hipMalloc");
     if ((e = hipMalloc(&ctx->d_decode_stat, 16)) != hipSuccess) return bail(e, "hipMalloc");
     if ((e = hipHostMalloc(&ctx->h_decode_stat, 16, hipHostMallocDefault)) != hipSuccess) return bail(e, "hipHostMalloc");
@@ -2414,6 +2429,7 @@ QVQ_API qvq_status qvq_set_vectors_exact(qvq_ctx *ctx, const double *X, uint64_t
     for (uint64_t i = 0; i < n * dim; i++)
         if (!std::isfinite(X[i])) return fail(ctx, QVQ_EINVAL, "exact mode: training values must be finite");
     HIPCHK(hipSetDevice(ctx->dev));
+    ctx->rf = qvq_ctx::RefineState();
     free_training(ctx);
     free_levels(ctx);
     ctx->N = n;
@@ -2623,6 +2639,7 @@ QVQ_API qvq_status qvq_lbg(qvq_ctx *ctx, uint32_t bits, double eps, double *code
     GUARD(ctx);
     if (ctx->N == 0) return fail(ctx, QVQ_ESTATE, "no training set");
     if (bits > 20) return fail(ctx, QVQ_EINVAL, "bits must be <= 20");
+    ctx->rf.valid = false;
     HIPCHK(hipSetDevice(ctx->dev));
     if (ctx->exact) return lbg_exact(ctx, bits, codebook, assign, distortion);
     const HostPlaceGuard place(ctx);
@@ -2938,7 +2955,8 @@ QVQ_API qvq_status qvq_lbg(qvq_ctx *ctx, uint32_t bits, double eps, double *code
         HIPCHK(host_copy(ctx, assign, ctx->d_A, ctx->N * 4, hipMemcpyDeviceToHost));
     // closed form: sum ||x||^2 - sum_k (2 c_k.S_k - n_k ||c_k||^2) cancels to a few ulps of
     // sum ||x||^2 when the cells are (nearly) exact; a distortion is never negative
-    if (distortion) *distortion = std::max(0.0, (dres[0] - dres[2]) / (dres[1] * (double)ctx->D));
+    const double dist_final = std::max(0.0, (dres[0] - dres[2]) / (dres[1] * (double)ctx->D));
+    if (distortion) *distortion = dist_final;
     for (uint32_t lvl = 1; lvl <= bits; lvl++) {
         // assign: the search kernel; update: the non-fused update; other: the rest of the
         // level up to the next level's search (recheck, kd-tree, reduce, finalize, tables)
@@ -2973,6 +2991,9 @@ QVQ_API qvq_status qvq_lbg(qvq_ctx *ctx, uint32_t bits, double eps, double *code
         ctx->htrace.mark("return");
         std::fprintf(stderr, "%s\n", ctx->htrace.finish().c_str());
     }
+    ctx->rf.valid = true;   // qvq_refine may continue from here
+    ctx->rf.K = Kmax;
+    ctx->rf.dist = dist_final;
     return QVQ_OK;
 }
 
@@ -2981,6 +3002,7 @@ QVQ_API qvq_status qvq_assign(qvq_ctx *ctx, const double *C, uint32_t K, uint32_
     GUARD(ctx);
     if (ctx->N == 0) return fail(ctx, QVQ_ESTATE, "no training set");
     if (!C || K == 0) return fail(ctx, QVQ_EINVAL, "empty codebook");
+    ctx->rf.valid = false;
     HIPCHK(hipSetDevice(ctx->dev));
     qvq_status st = ensure_levels(ctx, K);
     if (st != QVQ_OK) return st;
@@ -3013,6 +3035,7 @@ QVQ_API qvq_status qvq_update(qvq_ctx *ctx, const uint32_t *assign, uint32_t K, 
     GUARD(ctx);
     if (ctx->N == 0) return fail(ctx, QVQ_ESTATE, "no training set");
     if (!assign || K == 0) return fail(ctx, QVQ_EINVAL, "empty assignment");
+    ctx->rf.valid = false;
     for (uint64_t i = 0; i < ctx->N; i++)
         if (assign[i] >= K) return fail(ctx, QVQ_EINVAL, "assignment index out of range");
     HIPCHK(hipSetDevice(ctx->dev));
@@ -3051,6 +3074,7 @@ QVQ_API qvq_status qvq_update_kahan(qvq_ctx *ctx, const uint32_t *assign, uint32
     GUARD(ctx);
     if (ctx->N == 0) return fail(ctx, QVQ_ESTATE, "no training set");
     if (!assign || K == 0) return fail(ctx, QVQ_EINVAL, "empty assignment");
+    ctx->rf.valid = false;
     if (ctx->exact) return qvq_update(ctx, assign, K, C_out, nullptr);   // exact mode: the Kahan chain already
     if (ctx->cs != QVQ_CS_SCALED) return qvq_update(ctx, assign, K, C_out, nullptr);   // integers: exact = Kahan
     for (uint64_t i = 0; i < ctx->N; i++)
@@ -3098,6 +3122,7 @@ QVQ_API qvq_status qvq_update_kahan_split(qvq_ctx *ctx, const uint32_t *assign, 
     if (ctx->N == 0) return fail(ctx, QVQ_ESTATE, "no training set");
     if (ctx->exact || ctx->cs != QVQ_CS_SCALED) return fail(ctx, QVQ_EUNSUPPORTED, "SCALED byte rows only");
     if (!assign || K == 0 || !splits || nsplits == 0) return fail(ctx, QVQ_EINVAL, "empty assignment or splits");
+    ctx->rf.valid = false;
     if (splits[0] != 0 || splits[nsplits] != ctx->N) return fail(ctx, QVQ_EINVAL, "splits must run from 0 to N");
     for (uint32_t i = 0; i < nsplits; i++)
         if (splits[i] > splits[i + 1]) return fail(ctx, QVQ_EINVAL, "splits must not decrease");
@@ -3121,6 +3146,207 @@ QVQ_API qvq_status qvq_update_kahan_split(qvq_ctx *ctx, const uint32_t *assign, 
 // ---------------------------------------------------------------------------------------
 // Decode: CompressedImage::decompress (src/Compressor.cpp:156-165) as one device gather.
 // ---------------------------------------------------------------------------------------
+// Lloyd refinement at fixed K, resident on the device.  Iteration t + 1 is one
+// run_level against C_t -- qvq_assign's searches, recheck and kd-tree ties, with the exact sums of
+// the final assignment -- the reduce, the count of changed rows and refine_finalize_kernel, which
+// writes C_{t+1}, its search tables and tile order, and publishes C_{t+1}, the changed count and
+// the distortion term to mapped memory.  The host waits once per iteration, inside run_level, for
+// the codebook its tree build needs; the stop decision of iteration t comes with that codebook,
+// after the search against C_t is enqueued.  A stop therefore leaves one search in flight: it is
+// the FRESH assignment when that is wanted, and is drained and dropped otherwise.
+QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start, uint32_t max_iters, double eps,
+                              uint32_t flags, double *codebook, uint32_t *assign, double *distortion,
+                              uint64_t *changed, double *dist_trace, qvq_refine_info *info) {
+    if (!ctx) return QVQ_EINVAL;
+    GUARD(ctx);
+    if (ctx->N == 0) return fail(ctx, QVQ_ESTATE, "no training set");
+    const bool fresh = (flags & QVQ_REFINE_FRESH) != 0;
+    if (flags & ~(uint32_t)QVQ_REFINE_FRESH) return fail(ctx, QVQ_EINVAL, "unknown refine flags");
+    if (max_iters == 0 && !fresh) return fail(ctx, QVQ_EINVAL, "max_iters = 0 needs QVQ_REFINE_FRESH");
+    if (K == 0 || K > (1u << 20)) return fail(ctx, QVQ_EINVAL, "K must be in 1 .. 2^20");
+    if (!(eps >= 0)) return fail(ctx, QVQ_EINVAL, "eps must be >= 0");
+    if (ctx->exact) return fail(ctx, QVQ_EUNSUPPORTED, "refinement of an exact-mode training set is not supported");
+    if (ctx->comm || ctx->host_ar)
+        return fail(ctx, QVQ_EUNSUPPORTED, "refinement with a communicator joined is not supported");
+    const bool cont = C_start == nullptr;
+    if (cont) {
+        if (!ctx->rf.valid) return fail(ctx, QVQ_ESTATE, "no qvq_lbg or qvq_refine result to continue from");
+        if (ctx->rf.K != K) return fail(ctx, QVQ_EINVAL, "K differs from the result to continue from");
+    } else {
+        double vmin = ctx->terms.v64[0], vmax = ctx->terms.v64[0];
+        for (int b = 1; b < 256; b++) {
+            vmin = std::min(vmin, ctx->terms.v64[b]);
+            vmax = std::max(vmax, ctx->terms.v64[b]);
+        }
+        // (the searches' error bands assume |c| <= 1.2 vmax: valu_coeffs, mf_th)
+        for (uint64_t i = 0; i < (uint64_t)K * ctx->D; i++)
+            if (!(C_start[i] >= vmin && C_start[i] <= vmax))
+                return fail(ctx, QVQ_EINVAL, "starting codebook outside the colour space's value range");
+    }
+    const double d0 = ctx->rf.dist;
+    ctx->rf.valid = false;
+    HIPCHK(hipSetDevice(ctx->dev));
+    qvq_status st = ensure_levels(ctx, std::max<uint32_t>(K, 2));
+    if (st != QVQ_OK) return st;
+    if (!ctx->d_A_alt) HIPCHK(hipMalloc(&ctx->d_A_alt, ctx->N * 4));
+    std::memset(&ctx->tm, 0, sizeof(ctx->tm));
+    const uint32_t D = ctx->D;
+    const uint64_t KD = (uint64_t)K * D;
+    if (!ctx->rf.have_xsq) {   // sum ||x||^2 and the rows, from the byte histogram
+        uint64_t hist[256];
+        HIPCHK(hipMemcpy(hist, ctx->d_hist, sizeof(hist), hipMemcpyDeviceToHost));
+        long double sq = 0;
+        uint64_t n = 0;
+        for (int b = 0; b < 256; b++) {
+            sq += (long double)hist[b] * (long double)ctx->terms.v64[b] * (long double)ctx->terms.v64[b];
+            n += hist[b];
+        }
+        ctx->rf.xsq = (double)sq;
+        ctx->rf.rows = (double)(n / D);
+        ctx->rf.have_xsq = true;
+    }
+    const double xsq = ctx->rf.xsq, norm = ctx->rf.rows * (double)D;
+    if (!cont) HIPCHK(hipMemcpy(ctx->d_C64_cent, C_start, KD * 8, hipMemcpyHostToDevice));
+    // both iterations' counters, the changed total; copy 1 of the sums if a quantize left it dirty
+    HIPCHK(hipMemsetAsync(ctx->d_counters, 0, 4 * sizeof(unsigned), ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->d_counters + CHANGED_COUNTER, 0, 2 * sizeof(unsigned), ctx->stream));
+    if (ctx->sums1_dirty) {
+        HIPCHK(hipMemsetAsync(ctx->d_sums, 0, ctx->sums_bytes, ctx->stream));
+        ctx->sums1_dirty = false;
+    }
+    ctx->kd_pend = false;
+    ctx->pub = PubArgs();
+    const Terms &T = ctx->terms;
+    const bool prune = use_prune(ctx, K);
+    volatile uint64_t *h_pub = ctx->h_ready + 4;   // [4] rows changed, [5] the distortion term
+    // C_t's tables, tile order and host copy (t = 0: from the starting codebook; else the centroid step)
+    auto publish = [&](uint32_t t, bool tables, const uint64_t *sums, const unsigned *gate, unsigned *cnts,
+                       bool count) -> qvq_status {
+        RefineArgs r;
+        r.tables = tables;
+        r.sums = sums;
+        r.C_src = ctx->d_C64_cent;
+        r.K = K;
+        r.Kpad = pad32(K);
+        r.D = D;
+        r.Dp = ctx->Dp;
+        r.R = T.R;
+        r.bias = T.bias;
+        r.scale = T.scale;
+        r.cstride = sums_cap_stride(ctx);
+        r.gate = gate;
+        r.C_cent = ctx->d_C64_cent;
+        r.C_next = ctx->d_C64_split;
+        r.mu = T.mu;
+        r.sx = T.sx;
+        r.t = ctx->mf_t;
+        r.C32 = ctx->d_C32;
+        r.rows = ctx->d_rows;
+        r.E32 = ctx->d_E32;
+        r.host_cb = tables ? dev_cb_of(ctx, t) : nullptr;
+        r.perm = tables && prune ? ctx->d_perm : nullptr;
+        r.tint = ctx->d_tint;
+        r.dist_part = ctx->d_dist_part + 8;
+        r.done = ctx->d_counters + 2 * 33;
+        r.changed = count ? ctx->d_counters + CHANGED_COUNTER : nullptr;
+        r.clear_cnt = cnts;
+        r.pub = ctx->dh_ready + 4;
+        r.ready = ctx->dh_ready;
+        r.seq = ++ctx->seq;
+        HIPCHK(launch_refine_finalize(ctx->stream, r));
+        if (tables) ctx->perm_k = prune ? K : 0;
+        return QVQ_OK;
+    };
+    // the sums of the assignment run_level just made, reduced into d_sums (as qvq_lbg's level)
+    auto reduce = [&](int slot, const unsigned *&gate) -> qvq_status {
+        const unsigned *tcnt = ctx->d_counters + 2 * slot + 1;
+        gate = ctx->sums_copies > 1 ? tcnt : nullptr;
+        if (ctx->kd_pend) {
+            ctx->sums1_dirty = true;
+            HIPCHK(launch_kd_reduce(ctx->stream, ctx->d_codes, ctx->Dp, D, ctx->d_ties, tcnt, ctx->d_C64_split, K,
+                                    ctx->d_lut64, ctx->pend_kd, ctx->d_A, ctx->d_plut, ctx->d_part, ctx->d_part_cnt,
+                                    ctx->nslabs, ctx->nsub, ctx->d_sums, ctx->d_sums + sums_cap_stride(ctx)));
+            ctx->kd_pend = false;
+        } else if (ctx->nslabs) {
+            HIPCHK(launch_reduce(ctx->stream, ctx->d_part, ctx->d_part_cnt, ctx->nslabs, ctx->nsub, K, D, ctx->d_sums));
+        }
+        return QVQ_OK;
+    };
+    if ((st = publish(0, true, nullptr, nullptr, nullptr, false)) != QVQ_OK) return st;
+
+    uint32_t t = 0;        // iterations done: C_t is the codebook, A_t (t >= 1, or continuing) in d_A
+    int stop = -1;
+    bool have_A = cont, have_dprev = cont;
+    double d_prev = d0, d_last = d0;
+    // iteration t's published count and distortion, and the stop rule
+    auto absorb = [&]() {
+        std::atomic_thread_fence(std::memory_order_acquire);
+        const uint64_t chg = (t == 1 && !cont) ? ctx->N : h_pub[0];
+        const uint64_t bits = h_pub[1];
+        double term;
+        std::memcpy(&term, &bits, 8);
+        const double d = std::max(0.0, (xsq - term) / norm);
+        if (changed) changed[t - 1] = chg;
+        if (dist_trace) dist_trace[t - 1] = d;
+        if (chg == 0) stop = QVQ_STOP_FIXED;
+        else if (have_dprev && std::fabs(d_prev - d) / d_prev <= eps) stop = QVQ_STOP_EPS;
+        else if (t == max_iters) stop = QVQ_STOP_MAXIT;
+        d_prev = d_last = d;
+        have_dprev = true;
+    };
+    for (;;) {
+        if (t == max_iters && !fresh) {   // the last iteration's results; nothing else is in flight
+            if ((st = wait_codebook(ctx, ctx->seq)) != QVQ_OK) return st;
+            absorb();
+            break;
+        }
+        const int slot = (int)(t & 1);
+        if (have_A) std::swap(ctx->d_A, ctx->d_A_alt);   // d_A_alt: A_t; d_A takes the search against C_t
+        if ((st = run_level(ctx, K, slot, true, host_cb_of(ctx, t), ctx->seq)) != QVQ_OK) return st;
+        if (t >= 1) absorb();   // (run_level waited for C_t)
+        else if (max_iters == 0) stop = QVQ_STOP_MAXIT;
+        const unsigned *gate = nullptr;
+        if (stop >= 0) {
+            if (fresh) {   // the search in flight is A* = assign(C_t): its sums, the distortion of (C_t, A*)
+                if ((st = reduce(slot, gate)) != QVQ_OK) return st;
+                if ((st = publish(t, false, ctx->d_sums, gate, ctx->d_counters + 2 * slot, false)) != QVQ_OK) return st;
+                ctx->sums1_dirty = false;
+                if ((st = wait_codebook(ctx, ctx->seq)) != QVQ_OK) return st;
+                std::atomic_thread_fence(std::memory_order_acquire);
+                const uint64_t bits = h_pub[1];
+                double term;
+                std::memcpy(&term, &bits, 8);
+                d_last = std::max(0.0, (xsq - term) / norm);
+            } else {   // dropped: A_t stays the assignment
+                ctx->kd_pend = false;
+                if (have_A) std::swap(ctx->d_A, ctx->d_A_alt);
+                if ((st = wait_stream(ctx)) != QVQ_OK) return st;
+            }
+            break;
+        }
+        if ((st = reduce(slot, gate)) != QVQ_OK) return st;
+        if (have_A) HIPCHK(launch_count_changed(ctx->stream, ctx->num_cu, ctx->d_A, ctx->d_A_alt, ctx->N,
+                                                ctx->d_counters + CHANGED_COUNTER));
+        if ((st = publish(t + 1, true, ctx->d_sums, gate, ctx->d_counters + 2 * slot, have_A)) != QVQ_OK) return st;
+        ctx->sums1_dirty = false;
+        have_A = true;
+        t++;
+    }
+    // C_t as refine_finalize_kernel published it (t = 0: the starting codebook's copy)
+    if (codebook) std::memcpy(codebook, host_cb_of(ctx, t), KD * 8);
+    if (assign) HIPCHK(host_copy(ctx, assign, ctx->d_A, ctx->N * 4, hipMemcpyDeviceToHost));
+    if (distortion) *distortion = d_last;
+    if (info) {
+        info->iters = t;
+        info->stop = (uint32_t)stop;
+    }
+    (void)hipGetLastError();
+    ctx->rf.valid = true;
+    ctx->rf.K = K;
+    ctx->rf.dist = d_last;
+    return QVQ_OK;
+}
+
 static qvq_status check_decode_args(qvq_ctx *ctx, uint32_t K, uint64_t nblocks, uint32_t xSize, uint32_t ySize,
                                     uint32_t bw, uint32_t bh) {
     if (!ctx) return QVQ_EINVAL;
