@@ -277,6 +277,28 @@ QVQ_API qvq_status qvq_host_finalize(const uint64_t *hi, const uint64_t *lo, con
  * (dim entries each) -- for the host-side sharding tests. */
 QVQ_API qvq_status qvq_host_row_terms(const uint8_t *codes, uint32_t dim, int colorspace, uint64_t *hi,
                                       uint64_t *lo);
+/* The kernels a shape dispatches to: a training set of n rows of dim components and a codebook of K
+ * code vectors (qvq_assign, qvq_update, or a qvq_lbg level of that K), answered by the predicates
+ * the engine itself dispatches with, under the same QVQ_SEARCH / QVQ_KDTREE environment.  For
+ * tests that want a given path to run (tests/helpers/largek_cases.py). */
+enum { QVQ_PLAN_SEARCH_SMALL = 0, QVQ_PLAN_SEARCH_MF32 = 1, QVQ_PLAN_SEARCH_WIDE = 2, QVQ_PLAN_SEARCH_VALU = 3 };
+enum { QVQ_PLAN_RECHECK_MF32 = 0, QVQ_PLAN_RECHECK_STAGED = 1, QVQ_PLAN_RECHECK_CHUNKED = 2,
+       QVQ_PLAN_RECHECK_GLOBAL = 3 };
+enum { QVQ_PLAN_UPDATE_RUNS = 0, QVQ_PLAN_UPDATE_SORTED = 1, QVQ_PLAN_UPDATE_LDS = 2 };
+typedef struct {
+    uint32_t search;        /* QVQ_PLAN_SEARCH_SMALL | _MF32 | _WIDE | _VALU */
+    uint32_t fused;         /* sums fused into the search (qvq_lbg levels only) */
+    uint32_t c32_staged;    /* MF32: fp32 codebook in LDS (the unfused, unpruned search of qvq_assign) */
+    uint32_t cb_resident;   /* WIDE: whole codebook in LDS (else streamed slices) */
+    uint32_t valu_tiles;    /* VALU: codebook tiles, ceil(K / KT) */
+    uint32_t recheck;       /* QVQ_PLAN_RECHECK_MF32 | _STAGED | _CHUNKED | _GLOBAL */
+    uint32_t update;        /* QVQ_PLAN_UPDATE_RUNS | _SORTED | _LDS */
+    uint32_t update_copies; /* RUNS: LDS copies;  LDS: passes */
+    uint32_t prune;         /* a qvq_lbg level of this K searches in pruned order */
+    uint32_t device_tree;   /* kd-tree of this K can be built on the device (QVQ_KDTREE=device runs
+                               that build; QVQ_KDTREE=host builds no tree image: 0) */
+} qvq_plan;
+QVQ_API qvq_status qvq_host_plan(uint32_t dim, uint32_t K, uint64_t n, qvq_plan *out);
 /* The engine's bounded-wait policy (quant_amd/csrc/wait.hpp) driven by scripted probes, for
  * tests: scenario 0 the work publishes after ~5 ms; 1 it never does, no communicator; 2 it
  * never does, a healthy communicator; 3 the communicator reports an error after ~5 ms; 4 the

@@ -37,6 +37,16 @@ class _Timings(ctypes.Structure):
                 ("kahan_relays", ctypes.c_int), ("mean_ms", ctypes.c_double)]
 
 
+class _Plan(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_uint32) for f in ("search", "fused", "c32_staged", "cb_resident", "valu_tiles",
+                                                "recheck", "update", "update_copies", "prune", "device_tree")]
+
+
+# qvq_plan enumerators (qvq.h)
+PLAN_SEARCH_SMALL, PLAN_SEARCH_MF32, PLAN_SEARCH_WIDE, PLAN_SEARCH_VALU = 0, 1, 2, 3
+PLAN_RECHECK_MF32, PLAN_RECHECK_STAGED, PLAN_RECHECK_CHUNKED, PLAN_RECHECK_GLOBAL = 0, 1, 2, 3
+PLAN_UPDATE_RUNS, PLAN_UPDATE_SORTED, PLAN_UPDATE_LDS = 0, 1, 2
+
 _lib = None
 EXPORTED = ["qvq_create", "qvq_destroy", "qvq_last_error", "qvq_version", "qvq_set_images",
             "qvq_set_images_device", "qvq_set_synthetic", "qvq_set_vectors", "qvq_num_vectors",
@@ -45,7 +55,7 @@ EXPORTED = ["qvq_create", "qvq_destroy", "qvq_last_error", "qvq_version", "qvq_s
             "qvq_host_finalize", "qvq_host_row_terms", "qvq_decode", "qvq_decode_mse", "qvq_decode_device",
             "qvq_set_timeout", "qvq_host_wait_probe", "qvq_comm_init_host", "qvq_comm_info", "qvq_set_vectors_exact",
             "qvq_update_kahan_split", "qvq_host_pool_stress", "qvq_kdtree_device_check",
-            "qvq_host_kdtree_image", "qvq_refine"]
+            "qvq_host_kdtree_image", "qvq_refine", "qvq_host_plan"]
 
 COMM_NONE, COMM_RCCL, COMM_HOST = 0, 1, 2
 REFINE_FRESH = 1                              # qvq_refine flags
@@ -98,6 +108,7 @@ def lib():
             "qvq_comm_init_host": ([P, i, i, ALLREDUCE_FN, P], i),
             "qvq_comm_info": ([P, ctypes.POINTER(i), ctypes.POINTER(i), ctypes.POINTER(i)], i),
             "qvq_refine": ([P, u32, P, u32, ctypes.c_double, u32, P, P, P, P, P, P], i),
+            "qvq_host_plan": ([u32, u32, u64, ctypes.POINTER(_Plan)], i),
         }
         for name, (args, res) in sig.items():
             if os.environ.get("QVQ_LIB") and not hasattr(L, name):
@@ -379,6 +390,14 @@ def host_kdtree_nn(C, Q):
     out = np.empty(Q.shape[0], np.uint32)
     _check(lib().qvq_host_kdtree_nn(_p(C), C.shape[0], C.shape[1], _p(Q), Q.shape[0], _p(out)))
     return out
+
+
+def host_plan(dim, K, n):
+    """The kernels the engine dispatches to for n rows of dim components and K code vectors
+    (qvq_host_plan, under the current QVQ_SEARCH / QVQ_KDTREE): a dict of the qvq_plan fields."""
+    p = _Plan()
+    _check(lib().qvq_host_plan(int(dim), int(K), int(n), ctypes.byref(p)))
+    return {f: int(getattr(p, f)) for f, _ in _Plan._fields_}
 
 
 # KdbNode (kdtree_dev.hpp) and the image layout of qvq_host_kdtree_image

@@ -107,6 +107,8 @@ hipError_t launch_decode(hipStream_t s, const uint8_t *cb, uint32_t K, uint32_t 
 hipError_t launch_tile(hipStream_t s, const uint8_t *rgb, uint8_t *codes, uint32_t n_images, uint32_t xSize,
                        uint32_t ySize, uint32_t bw, uint32_t bh, uint32_t D, uint32_t Dp, uint8_t pad);
 // VALU fp32 search for any Dp (multiple of 4, <= 64); codebook C32 [K][Dp].
+// assign_valu_tile: code vectors per LDS tile (KT; K <= KT: the whole codebook, one tile).
+uint32_t assign_valu_tile(uint32_t Dp, uint32_t K);
 hipError_t launch_assign_valu(hipStream_t s, int num_cu, uint32_t Dp, const uint8_t *codes, uint64_t N,
                               const float *C32, uint32_t K, const float *lut32, float alpha, float beta, float gamma,
                               uint32_t *A, uint32_t *flags, unsigned *flag_cnt);
@@ -218,6 +220,7 @@ struct MfThresholds {
 };
 uint32_t mf_fuse_max_k();
 bool mf_can_search(uint32_t K);
+bool mf_small_search(uint32_t K);   // launch_assign_mfma: the small-K scan (given E32)
 // K <= 32: expanded fp32 scores from E32 [Kp][16] = [c''(0..11) | n | 0 0 0] (the MFMA row's
 // terms in fp32; padding rows n = 1e30).
 // perm / tint (finalize's prune_order, K <= PRUNE_MAXK): the pruned tile order of the MFMA
@@ -233,6 +236,8 @@ hipError_t launch_assign_mfma(hipStream_t s, int grid, bool fuse, const uint8_t 
 // for K above the small-K scan whenever mf32_fits.
 bool mf32_fits(uint32_t K, bool fuse);
 bool mf32_prune_fits(uint32_t K, bool fuse);
+// the fp32 codebook (the flagged rows' recompute) sits in LDS beside the MFMA rows
+bool mf32_c32_staged(uint32_t K, bool fuse, bool prune);
 hipError_t launch_assign_mf32(hipStream_t s, int grid, bool fuse, const uint8_t *codes, uint64_t N,
                               const _Float16 *cb_rows, uint32_t K, const float *C32, const uint64_t *plut,
                               const MfThresholds &th, uint32_t *A, uint32_t *flags, unsigned *flag_cnt,
@@ -263,6 +268,10 @@ hipError_t launch_assign_wide(hipStream_t s, int num_cu, uint32_t Dp, uint32_t D
 // search's); exact ties are listed in ties (tie_cnt) for launch_kd_resolve or the host.
 // With xslab != nullptr adds every other row's packed terms (hi << 32 | lo) to xslab [d][k]
 // and its count to xcnt [k] (the search's extra slab G).
+// recheck_path: the fp32 codebook whole in LDS, swept in LDS chunks (Dp = 12, 48), or read from
+// global memory.
+enum class RecheckPath { Staged, Chunked, Global };
+RecheckPath recheck_path(uint32_t Dp, uint32_t K);
 hipError_t launch_recheck(hipStream_t s, int num_cu, const uint8_t *codes, uint32_t Dp, uint32_t D,
                           const uint32_t *flags, const unsigned *flag_cnt, const double *C64, const float *C32,
                           uint32_t K, const double *lut64, float alpha, float beta, float gamma, double tie_rel, double tie_abs,
@@ -298,6 +307,13 @@ hipError_t launch_kd_resolve(hipStream_t s, const uint8_t *codes, uint32_t Dp, u
                              const unsigned *tie_cnt, const double *C64, uint32_t K, const double *lut64,
                              const KdView &kd, uint32_t *A, uint64_t *xslab, uint32_t *xcnt, const uint64_t *plut,
                              uint64_t *xsums = nullptr);   // xsums: moves into a final-sums copy (move_row_sums)
+// update_plan: register runs into `copies` LDS replicas of the sums (update_runs_kernel), or
+// `passes` passes of KR code vectors each over the rows (update_kernel); KR = 0: no room at all.
+struct UpdatePlan {
+    bool runs;
+    uint32_t copies, KR, passes;
+};
+UpdatePlan update_plan(uint32_t K, uint32_t D);
 hipError_t launch_update(hipStream_t s, uint32_t Dp, uint32_t G, const uint8_t *codes, uint64_t N, const uint32_t *A,
                          uint32_t K, uint32_t D, const uint64_t *plut, uint64_t *part, uint32_t *part_cnt);
 // Sums of a final assignment straight into sums [hi KD][lo KD][cnt K] (no slabs, no reduce)

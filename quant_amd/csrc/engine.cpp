@@ -389,6 +389,7 @@ double tie_band(const qvq_ctx *ctx);
 // The path knobs a test exercises: QVQ_SEARCH=valu (the VALU search at every K) and
 // QVQ_KDTREE=host (ties answered on the host); QVQ_KAHAN=0 / QVQ_SPECULATE=0 (index rule and
 // schedule); QVQ_KAHAN_FAIL_LEVEL / _RANK (forced check failures).
+// qvq_host_plan reports what the predicates below pick for a shape.
 bool env_is(const char *name, const char *val) {
     const char *v = std::getenv(name);
     return v && std::strcmp(v, val) == 0;
@@ -404,6 +405,11 @@ bool use_wide(const qvq_ctx *ctx, uint32_t K) {
     return ctx->D != MF_D && wide_can_search(ctx->Dp) && K >= WIDE_MIN_K && !env_is("QVQ_SEARCH", "valu");
 }
 bool use_fused(const qvq_ctx *ctx, uint32_t K) { return use_mfma(ctx, K) && K <= mf_fuse_max_k(); }
+// the MFMA recheck from K = 512 (below it the fp32 pass over K code vectors is cheaper than
+// staging the MFMA tables, profiles/r02f)
+bool use_recheck_mf32(const qvq_ctx *ctx, uint32_t K) {
+    return K >= 512 && use_mfma(ctx, K) && recheck_mf32_fits(K);
+}
 // Pruned MFMA search (k_mf32.hip PRUNE: tiles outside a chunk's provable window skipped) for
 // D = 12 from K = 256 (from K = 128 it measured slower, profiles/r05ao) up to prune_order's
 // capacity.  Its order is computed by the previous level's finalize.  Other D
@@ -1003,9 +1009,10 @@ bool device_tree_on() {
     static const bool on = env_is("QVQ_KDTREE", "device");
     return on;
 }
+// the shapes the device build takes (its LDS arrays) and is worth a launch for
+bool device_tree_shape(uint32_t K, uint32_t D) { return kd_build_fits(K, D) && (uint64_t)K * D >= KDB_MIN_KD; }
 bool use_device_tree(const qvq_ctx *ctx, uint32_t K) {
-    return device_tree_on() && ctx->kdb_cap >= K && !ctx->exact && kd_build_fits(K, ctx->D) &&
-           (uint64_t)K * ctx->D >= KDB_MIN_KD;
+    return device_tree_on() && ctx->kdb_cap >= K && !ctx->exact && device_tree_shape(K, ctx->D);
 }
 
 // Enqueue the device build of the tree over the K code vectors in d_C64_split on kstream, after
@@ -1324,9 +1331,7 @@ qvq_status run_level(qvq_ctx *ctx, uint32_t K, int slot, bool sums_out, const do
                                   ctx->d_lut32, alpha, beta, gamma, ctx->d_A, ctx->d_flags, &cnt[0]));
     }
     if (timing) HIPCHK(hipEventRecord(ctx->ev[slot][1], ctx->stream));
-    // the MFMA recheck from K = 512 (below it the fp32 pass over K code vectors is cheaper than
-    // staging the MFMA tables, profiles/r02f)
-    if (K >= 512 && use_mfma(ctx, K) && recheck_mf32_fits(K)) {
+    if (use_recheck_mf32(ctx, K)) {
         HIPCHK(launch_recheck_mf32(ctx->stream, ctx->num_cu, ctx->d_codes, ctx->d_flags, &cnt[0], ctx->d_rows,
                                    ctx->d_C64_split, K, ctx->d_lut64, ctx->mf_th, 1e-12, tie_band(ctx), ctx->d_A, ctx->d_ties,
                                    &cnt[1], xslab, xcnt, ctx->d_plut));
@@ -3613,6 +3618,50 @@ QVQ_API qvq_status qvq_host_finalize(const uint64_t *hi, const uint64_t *lo, con
     for (uint64_t k = 0; k < K; k++)
         for (uint32_t d = 0; d < dim; d++)
             C_out[k * dim + d] = centroid_value(hi[k * dim + d], lo[k * dim + d], cnt[k], t.R, t.bias, t.scale);
+    return QVQ_OK;
+}
+
+QVQ_API qvq_status qvq_host_plan(uint32_t dim, uint32_t K, uint64_t n, qvq_plan *out) {
+    if (!out || dim == 0 || K == 0 || n == 0) return QVQ_EINVAL;
+    std::unique_ptr<qvq_ctx> ctx(new qvq_ctx());   // the shape only: no device work
+    ctx->D = dim;
+    ctx->Dp = (dim + 3) & ~3u;
+    ctx->N = n;
+    if (ctx->Dp > 64) return QVQ_EINVAL;
+    qvq_plan p;
+    std::memset(&p, 0, sizeof(p));
+    // run_level's order of questions
+    if (use_mfma(ctx.get(), K)) {
+        p.search = mf_small_search(K) ? QVQ_PLAN_SEARCH_SMALL : QVQ_PLAN_SEARCH_MF32;
+        p.fused = use_fused(ctx.get(), K);
+    } else if (use_wide(ctx.get(), K)) {
+        p.search = QVQ_PLAN_SEARCH_WIDE;
+        p.cb_resident = wide_codebook_resident(ctx->Dp, K);
+    } else {
+        p.search = QVQ_PLAN_SEARCH_VALU;
+        const uint32_t KT = assign_valu_tile(ctx->Dp, K);
+        p.valu_tiles = (K + KT - 1) / KT;
+    }
+    p.prune = use_prune(ctx.get(), K);
+    if (p.search == QVQ_PLAN_SEARCH_MF32) p.c32_staged = mf32_c32_staged(K, false, false);
+    if (use_recheck_mf32(ctx.get(), K)) {
+        p.recheck = QVQ_PLAN_RECHECK_MF32;
+    } else {
+        switch (recheck_path(ctx->Dp, K)) {
+        case RecheckPath::Staged: p.recheck = QVQ_PLAN_RECHECK_STAGED; break;
+        case RecheckPath::Chunked: p.recheck = QVQ_PLAN_RECHECK_CHUNKED; break;
+        case RecheckPath::Global: p.recheck = QVQ_PLAN_RECHECK_GLOBAL; break;
+        }
+    }
+    if (use_sorted_sums(ctx.get(), K)) {
+        p.update = QVQ_PLAN_UPDATE_SORTED;
+    } else {
+        const UpdatePlan up = update_plan(K, dim);
+        p.update = up.runs ? QVQ_PLAN_UPDATE_RUNS : QVQ_PLAN_UPDATE_LDS;
+        p.update_copies = up.runs ? up.copies : up.passes;
+    }
+    p.device_tree = !env_is("QVQ_KDTREE", "host") && device_tree_shape(K, dim);
+    *out = p;
     return QVQ_OK;
 }
 

@@ -50,6 +50,7 @@ bool mf_can_search(uint32_t K) { return mf_lds_layout(K, false, false).total <= 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int MF_SMALL_K = 32;
+bool mf_small_search(uint32_t K) { return K <= MF_SMALL_K; }
 
 // ---------------------------------------------------------------------------------------
 // Small codebooks (K <= MF_SMALL_K): direct fp32 scan of all SK code vectors per row, rows in
@@ -308,7 +309,7 @@ hipError_t launch_assign_mfma(hipStream_t s, int grid, bool fuse, const uint8_t 
                               uint64_t *part, uint32_t *part_cnt, const uint32_t *perm, const int32_t *tint,
                               uint64_t *z1, uint32_t nz1) {
     if (!fuse) z1 = nullptr, nz1 = 0;   // (cleared by the fused kernels' set-up only)
-    if (K <= MF_SMALL_K && E32) {   // E32 is padded up to 32 rows (n = 1e30)
+    if (mf_small_search(K) && E32) {   // E32 is padded up to 32 rows (n = 1e30)
         const uint32_t sk = K <= 2 ? 2 : K <= 4 ? 4 : K <= 8 ? 8 : K <= 16 ? 16 : 32;
         // rows per lane: a multiple of 4 covering N over grid x waves x 64 lanes
         const uint32_t copies = fuse ? small_copies(sk) : 1;
@@ -455,10 +456,14 @@ __global__ __launch_bounds__(ASSIGN_THREADS) void assign_valu_kernel(
 
 #define QVQ_FOR_EACH_DP(X) X(4) X(8) X(12) X(16) X(20) X(24) X(28) X(32) X(36) X(40) X(44) X(48) X(52) X(56) X(60) X(64)
 
+uint32_t assign_valu_tile(uint32_t Dp, uint32_t K) {
+    return std::min<uint32_t>(K, (ASSIGN_LDS_BYTES - 1024) / (Dp * 4));
+}
+
 hipError_t launch_assign_valu(hipStream_t s, int num_cu, uint32_t Dp, const uint8_t *codes, uint64_t N,
                               const float *C32, uint32_t K, const float *lut32, float alpha, float beta, float gamma,
                               uint32_t *A, uint32_t *flags, unsigned *flag_cnt) {
-    const uint32_t KT = std::min<uint32_t>(K, (ASSIGN_LDS_BYTES - 1024) / (Dp * 4));
+    const uint32_t KT = assign_valu_tile(Dp, K);
     const size_t lds = 1024 + (size_t)KT * Dp * 4;
     switch (Dp) {
 #define X(DPV)                                                                                                 \
@@ -828,6 +833,14 @@ static void launch_recheck_variant(hipStream_t s, int grid, size_t lds, const ui
                        flag_cnt, C64, C32, K, lut64, alpha, beta, gamma, tie_rel, tie_abs, A, ties, tie_cnt, xslab, xcnt, plut);
 }
 
+static size_t recheck_cb_bytes(uint32_t Dp, uint32_t K) { return (size_t)K * recheck_c32_stride(Dp) * 4; }
+
+RecheckPath recheck_path(uint32_t Dp, uint32_t K) {
+    if (RECHECK_LDS_BASE + recheck_cb_bytes(Dp, K) <= RECHECK_LDS) return RecheckPath::Staged;
+    // too big for LDS: the chunked sweep for the widths it is built for
+    return Dp == 12 || Dp == 48 ? RecheckPath::Chunked : RecheckPath::Global;
+}
+
 hipError_t launch_recheck(hipStream_t s, int num_cu, const uint8_t *codes, uint32_t Dp, uint32_t D,
                           const uint32_t *flags, const unsigned *flag_cnt, const double *C64, const float *C32,
                           uint32_t K, const double *lut64, float alpha, float beta, float gamma, double tie_rel, double tie_abs,
@@ -835,11 +848,10 @@ hipError_t launch_recheck(hipStream_t s, int num_cu, const uint8_t *codes, uint3
                           const uint64_t *plut, const uint32_t *perm, const int32_t *tint, float qscale) {
     if (Dp % 4 || Dp > 64) return hipErrorInvalidValue;
     const size_t base = RECHECK_LDS_BASE;
-    const size_t cb = (size_t)K * recheck_c32_stride(Dp) * 4;
-    const bool staged = base + cb <= RECHECK_LDS;
-    const size_t lds = base + (staged ? cb : 0);
-    // too big for LDS: the chunked sweep for the widths it is built for
-    if (!staged && (Dp == 12 || Dp == 48)) {
+    const RecheckPath path = recheck_path(Dp, K);
+    const bool staged = path == RecheckPath::Staged;
+    const size_t lds = base + (staged ? recheck_cb_bytes(Dp, K) : 0);
+    if (path == RecheckPath::Chunked) {
         const size_t clds = base + (size_t)RC_CHUNK * recheck_c32_stride(Dp) * 4;
         if (Dp == 12)
             hipLaunchKernelGGL(recheck_chunked_kernel<12>, dim3(num_cu), dim3(RECHECK_THREADS), clds, s, codes, Dp, D,

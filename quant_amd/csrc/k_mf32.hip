@@ -720,6 +720,10 @@ bool mf32_prune_fits(uint32_t K, bool fuse) {
     return K <= 65536 && m32_lds_layout(K, fuse, false, 1, true).total <= M32_LDS_MAX;
 }
 
+bool mf32_c32_staged(uint32_t K, bool fuse, bool prune) {
+    return m32_lds_layout(K, fuse, true, 1, prune).total <= M32_LDS_MAX;
+}
+
 hipError_t launch_assign_mf32(hipStream_t s, int grid, bool fuse, const uint8_t *codes, uint64_t N,
                               const _Float16 *cb_rows, uint32_t K, const float *C32, const uint64_t *plut,
                               const MfThresholds &th, uint32_t *A, uint32_t *flags, unsigned *flag_cnt,
@@ -729,7 +733,7 @@ hipError_t launch_assign_mf32(hipStream_t s, int grid, bool fuse, const uint8_t 
     if (!fuse) z1 = nullptr, nz1 = 0;   // (cleared in the fused set-up block only)
     const bool prune = perm && tint;
     if (prune && !mf32_prune_fits(K, fuse)) return hipErrorInvalidValue;
-    const bool staged = m32_lds_layout(K, fuse, true, 1, prune).total <= M32_LDS_MAX;
+    const bool staged = mf32_c32_staged(K, fuse, prune);
     // sums copies (fused, 64 <= K <= 512): the most, up to 16, that fit.  With the padded copy
     // strides, C3: K = 64 / 128 / 256 / 512 -6 / -22 / -19 / -16 us against the wave run
     // reduction; K = 1024 has no room for a second copy (the run reduction at the pruned K = 256:

@@ -280,10 +280,18 @@ __global__ __launch_bounds__(urun_threads(DP)) void update_runs_kernel(const uin
     }
 }
 
+UpdatePlan update_plan(uint32_t K, uint32_t D) {
+    if (update_runs_fits(K, D)) return UpdatePlan{true, urun_copies(K, D), 0, 0};
+    const size_t per_k = (size_t)D * 8 + 4;
+    const uint32_t KR = (uint32_t)std::min<size_t>(K, (UPDATE_LDS - 2048 - 16) / per_k);
+    return UpdatePlan{false, 0, KR, KR ? (K + KR - 1) / KR : 0};
+}
+
 hipError_t launch_update(hipStream_t s, uint32_t Dp, uint32_t G, const uint8_t *codes, uint64_t N, const uint32_t *A,
                          uint32_t K, uint32_t D, const uint64_t *plut, uint64_t *part, uint32_t *part_cnt) {
-    if (update_runs_fits(K, D)) {
-        const uint32_t C = urun_copies(K, D);
+    const UpdatePlan up = update_plan(K, D);
+    if (up.runs) {
+        const uint32_t C = up.copies;
         const size_t lds = urun_bytes(K, D, C);
         switch (Dp) {
 #define X(DPV)                                                                                                     \
@@ -296,10 +304,8 @@ hipError_t launch_update(hipStream_t s, uint32_t Dp, uint32_t G, const uint8_t *
         }
         return hipErrorInvalidValue;
     }
-    const size_t per_k = (size_t)D * 8 + 4;
-    const uint32_t KR = (uint32_t)std::min<size_t>(K, (UPDATE_LDS - 2048 - 16) / per_k);
+    const uint32_t KR = up.KR, passes = up.passes;
     if (KR == 0) return hipErrorInvalidValue;
-    const uint32_t passes = (K + KR - 1) / KR;
     const size_t lds = (size_t)KR * D * 8 + ((KR + 1) / 2) * 8 + 256 * 8;
     const uint64_t rpg = (N + G - 1) / G;
     switch (Dp) {
