@@ -178,6 +178,15 @@ QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start /*
 /* Single steps over the current training set, for tests and benchmarks.
  * qvq_assign: nearest code vector of every row for codebook C (K x dim fp64, host),
  *   with the same MFMA/VALU search + fp64 recheck + kd-tree tie resolution as qvq_lbg.
+ *   On a byte-image training set every component of C must lie in [cmin, cmax] =
+ *   [min(1.2 vmin, 0.8 vmin), max(1.2 vmax, 0.8 vmax)], vmin and vmax the colour space's smallest
+ *   and largest value (SCALED: [0, 1.2]; NORMAL: [-153.6, 152.4]) -- every codebook qvq_lbg can
+ *   form, centroids and their 1.2 / 0.8 splits.  The searches' near-tie thresholds and their
+ *   f16 / fp32 score scale are worked out for that range: outside it a row could keep a wrong
+ *   index unflagged, or a score overflow.  A component outside it, NaN included, is QVQ_EINVAL
+ *   before anything reaches the device; assign is not written.  (qvq_refine's C_start keeps its
+ *   narrower [vmin, vmax].)  An exact-mode training set is not restricted: it runs no
+ *   fp32 search.
  * qvq_update: centroids of the rows under assignment A (host, n u32) into C_out
  *   (K x dim fp64) and counts (K u64), the engine's exact-sum rule. */
 QVQ_API qvq_status qvq_assign(qvq_ctx *ctx, const double *C, uint32_t K, uint32_t *assign);

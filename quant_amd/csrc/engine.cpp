@@ -513,18 +513,26 @@ uint64_t tree_bytes(uint32_t K, uint32_t D) {
     return 16ull * D + (2ull * K + 1) * sizeof(KdNodeDev) + 4ull * K;
 }
 
+// The range [cmin, cmax] of a code vector's components that the near-tie bounds below are worked
+// out for: centroids are means of data values in [vmin, vmax], the split scales them by 1.2 or 0.8.
+// qvq_assign refuses a byte-path codebook outside it.
+void codebook_range(const Terms &t, double &vmin, double &vmax, double &cmin, double &cmax) {
+    vmin = 1e300, vmax = -1e300;
+    for (int b = 0; b < 256; b++) {
+        vmin = std::min(vmin, t.v64[b]);
+        vmax = std::max(vmax, t.v64[b]);
+    }
+    cmin = std::min(1.2 * vmin, 0.8 * vmin);
+    cmax = std::max(1.2 * vmax, 0.8 * vmax);
+}
+
 // MFMA score scale and error bounds for the near-tie flag ("near-tie flags").
 void mfma_setup(qvq_ctx *ctx) {
     const Terms &t = ctx->terms;
     const double D = ctx->D;
-    // centroids are means of data values, the split scales them by 1.2 or 0.8
-    double vmin = 1e300, vmax = -1e300, wmax = 0;
-    for (int b = 0; b < 256; b++) {
-        vmin = std::min(vmin, t.v64[b]);
-        vmax = std::max(vmax, t.v64[b]);
-        wmax = std::max(wmax, (double)std::fabs(t.w[b]));
-    }
-    const double cmin = std::min(1.2 * vmin, 0.8 * vmin), cmax = std::max(1.2 * vmax, 0.8 * vmax);
+    double vmin, vmax, cmin, cmax, wmax = 0;
+    codebook_range(t, vmin, vmax, cmin, cmax);
+    for (int b = 0; b < 256; b++) wmax = std::max(wmax, (double)std::fabs(t.w[b]));
     const double cp = std::max(std::fabs(cmin - t.mu), std::fabs(cmax - t.mu));   // max |c - mu|
     const double n_max = D * cp * cp;
     const double c2_max = 2 * t.sx * cp;
@@ -3007,6 +3015,15 @@ QVQ_API qvq_status qvq_assign(qvq_ctx *ctx, const double *C, uint32_t K, uint32_
     GUARD(ctx);
     if (ctx->N == 0) return fail(ctx, QVQ_ESTATE, "no training set");
     if (!C || K == 0) return fail(ctx, QVQ_EINVAL, "empty codebook");
+    if (!ctx->exact) {
+        // the searches' near-tie thresholds (mfma_setup, valu_coeffs) and the f16 / fp32 score scale
+        // 2^t hold for components in [cmin, cmax] only; NaN fails the comparison too
+        double vmin, vmax, cmin, cmax;
+        codebook_range(ctx->terms, vmin, vmax, cmin, cmax);
+        for (uint64_t i = 0; i < (uint64_t)K * ctx->D; i++)
+            if (!(C[i] >= cmin && C[i] <= cmax))
+                return fail(ctx, QVQ_EINVAL, "codebook outside 1.2 times the colour space's value range");
+    }
     ctx->rf.valid = false;
     HIPCHK(hipSetDevice(ctx->dev));
     qvq_status st = ensure_levels(ctx, K);

@@ -1,7 +1,8 @@
-"""Records tests/golden/ref_nn.json: what the compiled reference kd-tree (oracle/_ref/libref_nn.so,
-`make -C oracle ref` where the reference checkout is present) answers for the inputs of
-tests/test_oracle_golden.py's kd-tree tests, as fingerprints of its index arrays beside those of the
-codebooks it was given.  Run from the repository root after a change of those inputs:
+"""Records tests/golden/ref_nn.json and tests/golden/ref_nn_neartie.json: what the compiled reference
+kd-tree (oracle/_ref/libref_nn.so, `make -C oracle ref` where the reference checkout is present)
+answers for the inputs of tests/test_oracle_golden.py's kd-tree tests and for every case of
+tests/helpers/neartie_cases.py, as fingerprints of its index arrays beside those of the codebooks it
+was given.  Run from the repository root after a change of those inputs:
 
     python tests/helpers/record_ref_nn.py
 """
@@ -14,6 +15,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__)))) 
 import numpy as np   # noqa: E402
 
 import test_oracle_golden as t   # noqa: E402
+from helpers import neartie_cases as nt   # noqa: E402
+
+WHAT = ("sha-256[:16] of the compiled reference kd-tree's indices (A, little-endian u32) for the codebook "
+        "with fingerprint C (float64), over every row of the case's training set")
 
 
 def record(C, X):
@@ -24,14 +29,20 @@ def record(C, X):
 
 
 def main():
-    out = {"what": "sha-256[:16] of the compiled reference kd-tree's indices (A, little-endian u32) for the codebook "
-                   "with fingerprint C (float64), over every row of the case's training set",
+    out = {"what": WHAT,
            "tie_heavy": {str(K): record(C, X) for K, C, X in t.tie_heavy_codebooks()}, "levels": {}}
     for case in t.LEVEL_CASES:
         X, splits, _ = t.level_case(case)
         out["levels"][case] = [record(Cs, X) for Cs in splits]
     with open(os.path.join(t.GOLDEN, "ref_nn.json"), "w") as f:
         json.dump(out, f, indent=1)
+        f.write("\n")
+    near = {"what": WHAT, "cases": {}}
+    for c in nt.CASES:
+        X, C = nt.inputs(c)
+        near["cases"][nt.key(c)] = record(C, X)
+    with open(os.path.join(t.GOLDEN, "ref_nn_neartie.json"), "w") as f:
+        json.dump(near, f, indent=1)
         f.write("\n")
 
 

@@ -143,8 +143,14 @@ def test_kd_tie_sets_across_leaves(engine, bw, bh):
     X, _ = oracle.tile(oracle.gen_image(128), 128, 128, bw, bh)
     D = X.shape[1]
     engine.set_vectors(X)
-    centres = X[rng.choice(len(X), 24, replace=False)]
     v = 2.0 ** -12
+    pick = rng.choice(len(X), 24, replace=False)
+    # a centre with a zero component would put c - v below the value range qvq_assign accepts (qvq.h):
+    # such a pick moves on to the next row without one
+    inside = X.min(axis=1) >= v
+    for i in np.flatnonzero(~inside[pick]):
+        pick[i] = next(r for r in range(pick[i] + 1, len(X)) if inside[r] and r not in pick)
+    centres = X[pick]
     star = np.concatenate([np.concatenate([c + v * np.eye(D), c - v * np.eye(D)]) for c in centres])
     others = X[rng.choice(len(X), 200, replace=False)] * 0.9
     C = np.concatenate([others[:100], star, np.zeros((100, D)), others[100:]])
