@@ -244,7 +244,7 @@ hipError_t launch_assign_mf32(hipStream_t s, int grid, bool fuse, const uint8_t 
                               uint64_t *part, uint32_t *part_cnt, const uint32_t *perm = nullptr,
                               const int32_t *tint = nullptr,
                               uint64_t *z1 = nullptr, uint32_t nz1 = 0);
-constexpr uint32_t PRUNE_MAXK_HOST = 4096;   // prune_order's capacity (k_misc.hip PRUNE_MAXK)
+constexpr uint32_t PRUNE_MAXK_HOST = 4096;   // prune_order's capacity (prune_order.hpp PRUNE_MAXK)
 // d_tint: the envelopes (2 int32 per tile, PRUNE_MAXK_HOST / 32 tiles), then Kpad floats of
 // projections (finalize -> prune_order)
 inline size_t tint_bytes(uint32_t Kp) { return (size_t)2 * (PRUNE_MAXK_HOST / 32) * 4 + (size_t)Kp * 4; }
@@ -348,12 +348,6 @@ constexpr uint32_t MEAN_COPIES = 8;
 hipError_t launch_mean_sums(hipStream_t s, uint32_t Dp, const uint8_t *codes, uint64_t N, uint32_t D,
                             const uint64_t *plut, uint64_t *sums, unsigned *zero, uint32_t n_zero, double *dist,
                             const uint64_t *hist, const double *v64);
-// Centroids of the reduced sums (C_cent [K][D]); with split also the next level's K' = 2K
-// code vectors (C64n and, if host_cb, mapped host memory) and their search tables (see
-// launch_prep) padded to Kpad_next; without split, given dist_out, dist_out[0] =
-// sum_k (2 c_k.S_k - n_k ||c_k||^2) (closed-form distortion).  With done (a counter at 0,
-// left at 0) the last block also publishes *ready = seq in mapped host memory; dist_part
-// holds the per-block partials (<= 8000).
 // The level's tie rows exported with the codebook (the speculative Kahan check, engine.cpp):
 // out (mapped host memory) = [u32 count][u32 pad] then per row [u32 row][u32 A[row]][Dp code
 // bytes], the first cap rows; released with the ready flag.
@@ -366,60 +360,64 @@ struct TieExport {
     uint64_t n_rows = 0;   // rows in codes / A (a row index past it is written as ~0, nothing read)
     uint8_t *out = nullptr;
 };
-hipError_t launch_finalize_prep(hipStream_t s, const uint64_t *sums, uint32_t K, uint32_t D, uint32_t Dp, int64_t R,
-                                int64_t bias, int scale, double *C_cent, bool split, double *C64n, uint32_t Kpad_next,
-                                double mu, double sx, int t, float *C32, _Float16 *cb_rows, float *E32,
-                                double *host_cb, double *dist_part, unsigned *done, double *dist_out, uint64_t *ready, uint64_t seq,
-                                bool zero_sums, uint32_t ncopy = 1, uint32_t *perm = nullptr, int32_t *tint = nullptr,
-                                uint32_t zero_skip = 0, uint64_t copy_stride = 0, const unsigned *copy_gate = nullptr,
-                                const TieExport &ties = TieExport());
-// (zero_sums: clears copies zero_skip .. ncopy - 1; copy_stride 0: the copies follow each other,
-// 2KD + K apart; copy_gate: copies past the first are read and cleared only if *copy_gate != 0)
-hipError_t launch_finalize(hipStream_t s, const uint64_t *sums, uint32_t K, uint32_t D, int64_t R, int64_t bias,
-                           int scale, double *C_cent);
-// Lloyd refinement at fixed K (k_refine.hip, qvq_refine).  One launch in place of
-// launch_finalize_prep, without the split:
-//   tables, sums:      C_cent = C_next = the exact centroids of sums (launch_finalize's rounding),
-//                      the search tables of C_next for the same K (Kpad rows) and, given perm / tint,
-//                      its pruned tile order; host_cb (mapped) gets the codebook;
-//   tables, no sums:   the same tables for the codebook C_src (C_next = C_src's values);
-//   no tables:         nothing written but the distortion term of (C_src, sums).
-// Every form then publishes pub[0] = *changed (launch_count_changed's total, cleared; null: 0),
-// pub[1] = the bits of sum_k (2 c_k.S_k - n_k ||c_k||^2) (0 without sums) and *ready = seq (pub
-// and ready in mapped host memory), and clears clear_cnt[0..1].  gate / cstride: copy 1 of the
-// sums (kd_reduce_kernel's moves), added when *gate != 0 and then cleared.  done: a block counter
-// at 0, left at 0; dist_part: 512 doubles of scratch.
-struct RefineArgs {
-    bool tables = true;
-    const uint64_t *sums = nullptr;
-    const double *C_src = nullptr;
-    uint32_t K = 0, Kpad = 0, D = 0, Dp = 0;
-    int64_t R = 0, bias = 0;
+// The finalize (k_finalize.hip): one kernel, its form chosen by sums, children and measure:
+//   sums, children 2:   C_cent = the exact centroids of the K cells; C_next (and host_cb, then the
+//                       cells' row counts, u32) = the 2K split code vectors (x1.2 | x0.8), with
+//                       their search tables padded to Kpad and, given perm / tint, their tile order
+//                       (qvq_lbg's levels);
+//   sums, children 1:   the same without the split: C_cent = C_next = the centroids, the tables of
+//                       the same K (qvq_refine's centroid step);
+//   no sums, children 1: the tables of the codebook C_src, whose values also go to C_next /
+//                       host_cb where given (qvq_assign; qvq_refine's starting point);
+//   sums, children 0:   C_cent only (qvq_update; qvq_lbg's last level);
+//   sums, measure:      nothing written but the distortion term of the codebook C_src under sums
+//                       that need not be its own (QVQ_REFINE_FRESH).
+// The distortion term sum_k (2 c_k.S_k - n_k ||c_k||^2) (closed-form distortion) goes to
+// dist_out[0] and its bits to pub[1].  With done the last block to finish clears what it is asked
+// to, publishes pub[0..1] and then *ready = seq (pub, ready, host_cb and ties.out: mapped host
+// memory); without done nothing of "the end" below happens.
+struct FinArgs {
+    // the cells
+    const uint64_t *sums = nullptr;   // the reduced sums hi[d][k] | lo[d][k] | cnt[k]; null: rows from C_src
+    uint32_t K = 0, D = 0, Dp = 0;
+    int64_t R = 0, bias = 0;          // Terms
     int scale = 0;
-    uint64_t cstride = 0;
-    const unsigned *gate = nullptr;
-    double *C_cent = nullptr, *C_next = nullptr;
-    double mu = 0, sx = 0;
-    int t = 0;
-    float *C32 = nullptr;
-    _Float16 *rows = nullptr;
-    float *E32 = nullptr;
-    double *host_cb = nullptr;
-    uint32_t *perm = nullptr;
+    uint32_t ncopy = 1;               // copies of the sums to add: the mean's MEAN_COPIES, or 2 (kd_reduce_kernel)
+    uint64_t cstride = 0;             // u64 from one copy to the next (0: they follow each other, 2KD + K apart)
+    const unsigned *gate = nullptr;   // non-null: copies past the first only when *gate != 0 (the level's
+                                      // tie count: without ties copy 1 is all zero, neither read nor cleared)
+    bool zero_sums = false;           // the last block clears copies zero_skip .. ncopy - 1 (under the gate)
+    uint32_t zero_skip = 0;
+    // the rows
+    uint32_t children = 0;            // table rows per cell: 2 the split, 1 the same K, 0 no tables
+    uint32_t Kpad = 0;                // table rows in all: rows children K .. Kpad - 1 are padding that never wins
+    const double *C_src = nullptr;    // sums == null: the codebook to prepare; measure: the codebook measured
+    bool measure = false;
+    double *C_cent = nullptr;         // the centroids [K][D]
+    double *C_next = nullptr;         // the table rows' code vectors [children K][D]: the next search's codebook
+    double mu = 0, sx = 0;            // Terms
+    int t = 0;                        // the MFMA scores' scale 2^t
+    float *C32 = nullptr;             // fp32 [Kpad][Dp] (VALU path and the rechecks)
+    _Float16 *rows = nullptr;         // the f16 MFMA rows (D = 12 or wide layout)
+    float *E32 = nullptr;             // D = 12: expanded fp32 terms [c''(12) | n | 0 0 0] (small-K scan)
+    double *host_cb = nullptr;        // mapped host memory: C_next's values for the host's kd-tree build
+    uint32_t *perm = nullptr;         // the next search's tile order (prune_order), or null
     int32_t *tint = nullptr;
-    double *dist_part = nullptr;
-    unsigned *done = nullptr, *changed = nullptr, *clear_cnt = nullptr;
-    uint64_t *pub = nullptr, *ready = nullptr;
+    TieExport ties;                   // out != null: the level's tie rows to mapped memory
+    // the end
+    double *dist_part = nullptr;      // per-block partials of the distortion term (512 doubles)
+    unsigned *done = nullptr;         // block counter at 0, left at 0
+    double *dist_out = nullptr;
+    unsigned *changed = nullptr;      // launch_count_changed's total: published as pub[0] (null: 0), then cleared
+    unsigned *clear_cnt = nullptr;    // the iteration's flag and tie counters (2), cleared for the next one
+    uint64_t *pub = nullptr;          // [0] rows changed, [1] the distortion term's bits (0 without sums)
+    uint64_t *ready = nullptr;
     uint64_t seq = 0;
 };
-hipError_t launch_refine_finalize(hipStream_t s, const RefineArgs &r);
+hipError_t launch_finalize(hipStream_t s, const FinArgs &f);
 // *out += the rows i < N with A[i] != B[i] (A, B 16-byte aligned).
 hipError_t launch_count_changed(hipStream_t s, int num_cu, const uint32_t *A, const uint32_t *B, uint64_t N,
                                 unsigned *out);
-// f16 MFMA tables (D = 12) and fp32 VALU table from an fp64 codebook of K code vectors.
-// With E32 (D = 12) also the expanded fp32 table of launch_assign_mfma.
-hipError_t launch_prep(hipStream_t s, const double *C64, uint32_t K, uint32_t Kpad, uint32_t D, uint32_t Dp,
-                       double mu, double sx, int t, float *C32, _Float16 *cb_rows, float *E32);
 hipError_t launch_gather_codes(hipStream_t s, const uint8_t *codes, uint32_t Dp, const uint32_t *rows, uint32_t n,
                                uint8_t *out);
 // Host-resolved rows: A[rows[i]] = vals[i]; with xslab their terms move from the

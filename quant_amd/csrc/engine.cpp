@@ -80,7 +80,10 @@ bool make_terms(int cs, Terms &t) {
 
 using namespace qvq;
 
-constexpr uint32_t SCHED_COUNTERS = 2 * 33 + 2, N_COUNTERS = SCHED_COUNTERS + 2;
+// d_counters: per level l < 33 [2l] flagged rows and [2l + 1] kd-tree ties; the block counters of the
+// finalize's and of the hand-off copies' last-block publication; the pruned wide search's two task counters
+constexpr uint32_t LEVEL_COUNTERS = 2 * 33, FIN_DONE_COUNTER = LEVEL_COUNTERS, COPY_DONE_COUNTER = LEVEL_COUNTERS + 1;
+constexpr uint32_t SCHED_COUNTERS = LEVEL_COUNTERS + 2, N_COUNTERS = SCHED_COUNTERS + 2;
 // ... and behind the counters a quantize clears: qvq_refine's rows-changed total (count_changed_kernel)
 constexpr uint32_t CHANGED_COUNTER = N_COUNTERS, N_COUNTERS_ALLOC = N_COUNTERS + 2;
 // Levels whose kd-tree the device builds (k_kdbuild.hip, beside the search): K * D from this up
@@ -669,10 +672,49 @@ qvq_status ensure_levels(qvq_ctx *ctx, uint32_t Kmax) {
     return QVQ_OK;
 }
 
+// What every finalize launch takes from the context: the terms, the centroids' and the tables'
+// buffers and, with last_block, the end-of-kernel scratch, block counter and ready number.
+FinArgs finalize_args(const qvq_ctx *ctx, uint32_t K, bool last_block) {
+    const Terms &T = ctx->terms;
+    FinArgs f;
+    f.K = K;
+    f.D = ctx->D;
+    f.Dp = ctx->Dp;
+    f.R = T.R;
+    f.bias = T.bias;
+    f.scale = T.scale;
+    f.mu = T.mu;
+    f.sx = T.sx;
+    f.t = ctx->mf_t;
+    f.C_cent = ctx->d_C64_cent;
+    f.C32 = ctx->d_C32;
+    f.rows = ctx->d_rows;
+    f.E32 = ctx->d_E32;
+    if (last_block) {
+        f.dist_part = ctx->d_dist_part + 8;
+        f.done = ctx->d_counters + FIN_DONE_COUNTER;
+        f.ready = ctx->dh_ready;
+    }
+    return f;
+}
+
 // Search tables for the K code vectors in d_C64_split.
 qvq_status run_prep(qvq_ctx *ctx, uint32_t K) {
-    HIPCHK(launch_prep(ctx->stream, ctx->d_C64_split, K, pad32(K), ctx->D, ctx->Dp, ctx->terms.mu, ctx->terms.sx,
-                       ctx->mf_t, ctx->d_C32, ctx->d_rows, ctx->d_E32));
+    FinArgs f = finalize_args(ctx, K, false);
+    f.C_src = ctx->d_C64_split;
+    f.children = 1;
+    f.Kpad = pad32(K);
+    HIPCHK(launch_finalize(ctx->stream, f));
+    return QVQ_OK;
+}
+
+// Copy 1 of d_sums may hold a kd_reduce's moves that no finalize took (a call that stopped
+// between the two): the sums cleared before they are used again.
+qvq_status clear_dirty_sums(qvq_ctx *ctx) {
+    if (ctx->sums1_dirty) {
+        HIPCHK(hipMemsetAsync(ctx->d_sums, 0, ctx->sums_bytes, ctx->stream));
+        ctx->sums1_dirty = false;
+    }
     return QVQ_OK;
 }
 
@@ -1363,7 +1405,7 @@ qvq_status run_level(qvq_ctx *ctx, uint32_t K, int slot, bool sums_out, const do
         } else {
             HIPCHK(launch_copy_out(ctx->stream, &cnt[1], reinterpret_cast<uint8_t *>(ctx->dh_ready) + 16, 4, nullptr,
                                    nullptr, 0, nullptr, nullptr, 0, ctx->dh_ready + 1, ctx->pub_seq,
-                                   ctx->d_counters + 2 * 33 + 1));
+                                   ctx->d_counters + COPY_DONE_COUNTER));
         }
     }
     if (early_upd) {
@@ -1417,6 +1459,32 @@ qvq_status run_level(qvq_ctx *ctx, uint32_t K, int slot, bool sums_out, const do
         HIPCHK(hipEventRecord(ctx->ev[slot][2], ctx->stream));
         if ((st = run_update_slabs(ctx, ctx->d_A, K)) != QVQ_OK) return st;
         HIPCHK(hipEventRecord(ctx->ev[slot][3], ctx->stream));
+    }
+    return QVQ_OK;
+}
+
+// The sums of the assignment run_level just made, reduced into d_sums: the slabs together with
+// the level's kd-tree ties (kd_reduce_kernel: their moves go to copy 1, which the finalize adds),
+// or the slabs alone; nslabs 0: the sorted sums are in d_sums already.  pub (may be null): a tie
+// count that run_level left to the slab reduce to publish.
+qvq_status reduce_level(qvq_ctx *ctx, uint32_t K, int slot, PubArgs *pub) {
+    const unsigned *tcnt = ctx->d_counters + 2 * slot + 1;   // the level's ties
+    const bool reduced = !ctx->kd_pend && ctx->nslabs != 0;
+    if (ctx->kd_pend) {
+        ctx->sums1_dirty = true;
+        HIPCHK(launch_kd_reduce(ctx->stream, ctx->d_codes, ctx->Dp, ctx->D, ctx->d_ties, tcnt, ctx->d_C64_split, K,
+                                ctx->d_lut64, ctx->pend_kd, ctx->d_A, ctx->d_plut, ctx->d_part, ctx->d_part_cnt,
+                                ctx->nslabs, ctx->nsub, ctx->d_sums, ctx->d_sums + sums_cap_stride(ctx)));
+        ctx->kd_pend = false;
+    } else if (ctx->nslabs) {
+        HIPCHK(launch_reduce(ctx->stream, ctx->d_part, ctx->d_part_cnt, ctx->nslabs, ctx->nsub, K, ctx->D, ctx->d_sums,
+                             pub ? *pub : PubArgs()));
+    }
+    if (pub && pub->flag) {
+        if (!reduced)   // the slab reduce did not run: a launch of its own
+            HIPCHK(launch_copy_out(ctx->stream, pub->cnt, pub->dst, 4, nullptr, nullptr, 0, nullptr, nullptr, 0, pub->flag,
+                                   pub->seq, ctx->d_counters + COPY_DONE_COUNTER));
+        *pub = PubArgs();
     }
     return QVQ_OK;
 }
@@ -2666,7 +2734,6 @@ QVQ_API qvq_status qvq_lbg(qvq_ctx *ctx, uint32_t bits, double eps, double *code
     if (st != QVQ_OK) return st;
     std::memset(&ctx->tm, 0, sizeof(ctx->tm));
     ctx->tm.levels = (int)bits;
-    const Terms &T = ctx->terms;
     // codeVectors[0] = trainingSetSum() / N, then the first split (src/Quantizer.cpp:129-138).
     // The mean kernel also clears the counters and writes [sum ||x||^2, rows] for the
     // closed-form distortion (summed over all ranks below).
@@ -2724,20 +2791,20 @@ QVQ_API qvq_status qvq_lbg(qvq_ctx *ctx, uint32_t bits, double eps, double *code
     auto enqueue_out = [&]() -> qvq_status {
         if (ctx->timing_level == -1) HIPCHK(hipEventRecord(ctx->ev_end, ctx->stream));   // each record idles the GPU ~6 us
         uint8_t *dh_small = reinterpret_cast<uint8_t *>(ctx->dh_ready) + 64;
-        static_assert(3 * sizeof(double) + 2 * 33 * sizeof(unsigned) <= 1024 - 64, "small results exceed the mapped area");
+        static_assert(3 * sizeof(double) + LEVEL_COUNTERS * sizeof(unsigned) <= 1024 - 64, "small results exceed the mapped area");
         const uint64_t cb_bytes = codebook ? (uint64_t)Kmax * ctx->D * 8 : 0;
         uint64_t *done = reinterpret_cast<uint64_t *>(dh_small + (1024 - 64 - 8));
         out_seq = ++ctx->out_seq;
         HIPCHK(launch_copy_out(ctx->stream, ctx->d_dist_part, dh_small, 3 * sizeof(double), ctx->d_counters,
-                               dh_small + 3 * sizeof(double), 2 * 33 * sizeof(unsigned), ctx->d_C64_cent, ctx->dh_cb,
-                               cb_bytes, done, out_seq, ctx->d_counters + 2 * 33 + 1));
+                               dh_small + 3 * sizeof(double), LEVEL_COUNTERS * sizeof(unsigned), ctx->d_C64_cent, ctx->dh_cb,
+                               cb_bytes, done, out_seq, ctx->d_counters + COPY_DONE_COUNTER));
         out_enqueued = true;
         return QVQ_OK;
     };
     // the published results out of the mapped buffers: distortion inputs, per-level counters,
     // the codebook (C4: 1.5 MB, ~60 us)
     double dres[3];
-    unsigned stats[2 * 33];
+    unsigned stats[LEVEL_COUNTERS];
     bool results_copied = false;
     auto copy_results = [&]() -> qvq_status {
         uint8_t *h_small = reinterpret_cast<uint8_t *>(ctx->h_ready) + 64;
@@ -2763,13 +2830,9 @@ QVQ_API qvq_status qvq_lbg(qvq_ctx *ctx, uint32_t bits, double eps, double *code
         (void)hipMemsetAsync(ctx->d_mean, 0, MEAN_COPIES * (2 * 64 + 1) * 8, ctx->stream);   // keep it clear for the next call
         return st;
     }
-    unsigned *dist_done = ctx->d_counters + 2 * 33;
     // finalize (+ split, tables, host codebook and its ready number) / final distortion
     // (K = 1 reads the mean sums and leaves them cleared for the next quantize)
-    if (ctx->sums1_dirty) {   // a quantize stopped between a kd_reduce and its finalize
-        HIPCHK(hipMemsetAsync(ctx->d_sums, 0, ctx->sums_bytes, ctx->stream));
-        ctx->sums1_dirty = false;
-    }
+    if ((st = clear_dirty_sums(ctx)) != QVQ_OK) return st;
     // copies 2: copy 1 holds the ties' moves (added here; the next level's search clears it)
     // the split a finalize writes: with deferred ties the level's own split must survive its
     // (speculative) finalize, so the next one goes to the other buffer and the two swap
@@ -2781,17 +2844,29 @@ QVQ_API qvq_status qvq_lbg(qvq_ctx *ctx, uint32_t bits, double eps, double *code
         if (split || tx.out) ctx->seq++;
         const bool prune = split && use_prune(ctx, 2 * K);   // the next search's tile order
         ctx->perm_k = prune ? 2 * K : 0;
-        return launch_finalize_prep(ctx->stream, K == 1 ? ctx->d_mean : ctx->d_sums, K, ctx->D, ctx->Dp, T.R, T.bias,
-                                    T.scale,
-                                    ctx->d_C64_cent, split, split_out, pad32(2 * K), T.mu, T.sx, ctx->mf_t,
-                                    ctx->d_C32, ctx->d_rows, ctx->d_E32,
-                                    split ? dev_cb_of(ctx, (uint32_t)__builtin_ctz(K) + 1) : nullptr, d_dist + 8,
-                                    dist_done,
-                                    split ? nullptr : d_dist + 2, (split || tx.out) ? ctx->dh_ready : nullptr,
-                                    ctx->seq, K == 1 || (clear1 && copies > 1), K == 1 ? MEAN_COPIES : copies,
-                                    prune ? ctx->d_perm : nullptr, prune ? ctx->d_tint : nullptr, K == 1 ? 0 : 1,
-                                    copies > 1 ? sums_cap_stride(ctx) : 0,
-                                    gate, tx);
+        FinArgs f = finalize_args(ctx, K, true);
+        f.sums = K == 1 ? ctx->d_mean : ctx->d_sums;
+        f.ncopy = K == 1 ? MEAN_COPIES : copies;
+        f.cstride = copies > 1 ? sums_cap_stride(ctx) : 0;
+        f.gate = gate;
+        f.zero_sums = K == 1 || (clear1 && copies > 1);
+        f.zero_skip = K == 1 ? 0 : 1;
+        if (split) {
+            f.children = 2;
+            f.Kpad = pad32(2 * K);
+            f.C_next = split_out;
+            f.host_cb = dev_cb_of(ctx, (uint32_t)__builtin_ctz(K) + 1);
+            if (prune) {
+                f.perm = ctx->d_perm;
+                f.tint = ctx->d_tint;
+            }
+        } else {
+            f.dist_out = d_dist + 2;
+        }
+        f.ties = tx;
+        if (!split && !tx.out) f.ready = nullptr;
+        f.seq = ctx->seq;
+        return launch_finalize(ctx->stream, f);
     };
     HIPCHK(finalize(1, bits > 0));
     // with bits >= 1 the first search writes every row's index
@@ -2850,24 +2925,8 @@ QVQ_API qvq_status qvq_lbg(qvq_ctx *ctx, uint32_t bits, double eps, double *code
         const bool split = lvl < bits;
         {
             const uint32_t copies = ctx->sums_copies;
-            if (copies > 1) ctx->sums1_dirty = true;
-            const unsigned *tcnt = ctx->d_counters + 2 * ((int)lvl - 1) + 1;   // the level's ties
-            if (ctx->kd_pend) {   // the level's ties and the reduce together
-                HIPCHK(launch_kd_reduce(ctx->stream, ctx->d_codes, ctx->Dp, ctx->D, ctx->d_ties, tcnt,
-                                        ctx->d_C64_split, K, ctx->d_lut64, ctx->pend_kd, ctx->d_A, ctx->d_plut,
-                                        ctx->d_part, ctx->d_part_cnt, ctx->nslabs, ctx->nsub, ctx->d_sums,
-                                        ctx->d_sums + sums_cap_stride(ctx)));
-                ctx->kd_pend = false;
-            } else if (ctx->nslabs) {   // nslabs 0: the sorted sums are in d_sums already
-                HIPCHK(launch_reduce(ctx->stream, ctx->d_part, ctx->d_part_cnt, ctx->nslabs, ctx->nsub, K, ctx->D,
-                                     ctx->d_sums, ctx->pub));
-            }
-            if (ctx->pub.flag) {   // run_level left the tie count to the reduce, which did not run
-                if (!ctx->nslabs || ctx->kd_pend)
-                    HIPCHK(launch_copy_out(ctx->stream, ctx->pub.cnt, ctx->pub.dst, 4, nullptr, nullptr, 0, nullptr,
-                                           nullptr, 0, ctx->pub.flag, ctx->pub.seq, ctx->d_counters + 2 * 33 + 1));
-                ctx->pub = PubArgs();
-            }
+            const unsigned *tcnt = ctx->d_counters + 2 * slot + 1;   // the level's ties
+            if ((st = reduce_level(ctx, K, slot, &ctx->pub)) != QVQ_OK) return st;
             if ((st = all_reduce_sums(ctx, K)) != QVQ_OK) return st;
             TieExport tx;
             if (spec) {   // the level's tie rows and their indices go out with its codebook
@@ -2950,17 +3009,14 @@ QVQ_API qvq_status qvq_lbg(qvq_ctx *ctx, uint32_t bits, double eps, double *code
     }
     ctx->deferred.clear();
     if ((st = wait_stream(ctx)) != QVQ_OK) return st;
-    if (ctx->sums1_dirty) {
-        HIPCHK(hipMemsetAsync(ctx->d_sums, 0, ctx->sums_bytes, ctx->stream));
-        ctx->sums1_dirty = false;
-    }
+    if ((st = clear_dirty_sums(ctx)) != QVQ_OK) return st;
     ctx->kd_pend = false;
     ctx->pub = PubArgs();
     ctx->tm.kahan_redo++;
     spec = false;
     }
     // Returned distortion: updateDistortion after the last fix (src/Quantizer.cpp:9-22,103),
-    // from the sums of the final assignment (finalize_prep_kernel without split).
+    // from the sums of the final assignment (finalize_kernel without tables).
     // (enqueue_out: before the last checks are joined when speculating)
     if (!out_enqueued && (st = enqueue_out()) != QVQ_OK) return st;
     if (!results_copied && (st = copy_results()) != QVQ_OK) return st;
@@ -3074,8 +3130,9 @@ QVQ_API qvq_status qvq_update(qvq_ctx *ctx, const uint32_t *assign, uint32_t K, 
     }
     if ((st = run_update(ctx, ctx->d_A, K)) != QVQ_OK) return st;
     if ((st = all_reduce_sums(ctx, K)) != QVQ_OK) return st;
-    const Terms &T = ctx->terms;
-    HIPCHK(launch_finalize(ctx->stream, ctx->d_sums, K, ctx->D, T.R, T.bias, T.scale, ctx->d_C64_cent));
+    FinArgs f = finalize_args(ctx, K, false);   // the centroids only
+    f.sums = ctx->d_sums;
+    HIPCHK(launch_finalize(ctx->stream, f));
     // results land in context-owned pinned memory and reach the caller only after the bounded
     // wait succeeds (a failed wait can leave these copies queued: wait_failed)
     const uint64_t cB = (uint64_t)K * ctx->D * 8, nB = (uint64_t)K * 8;
@@ -3165,12 +3222,9 @@ QVQ_API qvq_status qvq_update_kahan_split(qvq_ctx *ctx, const uint32_t *assign, 
     return QVQ_OK;
 }
 
-// ---------------------------------------------------------------------------------------
-// Decode: CompressedImage::decompress (src/Compressor.cpp:156-165) as one device gather.
-// ---------------------------------------------------------------------------------------
 // Lloyd refinement at fixed K, resident on the device.  Iteration t + 1 is one
 // run_level against C_t -- qvq_assign's searches, recheck and kd-tree ties, with the exact sums of
-// the final assignment -- the reduce, the count of changed rows and refine_finalize_kernel, which
+// the final assignment -- the reduce, the count of changed rows and the same-K finalize_kernel, which
 // writes C_{t+1}, its search tables and tile order, and publishes C_{t+1}, the changed count and
 // the distortion term to mapped memory.  The host waits once per iteration, inside run_level, for
 // the codebook its tree build needs; the stop decision of iteration t comes with that codebook,
@@ -3195,11 +3249,8 @@ QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start, u
         if (!ctx->rf.valid) return fail(ctx, QVQ_ESTATE, "no qvq_lbg or qvq_refine result to continue from");
         if (ctx->rf.K != K) return fail(ctx, QVQ_EINVAL, "K differs from the result to continue from");
     } else {
-        double vmin = ctx->terms.v64[0], vmax = ctx->terms.v64[0];
-        for (int b = 1; b < 256; b++) {
-            vmin = std::min(vmin, ctx->terms.v64[b]);
-            vmax = std::max(vmax, ctx->terms.v64[b]);
-        }
+        double vmin, vmax, cmin, cmax;
+        codebook_range(ctx->terms, vmin, vmax, cmin, cmax);
         // (the searches' error bands assume |c| <= 1.2 vmax: valu_coeffs, mf_th)
         for (uint64_t i = 0; i < (uint64_t)K * ctx->D; i++)
             if (!(C_start[i] >= vmin && C_start[i] <= vmax))
@@ -3232,67 +3283,48 @@ QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start, u
     // both iterations' counters, the changed total; copy 1 of the sums if a quantize left it dirty
     HIPCHK(hipMemsetAsync(ctx->d_counters, 0, 4 * sizeof(unsigned), ctx->stream));
     HIPCHK(hipMemsetAsync(ctx->d_counters + CHANGED_COUNTER, 0, 2 * sizeof(unsigned), ctx->stream));
-    if (ctx->sums1_dirty) {
-        HIPCHK(hipMemsetAsync(ctx->d_sums, 0, ctx->sums_bytes, ctx->stream));
-        ctx->sums1_dirty = false;
-    }
+    if ((st = clear_dirty_sums(ctx)) != QVQ_OK) return st;
     ctx->kd_pend = false;
     ctx->pub = PubArgs();
-    const Terms &T = ctx->terms;
     const bool prune = use_prune(ctx, K);
     volatile uint64_t *h_pub = ctx->h_ready + 4;   // [4] rows changed, [5] the distortion term
     // C_t's tables, tile order and host copy (t = 0: from the starting codebook; else the centroid step)
     auto publish = [&](uint32_t t, bool tables, const uint64_t *sums, const unsigned *gate, unsigned *cnts,
                        bool count) -> qvq_status {
-        RefineArgs r;
-        r.tables = tables;
-        r.sums = sums;
-        r.C_src = ctx->d_C64_cent;
-        r.K = K;
-        r.Kpad = pad32(K);
-        r.D = D;
-        r.Dp = ctx->Dp;
-        r.R = T.R;
-        r.bias = T.bias;
-        r.scale = T.scale;
-        r.cstride = sums_cap_stride(ctx);
-        r.gate = gate;
-        r.C_cent = ctx->d_C64_cent;
-        r.C_next = ctx->d_C64_split;
-        r.mu = T.mu;
-        r.sx = T.sx;
-        r.t = ctx->mf_t;
-        r.C32 = ctx->d_C32;
-        r.rows = ctx->d_rows;
-        r.E32 = ctx->d_E32;
-        r.host_cb = tables ? dev_cb_of(ctx, t) : nullptr;
-        r.perm = tables && prune ? ctx->d_perm : nullptr;
-        r.tint = ctx->d_tint;
-        r.dist_part = ctx->d_dist_part + 8;
-        r.done = ctx->d_counters + 2 * 33;
-        r.changed = count ? ctx->d_counters + CHANGED_COUNTER : nullptr;
-        r.clear_cnt = cnts;
-        r.pub = ctx->dh_ready + 4;
-        r.ready = ctx->dh_ready;
-        r.seq = ++ctx->seq;
-        HIPCHK(launch_refine_finalize(ctx->stream, r));
+        FinArgs f = finalize_args(ctx, K, true);
+        f.sums = sums;
+        f.C_src = ctx->d_C64_cent;
+        if (gate) {   // copy 1: kd_reduce_kernel's moves, added and then cleared under the gate
+            f.ncopy = 2;
+            f.cstride = sums_cap_stride(ctx);
+            f.gate = gate;
+            f.zero_sums = true;
+            f.zero_skip = 1;
+        }
+        if (tables) {
+            f.children = 1;
+            f.Kpad = pad32(K);
+            f.C_next = ctx->d_C64_split;
+            f.host_cb = dev_cb_of(ctx, t);
+            if (prune) {
+                f.perm = ctx->d_perm;
+                f.tint = ctx->d_tint;
+            }
+        } else {
+            f.measure = true;
+        }
+        f.changed = count ? ctx->d_counters + CHANGED_COUNTER : nullptr;
+        f.clear_cnt = cnts;
+        f.pub = ctx->dh_ready + 4;
+        f.seq = ++ctx->seq;
+        HIPCHK(launch_finalize(ctx->stream, f));
         if (tables) ctx->perm_k = prune ? K : 0;
         return QVQ_OK;
     };
-    // the sums of the assignment run_level just made, reduced into d_sums (as qvq_lbg's level)
+    // the sums of the assignment run_level just made, reduced into d_sums
     auto reduce = [&](int slot, const unsigned *&gate) -> qvq_status {
-        const unsigned *tcnt = ctx->d_counters + 2 * slot + 1;
-        gate = ctx->sums_copies > 1 ? tcnt : nullptr;
-        if (ctx->kd_pend) {
-            ctx->sums1_dirty = true;
-            HIPCHK(launch_kd_reduce(ctx->stream, ctx->d_codes, ctx->Dp, D, ctx->d_ties, tcnt, ctx->d_C64_split, K,
-                                    ctx->d_lut64, ctx->pend_kd, ctx->d_A, ctx->d_plut, ctx->d_part, ctx->d_part_cnt,
-                                    ctx->nslabs, ctx->nsub, ctx->d_sums, ctx->d_sums + sums_cap_stride(ctx)));
-            ctx->kd_pend = false;
-        } else if (ctx->nslabs) {
-            HIPCHK(launch_reduce(ctx->stream, ctx->d_part, ctx->d_part_cnt, ctx->nslabs, ctx->nsub, K, D, ctx->d_sums));
-        }
-        return QVQ_OK;
+        gate = ctx->sums_copies > 1 ? ctx->d_counters + 2 * slot + 1 : nullptr;
+        return reduce_level(ctx, K, slot, nullptr);
     };
     if ((st = publish(0, true, nullptr, nullptr, nullptr, false)) != QVQ_OK) return st;
 
@@ -3354,7 +3386,7 @@ QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start, u
         have_A = true;
         t++;
     }
-    // C_t as refine_finalize_kernel published it (t = 0: the starting codebook's copy)
+    // C_t as the finalize published it (t = 0: the starting codebook's copy)
     if (codebook) std::memcpy(codebook, host_cb_of(ctx, t), KD * 8);
     if (assign) HIPCHK(host_copy(ctx, assign, ctx->d_A, ctx->N * 4, hipMemcpyDeviceToHost));
     if (distortion) *distortion = d_last;
@@ -3369,6 +3401,9 @@ QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start, u
     return QVQ_OK;
 }
 
+// ---------------------------------------------------------------------------------------
+// Decode: CompressedImage::decompress (src/Compressor.cpp:156-165) as one device gather.
+// ---------------------------------------------------------------------------------------
 static qvq_status check_decode_args(qvq_ctx *ctx, uint32_t K, uint64_t nblocks, uint32_t xSize, uint32_t ySize,
                                     uint32_t bw, uint32_t bh) {
     if (!ctx) return QVQ_EINVAL;

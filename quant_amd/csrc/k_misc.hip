@@ -1,12 +1,11 @@
-// k_misc.hip -- tiling, synthetic rasters, exact centroid sums, finalisation, split and
-// codebook preparation, tie scatter, distortion.
+// k_misc.hip -- tiling, synthetic rasters, exact centroid sums and their reduce, the mean, tie
+// scatter, result hand-off, decode.
 //
 // Global sums layout (also the RCCL all-reduce buffer, u64):
 //   hi[d][k] (K*D) | lo[d][k] (K*D) | cnt[k] (K)
 // Workgroup slabs (update kernels): part[g][d][k] packed (hi << 32 | lo), part_cnt[g][k].
 #include "common.hpp"
 #include "mfma_util.hpp"
-#include "prune_order.hpp"
 
 namespace qvq {
 
@@ -948,381 +947,6 @@ hipError_t launch_copy_out(hipStream_t s, const void *src0, void *dst0, uint64_t
     const uint64_t words = std::max(bytes0, std::max(bytes1, bytes2)) / 4;
     const int grid = (int)std::min<uint64_t>(std::max<uint64_t>((words + 255) / 256, 1), 256);
     hipLaunchKernelGGL(copy_out_kernel, dim3(grid), dim3(256), 0, s, a);
-    return hipGetLastError();
-}
-
-// finalize (src/Quantizer.cpp:79-94 fixCodebook + :129-138 split) fused with the next
-// level's search tables.  Block = 256/L rows x L component lanes.  With split, row j < 2K is
-// split code vector j (cluster j mod K, factor 1.2 for j < K, 0.8 above) and rows
-// 2K..Kpad_next-1 are padding; the split codebook also goes to host_cb (mapped pinned
-// memory, for the host's kd-tree build; then the K cells' row counts, u32).  L = 16, 32 or 64 lanes per row (>= Dp).  Without split (last level) row k < K writes
-// centroid k and its distortion term sum_d (2 c S - n c^2).  The last block to finish sums
-// the per-block distortion terms in block order and then publishes *ready = seq (system
-// scope), which tells the host that host_cb holds the codebook.
-
-struct FinArgs {
-    const uint64_t *sums;
-    uint32_t K, D, Dp;
-    int64_t R, bias;
-    int scale;
-    double *C_cent;
-    int split;
-    double *C64n;
-    uint32_t Kpad_next;
-    double mu, sx, scale_t;
-    float *C32;
-    _Float16 *rows;
-    float *E32;   // D = 12: expanded fp32 terms [c''(12) | n | 0 0 0] (small-K scan)
-    double *host_cb;
-    bool dist;
-    uint64_t *zero_after;   // cleared by the last block once every block has read sums (mean)
-    uint32_t n_zero;
-    uint32_t ncopy;         // copies of the sums to add: the mean's MEAN_COPIES, or 2 (kd_reduce_kernel)
-    uint64_t cstride;       // u64 from one copy to the next (2KD + K, or the capacity's)
-    const unsigned *gate;   // non-null: copies past the first only when *gate != 0 (the level's
-                            // tie count: without ties copy 1 is all zero, read nor cleared)
-    uint32_t *perm;         // split: the next search's tile order (prune_order), or null
-    int32_t *tint;
-    float *qproj;           // with perm: the split code vectors' projections (finalize_split_item)
-    TieExport ties;         // out != null: the level's tie rows to mapped memory (TieExport)
-};
-
-// A split row j (< 2K: child of code vector j mod K, from that code vector's sums hs, ls, cnt of
-// component d; Kpad_next > j >= 2K: padding) -- its C64n / C32 / host values and the MFMA tables.
-__device__ inline void finalize_split_item(const FinArgs &a, uint32_t j, uint32_t d, uint32_t L, uint64_t hs,
-                                           uint64_t ls, uint64_t cnt) {
-    const uint32_t K = a.K, D = a.D, Dp = a.Dp;
-    if (j < 2 * K) {
-        const uint32_t k = j < K ? j : j - K;
-        double v = 0;
-        if (d < D) {
-            const double cv = centroid_value(hs, ls, cnt, a.R, a.bias, a.scale);
-            if (j < K) a.C_cent[(uint64_t)k * D + d] = cv;
-            v = cv * (j < K ? (double)(1 + 0.2) : (double)(1 - 0.2));
-            a.C64n[(uint64_t)j * D + d] = v;
-            if (a.host_cb) a.host_cb[(uint64_t)j * D + d] = v;
-        }
-        // after the split rows: the K cells' row counts (the tie check: a cell of <= 2 rows has
-        // the reference's bits, a Kahan sum of one or two values being the rounded exact sum)
-        if (a.host_cb && j < K && d == 0)
-            reinterpret_cast<uint32_t *>(a.host_cb + 2ull * K * D)[k] = cnt > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)cnt;
-        if (d < Dp) a.C32[(uint64_t)j * Dp + d] = (float)v;
-        if (a.rows) {   // MFMA row (common.hpp): hi / lo at their slots, norm at 2 LO
-            const uint32_t RF = cb_row_f16(D, Dp), LO = cb_lo_off(D, Dp);
-            _Float16 *row = a.rows + (uint64_t)j * RF;
-            const double cp = d < D ? v - a.mu : 0.0;
-            if (a.qproj) {   // the projection sum_d (c_d - mu) / sx for prune_order (any order: it
-                             // is widened by 1 there)
-                double qs = cp;
-                for (uint32_t off = L / 2; off >= 1; off >>= 1) qs += __shfl_xor(qs, (int)off, (int)L);
-                if (d == 0) a.qproj[j] = (float)(qs / a.sx);
-            }
-            double n = cp * cp;   // L >= LO lanes per row
-            for (uint32_t off = L / 2; off >= 1; off >>= 1) n += __shfl_xor(n, (int)off, (int)L);
-            if (d < D) {
-                const double c2 = -2.0 * a.sx * cp * a.scale_t;
-                const _Float16 h = (_Float16)(float)c2;
-                row[cb_hi_slot(D, Dp, d)] = h;
-                row[cb_lo_slot(D, Dp, d)] = (_Float16)(float)(c2 - (double)(float)h);
-            } else if (d < LO) {
-                row[cb_hi_slot(D, Dp, d)] = (_Float16)0.f;
-                row[cb_lo_slot(D, Dp, d)] = (_Float16)0.f;
-            }
-            n *= a.scale_t;
-            const _Float16 h = (_Float16)(float)n;
-            const _Float16 l = (_Float16)(float)(n - (double)(float)h);
-            for (uint32_t i = 2 * LO + d; i < RF; i += L)
-                row[i] = i == 2 * LO ? h : (i == 2 * LO + 1 ? l : (_Float16)0.f);
-            if (a.E32 && d < 16)   // L = 16 lanes for D = 12
-                a.E32[(uint64_t)j * 16 + d] =
-                    d < D ? (float)(-2.0 * a.sx * cp * a.scale_t) : (d == D ? (float)n : 0.f);
-        }
-    } else if (j < a.Kpad_next) {
-        if (d < Dp) a.C32[(uint64_t)j * Dp + d] = 0.f;
-        if (a.E32 && d < 16) a.E32[(uint64_t)j * 16 + d] = d == D ? 1e30f : 0.f;   // never wins
-        if (a.rows) {
-            const uint32_t RF = cb_row_f16(D, Dp), LO = cb_lo_off(D, Dp);
-            _Float16 *row = a.rows + (uint64_t)j * RF;
-            for (uint32_t i = d; i < RF; i += L)
-                row[i] = (_Float16)(i == 2 * LO || i == 2 * LO + 1 ? MF_PAD_SCORE : 0.f);
-        }
-    }
-}
-
-// One (row j, component lane d) item of the finalize; L lanes per row (16 when D == 12: the
-// norm of a row is a 16-lane butterfly).  Returns the item's distortion term (no split).
-__device__ inline double finalize_item(const FinArgs &a, uint32_t j, uint32_t d, uint32_t L) {
-    const uint32_t K = a.K, D = a.D;
-    const uint64_t KD = (uint64_t)K * D;
-    const uint32_t ncopy = a.gate && *a.gate == 0 ? 1 : a.ncopy;
-    auto sums_at = [&](uint64_t i) {   // the sum of the ncopy copies
-        uint64_t v = a.sums[i];
-        for (uint32_t c = 1; c < ncopy; c++) v += a.sums[c * a.cstride + i];
-        return v;
-    };
-    if (a.split) {
-        const uint32_t k = j < K ? j : j - K;
-        const uint64_t c = (uint64_t)d * K + k;
-        const bool have = j < 2 * K && d < D;
-        finalize_split_item(a, j, d, L, have ? sums_at(c) : 0, have ? sums_at(KD + c) : 0,
-                            j < 2 * K ? sums_at(2 * KD + k) : 0);
-        return 0.0;
-    }
-    if (j < K && d < D) {
-        const uint64_t c = (uint64_t)d * K + j;
-        const uint64_t cnt = sums_at(2 * KD + j), hs = sums_at(c), ls = sums_at(KD + c);
-        const double cv = centroid_value(hs, ls, cnt, a.R, a.bias, a.scale);
-        a.C_cent[(uint64_t)j * D + d] = cv;
-        if (a.dist && cnt) {
-            const __int128 Sq = (__int128)a.R * (__int128)hs + (__int128)ls - (__int128)a.bias * (__int128)cnt;
-            const double S = ldexp(i128_to_double(Sq), -a.scale);
-            return 2.0 * cv * S - (double)cnt * cv * cv;
-        }
-    }
-    return 0.0;
-}
-
-__device__ inline uint32_t fin_rows(const FinArgs &a) { return a.split ? max(2 * a.K, a.Kpad_next) : a.K; }
-
-// Grid-stride over groups of 256/L rows.  Each wave fences its mapped-host writes once, after
-// its last row (a system fence writes back the L2: per row it cost ~25 ns x rows).
-// The end of a finalize block: its distortion partial (red: blockDim doubles of LDS, tree order
-// over the block's threads; none without red), the done count, and in the last block the
-// distortion total (block order), the clearing, the next search's tile order and the host's
-// ready number.
-__device__ void finalize_block_done(const FinArgs &a, double term, double *red, double *__restrict__ dist_part,
-                                    unsigned *__restrict__ done, double *__restrict__ dist_out,
-                                    volatile uint64_t *ready, uint64_t seq) {
-    __shared__ bool last;
-    // one block (small codebooks): no count and no agent fence, only the system fence before the
-    // ready number (two fences of ~2-3.5 us each were most of a small level's finalize)
-    const bool one = gridDim.x == 1;
-    if (red) red[threadIdx.x] = term;
-    // host_cb: every wave's mapped stores complete before the barrier, and thread 0's
-    // system-scope fence below releases them with the block's count (MI355X guide's
-    // producer pattern: one fence per block, not one per thread)
-    if (a.host_cb || a.ties.out) __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (red)
-        for (int w = (int)blockDim.x / 2; w > 0; w >>= 1) {
-            if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-            __syncthreads();
-        }
-    if (threadIdx.x == 0) {
-        if (one) {
-            last = true;
-        } else {
-            if (red) dist_part[blockIdx.x] = red[0];
-            if (a.host_cb || a.ties.out) __threadfence_system();
-            else __threadfence();
-            last = atomicAdd(done, 1u) == gridDim.x - 1;
-        }
-    }
-    __syncthreads();
-    if (!last) return;
-    if (one) {
-        if (dist_out && threadIdx.x == 0) dist_out[0] = red[0];
-    } else {
-        __threadfence();
-    }
-    if (dist_out && !one) {   // the block partials, loaded in parallel, then added in block order
-        __shared__ double parts[512];
-        for (uint32_t b = threadIdx.x; b < gridDim.x; b += blockDim.x) parts[b] = __builtin_nontemporal_load(&dist_part[b]);
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double t = 0;
-            for (uint32_t b = 0; b < gridDim.x; b++) t += parts[b];
-            dist_out[0] = t;
-        }
-    }
-    if (!a.gate || *a.gate)
-        for (uint32_t i = threadIdx.x; i < a.n_zero; i += blockDim.x) a.zero_after[i] = 0;
-    if (a.perm) prune_order(a.qproj, 2 * a.K, a.Kpad_next, a.perm, a.tint);
-    if (threadIdx.x == 0) {
-        *done = 0;
-        if (ready) {
-            __threadfence_system();
-            *ready = seq;
-        }
-    }
-}
-
-// Grid-stride over groups of 256/L rows.  Each wave fences its mapped-host writes once, after
-// its last row (a system fence writes back the L2: per row it cost ~25 ns x rows).
-__global__ __launch_bounds__(256) void finalize_prep_kernel(FinArgs a, double *__restrict__ dist_part,
-                                                            unsigned *__restrict__ done, double *__restrict__ dist_out,
-                                                            volatile uint64_t *ready, uint64_t seq, uint32_t L) {
-    const uint32_t d = threadIdx.x % L, r = threadIdx.x / L;
-    const uint32_t per = 256 / L, n = fin_rows(a);
-    double term = 0.0;
-    for (uint32_t j0 = blockIdx.x * per; j0 < n; j0 += gridDim.x * per) term += finalize_item(a, j0 + r, d, L);
-    if (a.ties.out) {   // the tie rows, a thread per 4 bytes of a row record
-        const TieExport &t = a.ties;
-        const uint32_t nt = *t.cnt, m = min(nt, t.cap), words = 2 + a.Dp / 4;
-        uint32_t *o = reinterpret_cast<uint32_t *>(t.out);
-        if (blockIdx.x == 0 && threadIdx.x == 0) o[0] = nt;
-        for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (uint64_t)m * words;
-             i += (uint64_t)gridDim.x * blockDim.x) {
-            const uint32_t k = (uint32_t)(i / words), w = (uint32_t)(i % words), row = t.rows[k];
-            if (row >= t.n_rows) {   // (never: the recheck lists rows)
-                o[2 + i] = ~0u;
-                continue;
-            }
-            o[2 + i] = w == 0 ? row
-                              : (w == 1 ? t.A[row] : reinterpret_cast<const uint32_t *>(t.codes + (uint64_t)row * a.Dp)[w - 2]);
-        }
-    }
-    if (!done) return;
-    __shared__ double red[256];
-    // (the distortion's block tree only on the level that returns it: 8 barriers fewer elsewhere)
-    finalize_block_done(a, term, a.dist ? red : nullptr, dist_part, done, dist_out, ready, seq);
-}
-
-static FinArgs fin_args(const uint64_t *sums, uint32_t K, uint32_t D, uint32_t Dp, int64_t R, int64_t bias,
-                        int scale, double *C_cent, bool split, double *C64n, uint32_t Kpad_next, double mu, double sx,
-                        int t, float *C32, _Float16 *cb_rows, float *E32, double *host_cb, bool dist) {
-    FinArgs a;
-    a.sums = sums;
-    a.K = K;
-    a.D = D;
-    a.Dp = Dp;
-    a.R = R;
-    a.bias = bias;
-    a.scale = scale;
-    a.C_cent = C_cent;
-    a.split = split ? 1 : 0;
-    a.C64n = C64n;
-    a.Kpad_next = Kpad_next;
-    a.mu = mu;
-    a.sx = sx;
-    a.scale_t = std::ldexp(1.0, t);
-    a.C32 = C32;
-    a.rows = cb_rows;
-    a.E32 = D == MF_D ? E32 : nullptr;
-    a.host_cb = host_cb;
-    a.dist = dist;
-    a.zero_after = nullptr;
-    a.n_zero = 0;
-    a.ncopy = 1;
-    a.cstride = 2 * (uint64_t)K * D + K;
-    a.gate = nullptr;
-    a.perm = nullptr;
-    a.tint = nullptr;
-    a.qproj = nullptr;
-    a.ties = TieExport();
-    return a;
-}
-
-constexpr uint32_t FIN_ONE_BLOCK_ROWS = 64;   // split rows: K <= 32
-hipError_t launch_finalize_prep(hipStream_t s, const uint64_t *sums, uint32_t K, uint32_t D, uint32_t Dp, int64_t R,
-                                int64_t bias, int scale, double *C_cent, bool split, double *C64n, uint32_t Kpad_next,
-                                double mu, double sx, int t, float *C32, _Float16 *cb_rows, float *E32,
-                                double *host_cb, double *dist_part, unsigned *done, double *dist_out, uint64_t *ready,
-                                uint64_t seq, bool zero_sums, uint32_t ncopy, uint32_t *perm, int32_t *tint,
-                                uint32_t zero_skip, uint64_t copy_stride, const unsigned *copy_gate,
-                                const TieExport &ties) {
-    if (D == 0 || D > 64) return hipErrorInvalidValue;
-    if (ties.out && (!done || !ready || !ties.rows || !ties.cnt || !ties.A || !ties.codes || (Dp & 3) || !ties.n_rows))
-        return hipErrorInvalidValue;   // released with the ready flag
-    if (zero_sums && !done) return hipErrorInvalidValue;   // the clearing is the last block's
-    const uint32_t L = D <= 16 ? 16 : (D <= 32 ? 32 : 64);
-    const uint32_t n = split ? std::max(2 * K, Kpad_next) : K;
-    // <= dist_part capacity; small codebooks in one block (the grid-stride loop takes several rows
-    // per thread), which needs no cross-block count or fence (finalize_block_done)
-    const uint32_t grid = n <= FIN_ONE_BLOCK_ROWS ? 1u : std::min<uint32_t>((n + 256 / L - 1) / (256 / L), 512);
-    FinArgs a = fin_args(sums, K, D, Dp, R, bias, scale, C_cent, split, C64n, Kpad_next, mu, sx, t, C32, cb_rows,
-                         E32, host_cb, dist_out != nullptr);
-    a.ncopy = ncopy ? ncopy : 1;
-    a.gate = copy_gate;
-    a.ties = ties;
-    if (copy_stride) {
-        if (copy_stride < 2 * (uint64_t)K * D + K) return hipErrorInvalidValue;
-        a.cstride = copy_stride;
-    }
-    if (perm) {   // the last block orders the next search's code vectors (needs the done counter)
-        if (!done || !split || 2 * K > PRUNE_MAXK || Kpad_next % 32 || Kpad_next > PRUNE_MAXK) return hipErrorInvalidValue;
-        a.perm = perm;
-        a.tint = tint;
-        a.qproj = reinterpret_cast<float *>(tint + 2 * PRUNE_MAXT);   // (the envelopes' region is fixed)
-    }
-    if (zero_sums) {   // copies zero_skip .. ncopy - 1
-        if (zero_skip >= a.ncopy) return hipErrorInvalidValue;
-        a.zero_after = const_cast<uint64_t *>(sums) + (uint64_t)zero_skip * a.cstride;
-        a.n_zero = (uint32_t)((a.ncopy - zero_skip - 1) * a.cstride + 2 * (uint64_t)K * D + K);
-    }
-    hipLaunchKernelGGL(finalize_prep_kernel, dim3(grid), dim3(256), 0, s, a, dist_part, done, dist_out,
-                       (volatile uint64_t *)ready, seq, L);
-    return hipGetLastError();
-}
-
-// finalize without the tables (qvq_update): C_cent only.
-hipError_t launch_finalize(hipStream_t s, const uint64_t *sums, uint32_t K, uint32_t D, int64_t R, int64_t bias,
-                           int scale, double *C_cent) {
-    return launch_finalize_prep(s, sums, K, D, (D + 3) & ~3u, R, bias, scale, C_cent, false, nullptr, 0, 0, 0, 0,
-                                nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, false, 1,
-                                nullptr, nullptr, 0, 0, nullptr);
-}
-
-// Search tables from an fp64 codebook: fp32 [Kpad][Dp] (VALU path and the MFMA recompute)
-// and the f16 MFMA rows (D = 12 or wide layout, common.hpp).  Code vectors K..Kpad-1 are padding
-// that never wins.
-__device__ inline void prep_row(const double *v, uint32_t D, uint32_t Dp, double mu, double sx, double scale_t,
-                                float *__restrict__ c32, _Float16 *__restrict__ r, float *__restrict__ e32) {
-    const uint32_t RF = cb_row_f16(D, Dp), LO = cb_lo_off(D, Dp);
-    double n = 0;
-    for (uint32_t i = 0; i < RF; i++) r[i] = (_Float16)0.f;
-    for (uint32_t d = 0; d < Dp; d++) {
-        const double x = d < D ? v[d] : 0.0;
-        c32[d] = (float)x;
-        if (d < D) {
-            const double cp = x - mu;
-            n += cp * cp;
-            const double c2 = -2.0 * sx * cp * scale_t;
-            const _Float16 h = (_Float16)(float)c2;
-            r[cb_hi_slot(D, Dp, d)] = h;
-            r[cb_lo_slot(D, Dp, d)] = (_Float16)(float)(c2 - (double)(float)h);
-            if (e32) e32[d] = (float)c2;
-        }
-    }
-    n *= scale_t;
-    if (e32)
-        for (uint32_t d = D; d < 16; d++) e32[d] = d == D ? (float)n : 0.f;
-    const _Float16 h = (_Float16)(float)n;
-    r[2 * LO] = h;
-    r[2 * LO + 1] = (_Float16)(float)(n - (double)(float)h);
-}
-
-__device__ inline void prep_pad_row(uint32_t D, uint32_t Dp, float *__restrict__ c32, _Float16 *__restrict__ r,
-                                    float *__restrict__ e32) {
-    const uint32_t RF = cb_row_f16(D, Dp), LO = cb_lo_off(D, Dp);
-    for (uint32_t d = 0; d < Dp; d++) c32[d] = 0.f;
-    if (e32)
-        for (uint32_t d = 0; d < 16; d++) e32[d] = d == D ? 1e30f : 0.f;   // never wins
-    for (uint32_t i = 0; i < RF; i++) r[i] = (_Float16)0.f;
-    r[2 * LO] = (_Float16)MF_PAD_SCORE;
-    r[2 * LO + 1] = (_Float16)MF_PAD_SCORE;
-}
-
-__global__ void prep_kernel(const double *__restrict__ C64, uint32_t K, uint32_t Kpad, uint32_t D, uint32_t Dp,
-                            double mu, double sx, double scale_t, float *__restrict__ C32,
-                            _Float16 *__restrict__ rows, float *__restrict__ E32) {
-    const uint32_t RF = cb_row_f16(D, Dp);
-    for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < Kpad; k += gridDim.x * blockDim.x) {
-        float *e32 = E32 ? E32 + (uint64_t)k * 16 : nullptr;
-        if (k >= K) {
-            prep_pad_row(D, Dp, C32 + (uint64_t)k * Dp, rows + (uint64_t)k * RF, e32);
-            continue;
-        }
-        double v[64];
-        for (uint32_t d = 0; d < D; d++) v[d] = C64[(uint64_t)k * D + d];
-        prep_row(v, D, Dp, mu, sx, scale_t, C32 + (uint64_t)k * Dp, rows + (uint64_t)k * RF, e32);
-    }
-}
-
-hipError_t launch_prep(hipStream_t s, const double *C64, uint32_t K, uint32_t Kpad, uint32_t D, uint32_t Dp,
-                       double mu, double sx, int t, float *C32, _Float16 *cb_rows, float *E32) {
-    hipLaunchKernelGGL(prep_kernel, dim3((Kpad + 255) / 256), dim3(256), 0, s, C64, K, Kpad, D, Dp, mu, sx,
-                       std::ldexp(1.0, t), C32, cb_rows, D == MF_D ? E32 : nullptr);
     return hipGetLastError();
 }
 

@@ -1,5 +1,5 @@
-// prune_order.hpp -- the pruned searches' code-vector order (device code shared by the finalize
-// kernels of k_misc.hip and k_refine.hip).
+// prune_order.hpp -- the pruned searches' code-vector order (device code of the finalize kernel,
+// k_finalize.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

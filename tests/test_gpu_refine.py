@@ -64,7 +64,7 @@ def test_fixed_point(engine, name):
 
 
 def test_pruned_search_k512(engine):
-    """K = 512: the pruned MFMA search over refine_finalize_kernel's tile order, the MFMA recheck."""
+    """K = 512: the pruned MFMA search over the same-K finalize_kernel's tile order, the MFMA recheck."""
     S, bits = 256, 9
     rgb, X = ref.case_vectors(S, 2)
     engine.set_images(rgb, 1, S, S, 2, 2, quant_amd.SCALED)

@@ -31,7 +31,7 @@ def short(name):
     if m2:
         return "assign_mfma_kernel<%s,%s>" % ("fused" if m2.group(1) == "1" else "plain",
                                               "staged" if m2.group(2) == "1" else "global")
-    for key in ["mean_sums_kernel", "finalize_prep_kernel", "recheck_mf32_kernel", "recheck_kernel",
+    for key in ["mean_sums_kernel", "finalize_kernel", "recheck_mf32_kernel", "recheck_kernel",
                 "decode_rows_h_kernel", "decode_rows_kernel", "decode_pixels_kernel", "kd_resolve_kernel", "kd_reduce_kernel",
                 "reduce_kernel",
                 "update_kernel", "assign_valu_kernel", "tile_kernel", "gen_kernel", "byte_hist_kernel",
