@@ -308,6 +308,22 @@ typedef struct {
                                that build; QVQ_KDTREE=host builds no tree image: 0) */
 } qvq_plan;
 QVQ_API qvq_status qvq_host_plan(uint32_t dim, uint32_t K, uint64_t n, qvq_plan *out);
+/* The same for an exact-mode training set (qvq_set_vectors_exact) of dim <= 64 components and a codebook
+ * of K code vectors, from the constants the exact kernels' launchers use (quant_amd/csrc/exact_plan.hpp).
+ * For tests that want a given chunk or tile edge to run (tests/helpers/exact_cases.py). */
+typedef struct {
+    uint32_t kc;            /* code vectors per LDS chunk of the fp64 search */
+    uint32_t chunks;        /* ceil(K / kc); 1: the whole-codebook path (grid-stride over rows) */
+    uint32_t last_chunk;    /* code vectors in the last chunk, 1 .. kc */
+    uint32_t templated;     /* 1: the row is held in registers (dim 3, 6, 12, 48) */
+    uint32_t tile_rows;     /* T: rows per LDS tile of the Kahan chains (centroids and the mean) */
+} qvq_exact_plan;
+QVQ_API qvq_status qvq_host_exact_plan(uint32_t dim, uint32_t K, qvq_exact_plan *out);
+/* The exact kernels' grid caps, in blocks of `block` rows: more than cap * block rows take the
+ * kernel's grid-stride loop a second time (the search, the row-number fill of qvq_set_vectors_exact,
+ * the distortion). */
+typedef struct { uint32_t block, assign_blocks, iota_blocks, dist_blocks; } qvq_exact_grids;
+QVQ_API qvq_status qvq_host_exact_grids(qvq_exact_grids *out);
 /* The engine's bounded-wait policy (quant_amd/csrc/wait.hpp) driven by scripted probes, for
  * tests: scenario 0 the work publishes after ~5 ms; 1 it never does, no communicator; 2 it
  * never does, a healthy communicator; 3 the communicator reports an error after ~5 ms; 4 the

@@ -42,6 +42,14 @@ class _Plan(ctypes.Structure):
                                                 "recheck", "update", "update_copies", "prune", "device_tree")]
 
 
+class _ExactPlan(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_uint32) for f in ("kc", "chunks", "last_chunk", "templated", "tile_rows")]
+
+
+class _ExactGrids(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_uint32) for f in ("block", "assign_blocks", "iota_blocks", "dist_blocks")]
+
+
 # qvq_plan enumerators (qvq.h)
 PLAN_SEARCH_SMALL, PLAN_SEARCH_MF32, PLAN_SEARCH_WIDE, PLAN_SEARCH_VALU = 0, 1, 2, 3
 PLAN_RECHECK_MF32, PLAN_RECHECK_STAGED, PLAN_RECHECK_CHUNKED, PLAN_RECHECK_GLOBAL = 0, 1, 2, 3
@@ -55,7 +63,8 @@ EXPORTED = ["qvq_create", "qvq_destroy", "qvq_last_error", "qvq_version", "qvq_s
             "qvq_host_finalize", "qvq_host_row_terms", "qvq_decode", "qvq_decode_mse", "qvq_decode_device",
             "qvq_set_timeout", "qvq_host_wait_probe", "qvq_comm_init_host", "qvq_comm_info", "qvq_set_vectors_exact",
             "qvq_update_kahan_split", "qvq_host_pool_stress", "qvq_kdtree_device_check",
-            "qvq_host_kdtree_image", "qvq_refine", "qvq_host_plan"]
+            "qvq_host_kdtree_image", "qvq_refine", "qvq_host_plan", "qvq_host_exact_plan",
+            "qvq_host_exact_grids"]
 
 COMM_NONE, COMM_RCCL, COMM_HOST = 0, 1, 2
 REFINE_FRESH = 1                              # qvq_refine flags
@@ -109,6 +118,8 @@ def lib():
             "qvq_comm_info": ([P, ctypes.POINTER(i), ctypes.POINTER(i), ctypes.POINTER(i)], i),
             "qvq_refine": ([P, u32, P, u32, ctypes.c_double, u32, P, P, P, P, P, P], i),
             "qvq_host_plan": ([u32, u32, u64, ctypes.POINTER(_Plan)], i),
+            "qvq_host_exact_plan": ([u32, u32, ctypes.POINTER(_ExactPlan)], i),
+            "qvq_host_exact_grids": ([ctypes.POINTER(_ExactGrids)], i),
         }
         for name, (args, res) in sig.items():
             if os.environ.get("QVQ_LIB") and not hasattr(L, name):
@@ -398,6 +409,21 @@ def host_plan(dim, K, n):
     p = _Plan()
     _check(lib().qvq_host_plan(int(dim), int(K), int(n), ctypes.byref(p)))
     return {f: int(getattr(p, f)) for f, _ in _Plan._fields_}
+
+
+def host_exact_plan(dim, K):
+    """The exact mode's dispatch for dim components and K code vectors (qvq_host_exact_plan): a dict
+    of the qvq_exact_plan fields."""
+    p = _ExactPlan()
+    _check(lib().qvq_host_exact_plan(int(dim), int(K), ctypes.byref(p)))
+    return {f: int(getattr(p, f)) for f, _ in _ExactPlan._fields_}
+
+
+def host_exact_grids():
+    """The exact kernels' grid caps (qvq_host_exact_grids): a dict of the qvq_exact_grids fields."""
+    g = _ExactGrids()
+    _check(lib().qvq_host_exact_grids(ctypes.byref(g)))
+    return {f: int(getattr(g, f)) for f, _ in _ExactGrids._fields_}
 
 
 # KdbNode (kdtree_dev.hpp) and the image layout of qvq_host_kdtree_image

@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "exact_plan.hpp"
 #include "kdtree.hpp"
 #include "qvq.h"
 #include "wait.hpp"
@@ -3714,6 +3715,27 @@ QVQ_API qvq_status qvq_host_plan(uint32_t dim, uint32_t K, uint64_t n, qvq_plan 
     }
     p.device_tree = !env_is("QVQ_KDTREE", "host") && device_tree_shape(K, dim);
     *out = p;
+    return QVQ_OK;
+}
+
+QVQ_API qvq_status qvq_host_exact_plan(uint32_t dim, uint32_t K, qvq_exact_plan *out) {
+    if (!out || dim == 0 || dim > 64 || K == 0) return QVQ_EINVAL;
+    qvq_exact_plan p;
+    p.kc = exact_chunk_codes(dim);
+    p.chunks = (K + p.kc - 1) / p.kc;
+    p.last_chunk = K - (p.chunks - 1) * p.kc;
+    p.templated = exact_templated(dim) ? 1 : 0;
+    p.tile_rows = exact_tile_rows(dim);
+    *out = p;
+    return QVQ_OK;
+}
+
+QVQ_API qvq_status qvq_host_exact_grids(qvq_exact_grids *out) {
+    if (!out) return QVQ_EINVAL;
+    out->block = EX_THREADS;
+    out->assign_blocks = EX_ASSIGN_GRID_CAP;
+    out->iota_blocks = EX_IOTA_GRID_CAP;
+    out->dist_blocks = EX_DIST_GRID_CAP;
     return QVQ_OK;
 }
 

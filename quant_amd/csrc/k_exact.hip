@@ -18,16 +18,15 @@
 #include <hipcub/hipcub.hpp>
 
 #include "common.hpp"
+#include "exact_plan.hpp"
 
 namespace qvq {
-
-constexpr int EX_THREADS = 256;
 
 // A[row] = the lexicographic (fp64 distance, index) minimum over the K code vectors of C ([K][D]);
 // rows whose best two distances are within tie_rel go to ties.  The codebook is staged in LDS
 // in chunks of kc code vectors (kc * D * 8 <= EX_LDS_BYTES; one chunk when it fits), ascending,
-// so every row still scans k in ascending order; each lane keeps its row's best two across chunks.
-constexpr uint32_t EX_LDS_BYTES = 64 * 1024;
+// so every row still scans k in ascending order; each lane keeps its row's best two across chunks
+// (EX_LDS_BYTES and kc: exact_plan.hpp).
 
 // ref_l2_hd (kdtree_dev.hpp) with the dimension known at compile time: the same operations in
 // the same order, the row held in registers (with a run-time dimension every code vector re-read
@@ -181,7 +180,6 @@ __global__ __launch_bounds__(EX_THREADS) void kahan_centroids_kernel(const doubl
 // global loads (order, then the row) per 16 steps; here the chain only waits on LDS reads issued
 // 16 ahead of the dependent adds.
 constexpr int KC_THREADS = 256;
-constexpr uint32_t KC_TILE_BYTES = 32 * 1024;   // two buffers: the 64 KB dynamic LDS default
 constexpr uint32_t KC_MAX_K = 1u << 20;   // every level (the largest cell sets a level's time)
 
 __global__ __launch_bounds__(KC_THREADS) void kahan_chains_lds_kernel(const double *__restrict__ X, uint64_t N,
@@ -190,7 +188,7 @@ __global__ __launch_bounds__(KC_THREADS) void kahan_chains_lds_kernel(const doub
                                                                       uint64_t *__restrict__ cnt) {
     extern __shared__ double tiles[];   // [2][T * D]
     const uint32_t k = blockIdx.x;
-    const uint32_t T = KC_TILE_BYTES / 8 / D;
+    const uint32_t T = exact_tile_rows(D);
     const uint64_t b = order ? koff[k] : 0, e = order ? koff[k + 1] : N;
     const uint64_t n = e - b, ntiles = (n + T - 1) / T;
     const uint32_t wave = threadIdx.x / 64, lane = threadIdx.x % 64;
@@ -314,21 +312,25 @@ __global__ void exact_fix_kernel(uint32_t *__restrict__ A, const uint32_t *__res
     if (t < n) A[rows[t]] = vals[t];
 }
 
-static int grid_for(uint64_t items, int cap = 4096) {
+static int grid_for(uint64_t items, int cap) {
     return (int)std::max<uint64_t>(1, std::min<uint64_t>((items + EX_THREADS - 1) / EX_THREADS, (uint64_t)cap));
 }
 
 hipError_t launch_exact_assign(hipStream_t s, const double *X, uint64_t N, uint32_t D, const double *C, uint32_t K,
                                double tie_rel, uint32_t *A, uint32_t *ties, unsigned *tie_cnt) {
-    const uint32_t kc = (uint32_t)std::max<size_t>(1, EX_LDS_BYTES / (8 * (size_t)D));   // code vectors per chunk
+    const uint32_t kc = exact_chunk_codes(D);
     const size_t lds = (size_t)std::min(kc, K) * D * 8;
-    const dim3 grid(grid_for(N, 8192)), block(EX_THREADS);
+    const dim3 grid(grid_for(N, EX_ASSIGN_GRID_CAP)), block(EX_THREADS);
+    if (!exact_templated(D)) {
+        hipLaunchKernelGGL(exact_assign_kernel<0>, grid, block, lds, s, X, N, D, C, K, kc, tie_rel, A, ties, tie_cnt);
+        return hipGetLastError();
+    }
     switch (D) {   // the dimensions of the reference's block shapes held in registers
     case 3: hipLaunchKernelGGL(exact_assign_kernel<3>, grid, block, lds, s, X, N, D, C, K, kc, tie_rel, A, ties, tie_cnt); break;
     case 6: hipLaunchKernelGGL(exact_assign_kernel<6>, grid, block, lds, s, X, N, D, C, K, kc, tie_rel, A, ties, tie_cnt); break;
     case 12: hipLaunchKernelGGL(exact_assign_kernel<12>, grid, block, lds, s, X, N, D, C, K, kc, tie_rel, A, ties, tie_cnt); break;
     case 48: hipLaunchKernelGGL(exact_assign_kernel<48>, grid, block, lds, s, X, N, D, C, K, kc, tie_rel, A, ties, tie_cnt); break;
-    default: hipLaunchKernelGGL(exact_assign_kernel<0>, grid, block, lds, s, X, N, D, C, K, kc, tie_rel, A, ties, tie_cnt);
+    default: return hipErrorInvalidValue;   // exact_templated names a dimension without an instantiation
     }
     return hipGetLastError();
 }
@@ -345,13 +347,13 @@ hipError_t launch_exact_centroids(hipStream_t s, const double *X, uint64_t N, ui
                                   size_t temp_bytes, double *C, uint64_t *cnt) {
     // LDS-staged chains (a thread per chain only beyond their limits: D > 64 or K > KC_MAX_K)
     const bool lds_chains = D <= 64 && (!A || K <= KC_MAX_K);
-    const size_t lds_bytes = lds_chains ? 2 * (size_t)(KC_TILE_BYTES / 8 / D) * D * 8 : 0;
+    const size_t lds_bytes = lds_chains ? 2 * (size_t)exact_tile_rows(D) * D * 8 : 0;
     if (!A) {   // the mean: every row, in order
         if (lds_chains)
             hipLaunchKernelGGL(kahan_chains_lds_kernel, dim3(1), dim3(KC_THREADS), lds_bytes, s, X, N, D,
                                (const uint32_t *)nullptr, (const uint32_t *)nullptr, C, cnt);
         else
-            hipLaunchKernelGGL(kahan_centroids_kernel, dim3(grid_for((uint64_t)D)), dim3(EX_THREADS), 0, s, X, N, D,
+            hipLaunchKernelGGL(kahan_centroids_kernel, dim3(grid_for((uint64_t)D, 4096)), dim3(EX_THREADS), 0, s, X, N, D,
                                (const uint32_t *)nullptr, (const uint32_t *)nullptr, 1u, C, cnt);
         return hipGetLastError();
     }
@@ -375,13 +377,13 @@ __global__ void exact_iota_kernel(uint32_t *__restrict__ v, uint64_t N) {
         v[i] = (uint32_t)i;
 }
 hipError_t launch_exact_iota(hipStream_t s, uint32_t *v, uint64_t N) {
-    hipLaunchKernelGGL(exact_iota_kernel, dim3(grid_for(N)), dim3(EX_THREADS), 0, s, v, N);
+    hipLaunchKernelGGL(exact_iota_kernel, dim3(grid_for(N, EX_IOTA_GRID_CAP)), dim3(EX_THREADS), 0, s, v, N);
     return hipGetLastError();
 }
 
 hipError_t launch_exact_distortion(hipStream_t s, const double *X, uint64_t N, uint32_t D, const double *C,
                                    const uint32_t *A, double *part, double *out) {
-    const int g = grid_for(N, 1024);
+    const int g = grid_for(N, EX_DIST_GRID_CAP);
     hipLaunchKernelGGL(exact_dist_kernel, dim3(g), dim3(EX_THREADS), 0, s, X, N, D, C, A, part);
     hipLaunchKernelGGL(exact_sum_kernel, dim3(1), dim3(1), 0, s, part, (uint32_t)g, 1.0 / ((double)N * (double)D), out);
     return hipGetLastError();

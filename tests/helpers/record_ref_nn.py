@@ -1,7 +1,8 @@
-"""Records tests/golden/ref_nn.json and tests/golden/ref_nn_neartie.json: what the compiled reference
-kd-tree (oracle/_ref/libref_nn.so, `make -C oracle ref` where the reference checkout is present)
-answers for the inputs of tests/test_oracle_golden.py's kd-tree tests and for every case of
-tests/helpers/neartie_cases.py, as fingerprints of its index arrays beside those of the codebooks it
+"""Records tests/golden/ref_nn.json, tests/golden/ref_nn_neartie.json and tests/golden/ref_nn_exact.json:
+what the compiled reference kd-tree (oracle/_ref/libref_nn.so, `make -C oracle ref` where the reference
+checkout is present) answers for the inputs of tests/test_oracle_golden.py's kd-tree tests, for every
+case of tests/helpers/neartie_cases.py, and for the chunk and near-tie cases of
+tests/helpers/exact_cases.py, as fingerprints of its index arrays beside those of the codebooks it
 was given.  Run from the repository root after a change of those inputs:
 
     python tests/helpers/record_ref_nn.py
@@ -15,6 +16,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__)))) 
 import numpy as np   # noqa: E402
 
 import test_oracle_golden as t   # noqa: E402
+from helpers import exact_cases as ex   # noqa: E402
 from helpers import neartie_cases as nt   # noqa: E402
 
 WHAT = ("sha-256[:16] of the compiled reference kd-tree's indices (A, little-endian u32) for the codebook "
@@ -43,6 +45,13 @@ def main():
         near["cases"][nt.key(c)] = record(C, X)
     with open(os.path.join(t.GOLDEN, "ref_nn_neartie.json"), "w") as f:
         json.dump(near, f, indent=1)
+        f.write("\n")
+    exact = {"what": WHAT, "cases": {}}
+    for c in ex.CHUNK_CASES + ex.NEARTIE_CASES:
+        X, C = ex.inputs(c)[:2]
+        exact["cases"][ex.key(c)] = record(C, X)
+    with open(os.path.join(t.GOLDEN, "ref_nn_exact.json"), "w") as f:
+        json.dump(exact, f, indent=1)
         f.write("\n")
 
 
