@@ -163,7 +163,24 @@ QVQ_API const uint32_t *qvq_assign_device(const qvq_ctx *ctx);
  * changed and dist_trace (max_iters entries each, the first info->iters written), info.
  * qvq_assign_device points at the returned assignment.  A later qvq_lbg on the context gives
  * exactly what it gave before.  Exact mode (qvq_set_vectors_exact, or its fallback inside
- * qvq_set_vectors) and a joined communicator return QVQ_EUNSUPPORTED.
+ * qvq_set_vectors) returns QVQ_EUNSUPPORTED.
+ *
+ * With a communicator (qvq_comm_init or qvq_comm_init_host, any nranks >= 1) every rank calls this
+ * on its own rows -- consecutive ranges of the global rows, rank 0 first, as for qvq_lbg -- with
+ * the same K, max_iters, eps and flags and the same C_start bytes (or NULL on every rank; it then
+ * continues from the sharded qvq_lbg or qvq_refine on the same communicator).  Every rank returns
+ * the same codebook, distortion, changed[], dist_trace[] and info: the values one rank would return
+ * over all the rows, bit for bit.  changed[] counts the rows of every rank (a warm start reports
+ * the global N at iteration 1) and the stop rule sees the global count and distortion only, so
+ * every rank stops at the same iteration.  assign and qvq_assign_device hold this rank's rows; the
+ * ranks' indices concatenate to the one-rank assignment.  Collectives per call: the histogram
+ * behind sum ||x||^2, one all-reduce per iteration run (the level's sums with the rows changed
+ * behind them) and one more with QVQ_REFINE_FRESH; several ranks first exchange their verdict on
+ * the call and a digest of its arguments: if a rank rejects its call (QVQ_ESTATE, QVQ_EINVAL,
+ * QVQ_EUNSUPPORTED) it returns that status, the other ranks return QVQ_EINVAL (qvq_last_error: a
+ * peer rejected the call), and so does every rank when the arguments differ; no rank's state is
+ * touched and none waits for a peer that will not come.  A collective that fails returns QVQ_ECOMM
+ * as everywhere (qvq_comm_init).
  */
 enum { QVQ_REFINE_FRESH = 1 };                    /* flags */
 enum { QVQ_STOP_FIXED = 0, QVQ_STOP_EPS = 1, QVQ_STOP_MAXIT = 2 };

@@ -235,7 +235,11 @@ class Engine:
         a K x dim array C is a warm start.  fresh=True returns the indices of the final codebook
         (one more assignment) and their distortion.  info: iters, stop (STOP_FIXED / STOP_EPS /
         STOP_MAXIT), changed (rows that moved, per iteration), distortion (per iteration).
-        want_assign=False leaves the indices on the device (A is None)."""
+        want_assign=False leaves the indices on the device (A is None).
+        With a communicator joined (comm_init / comm_init_host) every rank calls it with the same
+        arguments on its own rows: C, distortion and info are those of one rank over all the rows,
+        bit for bit and the same on every rank (changed counts every rank's rows), A is this rank's
+        rows.  A rank whose call is invalid raises its own status, its peers QVQ_EINVAL."""
         if C is not None:
             C = np.ascontiguousarray(C, np.float64)
             if C.ndim != 2 or C.shape[1] != self.dim or (K is not None and K != C.shape[0]):

@@ -409,6 +409,8 @@ struct FinArgs {
     unsigned *done = nullptr;         // block counter at 0, left at 0
     double *dist_out = nullptr;
     unsigned *changed = nullptr;      // launch_count_changed's total: published as pub[0] (null: 0), then cleared
+    uint64_t *changed64 = nullptr;    // or (a communicator): the all-reduced total behind the level's sums
+                                      // (launch_count_changed64), published and cleared the same way
     unsigned *clear_cnt = nullptr;    // the iteration's flag and tie counters (2), cleared for the next one
     uint64_t *pub = nullptr;          // [0] rows changed, [1] the distortion term's bits (0 without sums)
     uint64_t *ready = nullptr;
@@ -418,6 +420,10 @@ hipError_t launch_finalize(hipStream_t s, const FinArgs &f);
 // *out += the rows i < N with A[i] != B[i] (A, B 16-byte aligned).
 hipError_t launch_count_changed(hipStream_t s, int num_cu, const uint32_t *A, const uint32_t *B, uint64_t N,
                                 unsigned *out);
+// The same into a u64 total: the slot behind a level's sums, all-reduced with them (qvq_refine on
+// a communicator).
+hipError_t launch_count_changed64(hipStream_t s, int num_cu, const uint32_t *A, const uint32_t *B, uint64_t N,
+                                  uint64_t *out);
 hipError_t launch_gather_codes(hipStream_t s, const uint8_t *codes, uint32_t Dp, const uint32_t *rows, uint32_t n,
                                uint8_t *out);
 // Host-resolved rows: A[rows[i]] = vals[i]; with xslab their terms move from the

@@ -3231,32 +3231,74 @@ QVQ_API qvq_status qvq_update_kahan_split(qvq_ctx *ctx, const uint32_t *assign, 
 // the codebook its tree build needs; the stop decision of iteration t comes with that codebook,
 // after the search against C_t is enqueued.  A stop therefore leaves one search in flight: it is
 // the FRESH assignment when that is wanted, and is drained and dropped otherwise.
+// On a communicator the rows changed are counted into the u64 behind the level's
+// sums and one all-reduce per iteration, between the reduce and the finalize, carries both: the
+// codebook, the count and the distortion term -- all the stop rule reads -- are then the same on
+// every rank.  Several ranks first exchange their verdicts on the call (the entry vote).
 QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start, uint32_t max_iters, double eps,
                               uint32_t flags, double *codebook, uint32_t *assign, double *distortion,
                               uint64_t *changed, double *dist_trace, qvq_refine_info *info) {
     if (!ctx) return QVQ_EINVAL;
     GUARD(ctx);
-    if (ctx->N == 0) return fail(ctx, QVQ_ESTATE, "no training set");
     const bool fresh = (flags & QVQ_REFINE_FRESH) != 0;
-    if (flags & ~(uint32_t)QVQ_REFINE_FRESH) return fail(ctx, QVQ_EINVAL, "unknown refine flags");
-    if (max_iters == 0 && !fresh) return fail(ctx, QVQ_EINVAL, "max_iters = 0 needs QVQ_REFINE_FRESH");
-    if (K == 0 || K > (1u << 20)) return fail(ctx, QVQ_EINVAL, "K must be in 1 .. 2^20");
-    if (!(eps >= 0)) return fail(ctx, QVQ_EINVAL, "eps must be >= 0");
-    if (ctx->exact) return fail(ctx, QVQ_EUNSUPPORTED, "refinement of an exact-mode training set is not supported");
-    if (ctx->comm || ctx->host_ar)
-        return fail(ctx, QVQ_EUNSUPPORTED, "refinement with a communicator joined is not supported");
     const bool cont = C_start == nullptr;
-    if (cont) {
-        if (!ctx->rf.valid) return fail(ctx, QVQ_ESTATE, "no qvq_lbg or qvq_refine result to continue from");
-        if (ctx->rf.K != K) return fail(ctx, QVQ_EINVAL, "K differs from the result to continue from");
+    const bool sharded = ctx->comm || ctx->host_ar;
+    // this rank's own verdict on the call; with a communicator the ranks exchange it (below)
+    // before any of them returns
+    qvq_status lst = QVQ_OK;
+    const char *lmsg = "";
+    auto reject = [&](qvq_status s, const char *m) {
+        lst = s;
+        lmsg = m;
+    };
+    if (ctx->N == 0) reject(QVQ_ESTATE, "no training set");
+    else if (flags & ~(uint32_t)QVQ_REFINE_FRESH) reject(QVQ_EINVAL, "unknown refine flags");
+    else if (max_iters == 0 && !fresh) reject(QVQ_EINVAL, "max_iters = 0 needs QVQ_REFINE_FRESH");
+    else if (K == 0 || K > (1u << 20)) reject(QVQ_EINVAL, "K must be in 1 .. 2^20");
+    else if (!(eps >= 0)) reject(QVQ_EINVAL, "eps must be >= 0");
+    else if (ctx->exact) reject(QVQ_EUNSUPPORTED, "refinement of an exact-mode training set is not supported");
+    else if (cont) {
+        if (!ctx->rf.valid) reject(QVQ_ESTATE, "no qvq_lbg or qvq_refine result to continue from");
+        else if (ctx->rf.K != K) reject(QVQ_EINVAL, "K differs from the result to continue from");
     } else {
         double vmin, vmax, cmin, cmax;
         codebook_range(ctx->terms, vmin, vmax, cmin, cmax);
         // (the searches' error bands assume |c| <= 1.2 vmax: valu_coeffs, mf_th)
         for (uint64_t i = 0; i < (uint64_t)K * ctx->D; i++)
-            if (!(C_start[i] >= vmin && C_start[i] <= vmax))
-                return fail(ctx, QVQ_EINVAL, "starting codebook outside the colour space's value range");
+            if (!(C_start[i] >= vmin && C_start[i] <= vmax)) {
+                reject(QVQ_EINVAL, "starting codebook outside the colour space's value range");
+                break;
+            }
     }
+    if (sharded && ctx->nranks > 1) {
+        // The entry vote: every rank's verdict and a digest of its arguments, one slot pair per
+        // rank (the sum is then a gather: every rank sees the same table and decides alike).  No
+        // rank goes on to a per-iteration collective that a peer will not join.
+        uint64_t h = 0xcbf29ce484222325ull;   // FNV-1a
+        auto mix = [&](const void *p, uint64_t n) {
+            const uint8_t *b = static_cast<const uint8_t *>(p);
+            for (uint64_t i = 0; i < n; i++) h = (h ^ b[i]) * 0x100000001b3ull;
+        };
+        uint64_t ebits;
+        std::memcpy(&ebits, &eps, 8);
+        const uint64_t head[5] = {K, max_iters, ebits, flags, cont ? 1u : 0u};
+        mix(head, sizeof(head));
+        if (!cont && K >= 1 && K <= (1u << 20)) mix(C_start, (uint64_t)K * ctx->D * 8);
+        const uint32_t R = (uint32_t)ctx->nranks;
+        std::vector<uint64_t> v(2ull * R, 0);
+        v[2 * ctx->rank] = lst == QVQ_OK ? 1 : 2;   // (0: the rank wrote nothing)
+        v[2 * ctx->rank + 1] = h;
+        HIPCHK(hipSetDevice(ctx->dev));
+        qvq_status vs = vote(ctx, v.data(), v.size());
+        if (vs != QVQ_OK) return vs;
+        if (lst != QVQ_OK) return fail(ctx, lst, lmsg);
+        for (uint32_t r = 0; r < R; r++)
+            if (v[2 * r] != 1) return fail(ctx, QVQ_EINVAL, "a peer rank rejected the qvq_refine call");
+        for (uint32_t r = 0; r < R; r++)
+            if (v[2 * r + 1] != h)
+                return fail(ctx, QVQ_EINVAL, "qvq_refine arguments differ between the ranks");
+    }
+    if (lst != QVQ_OK) return fail(ctx, lst, lmsg);
     const double d0 = ctx->rf.dist;
     ctx->rf.valid = false;
     HIPCHK(hipSetDevice(ctx->dev));
@@ -3266,25 +3308,48 @@ QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start, u
     std::memset(&ctx->tm, 0, sizeof(ctx->tm));
     const uint32_t D = ctx->D;
     const uint64_t KD = (uint64_t)K * D;
-    if (!ctx->rf.have_xsq) {   // sum ||x||^2 and the rows, from the byte histogram
-        uint64_t hist[256];
-        HIPCHK(hipMemcpy(hist, ctx->d_hist, sizeof(hist), hipMemcpyDeviceToHost));
+    // sum ||x||^2 and the rows, from the byte histogram
+    auto hist_totals = [&](const uint64_t *hist, double &sq_out, uint64_t &rows_out) {
         long double sq = 0;
         uint64_t n = 0;
         for (int b = 0; b < 256; b++) {
             sq += (long double)hist[b] * (long double)ctx->terms.v64[b] * (long double)ctx->terms.v64[b];
             n += hist[b];
         }
-        ctx->rf.xsq = (double)sq;
-        ctx->rf.rows = (double)(n / D);
-        ctx->rf.have_xsq = true;
+        sq_out = (double)sq;
+        rows_out = n / D;
+    };
+    double xsq;
+    uint64_t rows_all;   // the rows of every rank
+    if (sharded) {   // of every rank's rows: the histogram all-reduced as integers, as qvq_lbg does (once per call)
+        HIPCHK(hipMemcpyAsync(ctx->d_hist + 256, ctx->d_hist, 256 * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        if ((st = all_reduce(ctx, ctx->d_hist + 256, 256, false)) != QVQ_OK) return st;
+        if ((st = ensure_pinned(ctx, ctx->h_stage, ctx->stage_bytes, 256 * 8)) != QVQ_OK) return st;
+        HIPCHK(hipMemcpyAsync(ctx->h_stage, ctx->d_hist + 256, 256 * 8, hipMemcpyDeviceToHost, ctx->stream));
+        if ((st = wait_stream(ctx)) != QVQ_OK) return st;   // bounded: the all-reduce may wait on peer ranks
+        hist_totals(static_cast<const uint64_t *>(ctx->h_stage), xsq, rows_all);
+    } else {
+        if (!ctx->rf.have_xsq) {   // once per training set
+            uint64_t hist[256], n;
+            HIPCHK(hipMemcpy(hist, ctx->d_hist, sizeof(hist), hipMemcpyDeviceToHost));
+            hist_totals(hist, ctx->rf.xsq, n);
+            ctx->rf.rows = (double)n;
+            ctx->rf.have_xsq = true;
+        }
+        xsq = ctx->rf.xsq;
+        rows_all = ctx->N;
     }
-    const double xsq = ctx->rf.xsq, norm = ctx->rf.rows * (double)D;
+    const double norm = (sharded ? (double)rows_all : ctx->rf.rows) * (double)D;
+    // a communicator: the rows changed are counted into the u64 behind the level's sums and
+    // all-reduced with them (one collective per iteration)
+    const uint64_t cell_u64 = 2 * KD + K;
+    uint64_t *const changed64 = sharded ? ctx->d_sums + cell_u64 : nullptr;
     if (!cont) HIPCHK(hipMemcpy(ctx->d_C64_cent, C_start, KD * 8, hipMemcpyHostToDevice));
     // both iterations' counters, the changed total; copy 1 of the sums if a quantize left it dirty
     HIPCHK(hipMemsetAsync(ctx->d_counters, 0, 4 * sizeof(unsigned), ctx->stream));
     HIPCHK(hipMemsetAsync(ctx->d_counters + CHANGED_COUNTER, 0, 2 * sizeof(unsigned), ctx->stream));
     if ((st = clear_dirty_sums(ctx)) != QVQ_OK) return st;
+    if (changed64) HIPCHK(hipMemsetAsync(changed64, 0, 8, ctx->stream));
     ctx->kd_pend = false;
     ctx->pub = PubArgs();
     const bool prune = use_prune(ctx, K);
@@ -3314,7 +3379,8 @@ QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start, u
         } else {
             f.measure = true;
         }
-        f.changed = count ? ctx->d_counters + CHANGED_COUNTER : nullptr;
+        if (count && changed64) f.changed64 = changed64;
+        else if (count) f.changed = ctx->d_counters + CHANGED_COUNTER;
         f.clear_cnt = cnts;
         f.pub = ctx->dh_ready + 4;
         f.seq = ++ctx->seq;
@@ -3322,7 +3388,8 @@ QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start, u
         if (tables) ctx->perm_k = prune ? K : 0;
         return QVQ_OK;
     };
-    // the sums of the assignment run_level just made, reduced into d_sums
+    // the sums of the assignment run_level just made, reduced into d_sums (a communicator:
+    // run_level has answered the kd-tree ties itself, the sums are one copy and there is no gate)
     auto reduce = [&](int slot, const unsigned *&gate) -> qvq_status {
         gate = ctx->sums_copies > 1 ? ctx->d_counters + 2 * slot + 1 : nullptr;
         return reduce_level(ctx, K, slot, nullptr);
@@ -3336,7 +3403,7 @@ QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start, u
     // iteration t's published count and distortion, and the stop rule
     auto absorb = [&]() {
         std::atomic_thread_fence(std::memory_order_acquire);
-        const uint64_t chg = (t == 1 && !cont) ? ctx->N : h_pub[0];
+        const uint64_t chg = (t == 1 && !cont) ? rows_all : h_pub[0];
         const uint64_t bits = h_pub[1];
         double term;
         std::memcpy(&term, &bits, 8);
@@ -3364,6 +3431,7 @@ QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start, u
         if (stop >= 0) {
             if (fresh) {   // the search in flight is A* = assign(C_t): its sums, the distortion of (C_t, A*)
                 if ((st = reduce(slot, gate)) != QVQ_OK) return st;
+                if ((st = all_reduce_sums(ctx, K)) != QVQ_OK) return st;   // every rank's rows of A*
                 if ((st = publish(t, false, ctx->d_sums, gate, ctx->d_counters + 2 * slot, false)) != QVQ_OK) return st;
                 ctx->sums1_dirty = false;
                 if ((st = wait_codebook(ctx, ctx->seq)) != QVQ_OK) return st;
@@ -3380,9 +3448,16 @@ QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start, u
             break;
         }
         if ((st = reduce(slot, gate)) != QVQ_OK) return st;
-        if (have_A) HIPCHK(launch_count_changed(ctx->stream, ctx->num_cu, ctx->d_A, ctx->d_A_alt, ctx->N,
-                                                ctx->d_counters + CHANGED_COUNTER));
-        if ((st = publish(t + 1, true, ctx->d_sums, gate, ctx->d_counters + 2 * slot, have_A)) != QVQ_OK) return st;
+        if (changed64) {   // the level's sums and the rows changed over every rank: one collective
+            ctx->sums1_dirty = true;   // (the slot lies in copy 1's range: cleared if the call ends before the finalize)
+            if (have_A) HIPCHK(launch_count_changed64(ctx->stream, ctx->num_cu, ctx->d_A, ctx->d_A_alt, ctx->N, changed64));
+            if ((st = all_reduce(ctx, ctx->d_sums, cell_u64 + 1, false)) != QVQ_OK) return st;
+        } else if (have_A) {
+            HIPCHK(launch_count_changed(ctx->stream, ctx->num_cu, ctx->d_A, ctx->d_A_alt, ctx->N,
+                                        ctx->d_counters + CHANGED_COUNTER));
+        }
+        if ((st = publish(t + 1, true, ctx->d_sums, gate, ctx->d_counters + 2 * slot, have_A || changed64)) != QVQ_OK)
+            return st;
         ctx->sums1_dirty = false;
         have_A = true;
         t++;

@@ -189,10 +189,11 @@ __device__ void finalize_block_done(const FinDev &a, double term, bool open) {
         *a.done = 0;
         if (a.dist_out) a.dist_out[0] = total;
         if (a.pub) {
-            a.pub[0] = a.changed ? (uint64_t)*a.changed : 0;
+            a.pub[0] = a.changed64 ? *a.changed64 : (a.changed ? (uint64_t)*a.changed : 0);
             a.pub[1] = a.dist ? (uint64_t)__double_as_longlong(total) : 0;
         }
         if (a.changed) *a.changed = 0;
+        if (a.changed64) *a.changed64 = 0;
         if (a.clear_cnt) a.clear_cnt[0] = a.clear_cnt[1] = 0;
         if (a.ready) {
             __threadfence_system();
@@ -233,11 +234,14 @@ __global__ __launch_bounds__(256) void finalize_kernel(FinDev a, uint32_t L) {
 }
 
 // Rows whose code vector differs between two assignments: 16-byte loads, a wave reduction, one
-// atomic per workgroup.  8 bytes of HBM traffic per row and nothing else.
+// atomic per workgroup.  8 bytes of HBM traffic per row and nothing else.  T: the total's type
+// (unsigned: one rank's counter; unsigned long long: the slot behind the level's sums, which is
+// all-reduced with them).
 constexpr int CHG_THREADS = 256;
+template <typename T>
 __global__ __launch_bounds__(CHG_THREADS) void count_changed_kernel(const uint32_t *__restrict__ A,
                                                                     const uint32_t *__restrict__ B, uint64_t N,
-                                                                    unsigned *__restrict__ out) {
+                                                                    T *__restrict__ out) {
     __shared__ unsigned wsum[CHG_THREADS / 64];
     const uint64_t n4 = N / 4;
     const uint4 *A4 = reinterpret_cast<const uint4 *>(A), *B4 = reinterpret_cast<const uint4 *>(B);
@@ -254,7 +258,7 @@ __global__ __launch_bounds__(CHG_THREADS) void count_changed_kernel(const uint32
     if (threadIdx.x == 0) {
         unsigned t = 0;
         for (int w = 0; w < CHG_THREADS / 64; w++) t += wsum[w];
-        if (t) atomicAdd(out, t);
+        if (t) atomicAdd(out, (T)t);
     }
 }
 
@@ -275,7 +279,9 @@ hipError_t launch_finalize(hipStream_t s, const FinArgs &f) {
     if (f.zero_sums && (!f.done || !f.sums || f.zero_skip >= f.ncopy)) return hipErrorInvalidValue;   // the last block's
     if (f.cstride && f.cstride < cell_u64) return hipErrorInvalidValue;
     // what the last block publishes needs its counter, and the host a ready number to wait for
-    if ((f.dist_out || f.ready || f.pub || f.changed || f.clear_cnt) && !f.done) return hipErrorInvalidValue;
+    if ((f.dist_out || f.ready || f.pub || f.changed || f.changed64 || f.clear_cnt) && !f.done)
+        return hipErrorInvalidValue;
+    if (f.changed && f.changed64) return hipErrorInvalidValue;
     if (f.pub && (!f.ready || !f.dist_part)) return hipErrorInvalidValue;
     FinDev a;
     static_cast<FinArgs &>(a) = f;
@@ -304,12 +310,27 @@ hipError_t launch_finalize(hipStream_t s, const FinArgs &f) {
     return hipGetLastError();
 }
 
+namespace {
+inline int changed_grid(int num_cu, uint64_t N) {
+    const uint64_t want = (N / 4 + CHG_THREADS - 1) / CHG_THREADS / 4 + 1;   // ~4 loads in flight per thread
+    return (int)std::min<uint64_t>(want, (uint64_t)std::max(num_cu, 1) * 8);
+}
+}  // namespace
+
 hipError_t launch_count_changed(hipStream_t s, int num_cu, const uint32_t *A, const uint32_t *B, uint64_t N,
                                 unsigned *out) {
     if (!A || !B || !out || N == 0) return hipErrorInvalidValue;
-    const uint64_t want = (N / 4 + CHG_THREADS - 1) / CHG_THREADS / 4 + 1;   // ~4 loads in flight per thread
-    const int grid = (int)std::min<uint64_t>(want, (uint64_t)std::max(num_cu, 1) * 8);
-    hipLaunchKernelGGL(count_changed_kernel, dim3(grid), dim3(CHG_THREADS), 0, s, A, B, N, out);
+    hipLaunchKernelGGL(count_changed_kernel<unsigned>, dim3(changed_grid(num_cu, N)), dim3(CHG_THREADS), 0, s, A, B, N,
+                       out);
+    return hipGetLastError();
+}
+
+hipError_t launch_count_changed64(hipStream_t s, int num_cu, const uint32_t *A, const uint32_t *B, uint64_t N,
+                                  uint64_t *out) {
+    if (!A || !B || !out || N == 0) return hipErrorInvalidValue;
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the u64 slot");
+    hipLaunchKernelGGL(count_changed_kernel<unsigned long long>, dim3(changed_grid(num_cu, N)), dim3(CHG_THREADS), 0,
+                       s, A, B, N, reinterpret_cast<unsigned long long *>(out));
     return hipGetLastError();
 }
 

@@ -15,6 +15,11 @@ reads nothing outside the repository.  Prints one JSON object (and writes it wit
                         PCIe both ways each iteration), per iteration, median over reps
   distortion_lbg / distortion_refined, iters, stop, changed (first run)
 
+--comm rccl1 joins a one-rank RCCL communicator before the timed loops: every collective of the
+sharded schedule (per iteration the all-reduce of the level's sums and the rows changed) then runs
+through ncclAllReduce, and the results stay the one-rank results.  --composed-reps 0 leaves the
+composed loop out.
+
 Every timed call ends in the engine's own wait for its results; the first --warmup repetitions of
 each leg are not timed.
 """
@@ -38,6 +43,7 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--composed-reps", type=int, default=2)
+    ap.add_argument("--comm", choices=["none", "rccl1"], default="none")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
 
@@ -49,8 +55,11 @@ def main():
         r = fn()
         return (time.perf_counter() - t0) * 1e3, r
 
-    res = {"workload": "%dx%d_b%d_bits%d" % (a.size, a.size, a.block, a.bits), "iters_asked": a.iters}
+    res = {"workload": "%dx%d_b%d_bits%d" % (a.size, a.size, a.block, a.bits), "iters_asked": a.iters,
+           "comm": a.comm}
     with quant_amd.Engine(0) as eng:
+        if a.comm == "rccl1":
+            eng.comm_init(1, 0, quant_amd.Engine.comm_unique_id())
         eng.set_synthetic(a.size, 0x5EED, 1, a.block, a.block, quant_amd.SCALED)
         res["blocks"] = eng.n
         t_lbg, t_ref, t_one = [], [], []
@@ -85,7 +94,7 @@ def main():
         # the composed loop: the same iterations over the existing single-step entries
         K = 1 << a.bits
         t_comp = []
-        for rep in range(1 + a.composed_reps):
+        for rep in range(1 + a.composed_reps if a.composed_reps else 0):
             C, _, _ = eng.lbg(a.bits, want_assign=False)
             t0 = time.perf_counter()
             for _ in range(n):
@@ -93,8 +102,9 @@ def main():
                 C, _ = eng.update(A, K)
             if rep >= 1:
                 t_comp.append((time.perf_counter() - t0) * 1e3 / n)
-        res["composed_iter_ms"] = statistics.median(t_comp)
-        res["composed_over_device"] = res["composed_iter_ms"] / res["iter_ms"]
+        if t_comp:
+            res["composed_iter_ms"] = statistics.median(t_comp)
+            res["composed_over_device"] = res["composed_iter_ms"] / res["iter_ms"]
         res["iter_over_level10"] = res["iter_ms"] / res["lbg_level10_ms"]
     line = json.dumps(res)
     print(line)
