@@ -304,9 +304,9 @@ QVQ_API qvq_status qvq_host_finalize(const uint64_t *hi, const uint64_t *lo, con
 QVQ_API qvq_status qvq_host_row_terms(const uint8_t *codes, uint32_t dim, int colorspace, uint64_t *hi,
                                       uint64_t *lo);
 /* The kernels a shape dispatches to: a training set of n rows of dim components and a codebook of K
- * code vectors (qvq_assign, qvq_update, or a qvq_lbg level of that K), answered by the predicates
- * the engine itself dispatches with, under the same QVQ_SEARCH / QVQ_KDTREE environment.  For
- * tests that want a given path to run (tests/helpers/largek_cases.py). */
+ * code vectors (qvq_assign, qvq_update, or a qvq_lbg level of that K): the plan the engine makes
+ * for such a level and its run_level switches on, field by field, under the same QVQ_SEARCH /
+ * QVQ_KDTREE environment.  For tests that want a given path to run (tests/helpers/largek_cases.py). */
 enum { QVQ_PLAN_SEARCH_SMALL = 0, QVQ_PLAN_SEARCH_MF32 = 1, QVQ_PLAN_SEARCH_WIDE = 2, QVQ_PLAN_SEARCH_VALU = 3 };
 enum { QVQ_PLAN_RECHECK_MF32 = 0, QVQ_PLAN_RECHECK_STAGED = 1, QVQ_PLAN_RECHECK_CHUNKED = 2,
        QVQ_PLAN_RECHECK_GLOBAL = 3 };

@@ -302,17 +302,12 @@ struct qvq_ctx {
     int job_buf = 0;
     KdView job_kd;
     uint64_t tree_cap = 0;
-    uint32_t nslabs = 0;   // slabs holding the last run_level's sums
     uint32_t col_blocks = 0;   // blocks per image column (consecutive rows run down a column); 0: no image
-    bool kd_pend = false;      // run_level left its kd-tree ties to kd_reduce_kernel (pend_kd)
-    PubArgs pub;               // run_level left its tie-count publication to the next reduce
-    uint32_t sums_copies = 1;  // 2: run_level's tie moves are in copy 1 of d_sums (the finalize adds it)
-    KdView pend_kd{};
-    bool sums1_dirty = false;  // copy 1 of d_sums may hold moves (a quantize that stopped early)
+    // copy 1 of d_sums may hold moves that no finalize has taken (a call that stopped between the
+    // two): raised by mark_sums1, lowered by run_finalize and clear_dirty_sums, nowhere else
+    bool sums1_dirty = false;
     uint64_t sums_bytes = 0;
-    uint32_t nsub = 0;     // ... of which the last nsub are subtracted
     int timing_level = -2;   // qvq_set_timing: -1 all levels, -2 none (default), else that level only
-    bool upd[32] = {};
     hipEvent_t ev_end = nullptr;
     hipEvent_t ev_sync = nullptr;   // wait_stream
     double timeout_s = 120;         // bound of every host wait (qvq_set_timeout, QVQ_TIMEOUT_S)
@@ -388,32 +383,33 @@ void dfree(T *&p) {
 }
 
 uint32_t pad32(uint32_t K) { return (K + 31) & ~31u; }   // MFMA tile pairs
-bool kahan_mode(const qvq_ctx *ctx);
-double tie_band(const qvq_ctx *ctx);
-// The path knobs a test exercises: QVQ_SEARCH=valu (the VALU search at every K) and
-// QVQ_KDTREE=host (ties answered on the host); QVQ_KAHAN=0 / QVQ_SPECULATE=0 (index rule and
-// schedule); QVQ_KAHAN_FAIL_LEVEL / _RANK (forced check failures).
-// qvq_host_plan reports what the predicates below pick for a shape.
 bool env_is(const char *name, const char *val) {
     const char *v = std::getenv(name);
     return v && std::strcmp(v, val) == 0;
 }
-bool use_mfma(const qvq_ctx *ctx, uint32_t K) {
-    return ctx->D == MF_D && mf_can_search(K) && !env_is("QVQ_SEARCH", "valu");
-}
+
+// The dispatch of one level (N rows of D components, Dp padded, against K code vectors), decided
+// once by plan_level: run_level and the finalize builders switch on it, qvq_host_plan reports it
+// (DESIGN.md 6.1).  What depends on the call and not on the shape (sums wanted, the tile order at
+// hand, a communicator, deferred ties) meets the plan at the top of run_level.
+struct LevelPlan {
+    uint32_t search = QVQ_PLAN_SEARCH_VALU;   // QVQ_PLAN_SEARCH_* (qvq.h)
+    bool fusable = false;        // the sums can ride in the search (MFMA, K <= mf_fuse_max_k())
+    bool prunable = false;       // the finalize before this level writes its tile order
+    bool c32_staged = false;     // MF32: fp32 codebook in LDS when the search runs unfused, unpruned
+    bool cb_resident = false;    // WIDE: whole codebook in LDS
+    uint32_t valu_tiles = 0;     // VALU: codebook tiles
+    uint32_t recheck = 0;        // QVQ_PLAN_RECHECK_*: the MFMA recheck, or launch_recheck's path
+    bool sorted_sums = false;    // the sums pass through the counting sort; else update, launch_update's plan
+    UpdatePlan update{};
+    bool kd_host = false, kd_device = false;   // QVQ_KDTREE=host: no tree image; =device: the device build
+    bool tree_shape = false;     // a shape the device build takes and is worth a launch for
+    bool mfma() const { return search == QVQ_PLAN_SEARCH_SMALL || search == QVQ_PLAN_SEARCH_MF32; }
+};
 // MFMA search for D != 12 from K = 128 code vectors up: below it the VALU search wins (C4,
 // D = 48: 82 vs 182 us at K = 32, 154 vs 187 at K = 64; from K = 64 or 32 the C4 levels ran
 // slower, profiles/r05ak).
 constexpr uint32_t WIDE_MIN_K = 128;
-bool use_wide(const qvq_ctx *ctx, uint32_t K) {
-    return ctx->D != MF_D && wide_can_search(ctx->Dp) && K >= WIDE_MIN_K && !env_is("QVQ_SEARCH", "valu");
-}
-bool use_fused(const qvq_ctx *ctx, uint32_t K) { return use_mfma(ctx, K) && K <= mf_fuse_max_k(); }
-// the MFMA recheck from K = 512 (below it the fp32 pass over K code vectors is cheaper than
-// staging the MFMA tables, profiles/r02f)
-bool use_recheck_mf32(const qvq_ctx *ctx, uint32_t K) {
-    return K >= 512 && use_mfma(ctx, K) && recheck_mf32_fits(K);
-}
 // Pruned MFMA search (k_mf32.hip PRUNE: tiles outside a chunk's provable window skipped) for
 // D = 12 from K = 256 (from K = 128 it measured slower, profiles/r05ao) up to prune_order's
 // capacity.  Its order is computed by the previous level's finalize.  Other D
@@ -421,13 +417,48 @@ bool use_recheck_mf32(const qvq_ctx *ctx, uint32_t K) {
 // is searched unpruned: its per-wave windows measured no faster.
 // The D = 12 kernel keeps one tile envelope per lane: at most 64 tiles (K <= 2048).
 constexpr uint32_t PRUNE_MIN_K = 256, WPRUNE_MIN_K = 1024;
-bool use_prune(const qvq_ctx *ctx, uint32_t K) {
-    if (K > PRUNE_MAXK_HOST) return false;
-    if (ctx->D == MF_D)
-        return K >= PRUNE_MIN_K && K <= 2048 && use_mfma(ctx, K) && mf32_prune_fits(K, use_fused(ctx, K));
-    if (wide_codebook_resident(ctx->Dp, K)) return false;
-    return K >= WPRUNE_MIN_K && use_wide(ctx, K) && wide_prune_fits(ctx->Dp, K);
+// The path knobs a test exercises are read here, at every call (tests flip them between calls):
+// QVQ_SEARCH=valu (the VALU search at every K), QVQ_KDTREE=host (ties answered on the host) and
+// QVQ_KDTREE=device (the level's tree built on the device, k_kdbuild.hip: opt-in, bit-identical
+// to the host build but slower than it -- K = 4096 3.7 ms vs 1.8 ms, K = 2048 2.2 vs 0.7: a node
+// costs ~10-20 us of dependent device round trips and barriers, and C4's trees have ~300 big
+// nodes on one serial path -- so the host build, overlapping the search, stays the default,
+// DESIGN.md 8).  The other knobs: QVQ_KAHAN=0 / QVQ_SPECULATE=0 (index rule and schedule,
+// DESIGN.md 3.8-3.9); QVQ_KAHAN_FAIL_LEVEL / _RANK (forced check failures).
+LevelPlan plan_level(uint32_t D, uint32_t Dp, uint64_t N, uint32_t K) {
+    LevelPlan p;
+    const bool valu = env_is("QVQ_SEARCH", "valu");
+    p.kd_host = env_is("QVQ_KDTREE", "host");
+    p.kd_device = env_is("QVQ_KDTREE", "device");
+    const RecheckPath rp = recheck_path(Dp, K);
+    p.recheck = rp == RecheckPath::Staged    ? QVQ_PLAN_RECHECK_STAGED
+                : rp == RecheckPath::Chunked ? QVQ_PLAN_RECHECK_CHUNKED
+                                             : QVQ_PLAN_RECHECK_GLOBAL;
+    if (D == MF_D && mf_can_search(K) && !valu) {
+        p.search = mf_small_search(K) ? QVQ_PLAN_SEARCH_SMALL : QVQ_PLAN_SEARCH_MF32;
+        p.fusable = K <= mf_fuse_max_k();
+        p.c32_staged = p.search == QVQ_PLAN_SEARCH_MF32 && mf32_c32_staged(K, false, false);
+        p.prunable = K >= PRUNE_MIN_K && K <= 2048 && mf32_prune_fits(K, p.fusable);
+        // the MFMA recheck from K = 512 (below it the fp32 pass over K code vectors is cheaper
+        // than staging the MFMA tables, profiles/r02f)
+        if (K >= 512 && recheck_mf32_fits(K)) p.recheck = QVQ_PLAN_RECHECK_MF32;
+    } else if (D != MF_D && wide_can_search(Dp) && K >= WIDE_MIN_K && !valu) {
+        p.search = QVQ_PLAN_SEARCH_WIDE;
+        p.cb_resident = wide_codebook_resident(Dp, K);
+        p.prunable = !p.cb_resident && K >= WPRUNE_MIN_K && K <= PRUNE_MAXK_HOST && wide_prune_fits(Dp, K);
+    } else {
+        const uint32_t KT = assign_valu_tile(Dp, K);
+        p.valu_tiles = (K + KT - 1) / KT;
+    }
+    // sums of a final assignment through the counting sort (k_misc.hip) from K * D = 1536 (C4 from
+    // K = 32: 5.52 -> 5.23 ms against 16384)
+    p.sorted_sums = (uint64_t)K * D >= 1536 && sorted_sums_fits(K) && N <= 0xFFFFFFFFull;
+    p.update = update_plan(K, D);
+    // levels whose tree the device build takes (its LDS arrays) and is worth a launch for
+    p.tree_shape = kd_build_fits(K, D) && (uint64_t)K * D >= KDB_MIN_KD;
+    return p;
 }
+LevelPlan plan_level(const qvq_ctx *ctx, uint32_t K) { return plan_level(ctx->D, ctx->Dp, ctx->N, K); }
 
 void free_kahan_work(KahanWork &w) {
     for (uint32_t **p : {&w.hist, &w.tot, &w.koff, &w.segoff, &w.blkoff}) dfree(*p);
@@ -511,7 +542,6 @@ void free_levels(qvq_ctx *ctx) {
     ctx->Kcap = 0;
 }
 
-bool device_tree_on();
 // Flattened tree: root box lo[D], hi[D] | nodes[<= 2K] | vind[K].
 uint64_t tree_bytes(uint32_t K, uint32_t D) {
     return 16ull * D + (2ull * K + 1) * sizeof(KdNodeDev) + 4ull * K;
@@ -655,7 +685,7 @@ qvq_status ensure_levels(qvq_ctx *ctx, uint32_t Kmax) {
     HIPCHK(hipMalloc(&ctx->d_tree, ctx->tree_cap));
     {   // the device tree build's scratch (levels of up to KDB_MAXK code vectors)
         const uint32_t Kb = std::min<uint32_t>(Kmax, KDB_MAXK);
-        if (device_tree_on() && kd_build_fits(Kb, ctx->D) && (uint64_t)Kmax * ctx->D >= KDB_MIN_KD) {
+        if (plan_level(ctx, Kb).kd_device && kd_build_fits(Kb, ctx->D) && (uint64_t)Kmax * ctx->D >= KDB_MIN_KD) {
             HIPCHK(hipMalloc(&ctx->d_kdb_vind, (uint64_t)Kb * 4));
             HIPCHK(hipMalloc(&ctx->d_kdb_nodes, 2ull * Kb * sizeof(KdbNode)));
             HIPCHK(hipMalloc(&ctx->d_kdb_nbox, 2ull * Kb * 2 * ctx->D * 8));
@@ -699,24 +729,83 @@ FinArgs finalize_args(const qvq_ctx *ctx, uint32_t K, bool last_block) {
     return f;
 }
 
-// Search tables for the K code vectors in d_C64_split.
-qvq_status run_prep(qvq_ctx *ctx, uint32_t K) {
-    FinArgs f = finalize_args(ctx, K, false);
-    f.C_src = ctx->d_C64_split;
-    f.children = 1;
-    f.Kpad = pad32(K);
-    HIPCHK(launch_finalize(ctx->stream, f));
-    return QVQ_OK;
-}
+// Copy 1 of d_sums sits one capacity-sized copy in, where no level's copy 0 reaches.
+uint64_t sums_cap_stride(const qvq_ctx *ctx) { return 2 * (uint64_t)ctx->Kcap * ctx->D + ctx->Kcap; }
 
-// Copy 1 of d_sums may hold a kd_reduce's moves that no finalize took (a call that stopped
-// between the two): the sums cleared before they are used again.
+// What run_level left of the level's sums, for reduce_level: a value that ends with the level
+// (a level that is abandoned leaves nothing behind but, possibly, sums1_dirty).
+struct LevelSums {
+    // slabs of d_part / d_part_cnt to reduce (0: none, the sums are in d_sums), the last nsub subtracted
+    uint32_t nslabs = 0, nsub = 0;
+    // fused sums: slab G and its counts (the rows the recheck and the ties move at their new
+    // index; slab G + 1, behind it, has them at the provisional one)
+    uint64_t *xslab = nullptr;
+    uint32_t *xcnt = nullptr;
+    uint32_t copies = 1;    // 2: the ties' moves go to copy 1 of d_sums, which the finalize adds
+    bool kd_pend = false;   // the kd-tree ties were left to the reduce (kd_reduce_kernel, over kd)
+    KdView kd{};
+    PubArgs pub;            // a tie-count publication left to the reduce
+    bool upd = false;       // a separate sums pass ran between ev[slot][2] and [3]
+};
+// What reduce_level left in d_sums, for the finalize: the copies to add, and the gate of the
+// copies past the first (the level's tie count), or null.
+struct ReducedSums {
+    uint32_t copies = 1;
+    const unsigned *gate = nullptr;
+};
+
+// A writer of moves into copy 1 of d_sums (or of qvq_refine's changed total behind a level's
+// sums, which lies in its range) says so first; the finalize that takes them lowers the flag.
+void mark_sums1(qvq_ctx *ctx) { ctx->sums1_dirty = true; }
+// Copy 1 of d_sums may hold moves that no finalize took (a call that stopped between the two):
+// the sums cleared before they are used again.
 qvq_status clear_dirty_sums(qvq_ctx *ctx) {
     if (ctx->sums1_dirty) {
         HIPCHK(hipMemsetAsync(ctx->d_sums, 0, ctx->sums_bytes, ctx->stream));
         ctx->sums1_dirty = false;
     }
     return QVQ_OK;
+}
+
+// The sums side of a finalize: a level's reduced sums r (clear1: the finalize also clears copy 1
+// after adding it, where no fused search of a later level does), or, r null, the mean sums at
+// K = 1, which it leaves cleared for the next quantize.
+void sums_args(const qvq_ctx *ctx, FinArgs &f, const ReducedSums *r, bool clear1) {
+    f.sums = r ? ctx->d_sums : ctx->d_mean;
+    f.ncopy = r ? r->copies : MEAN_COPIES;
+    f.cstride = r && r->copies > 1 ? sums_cap_stride(ctx) : 0;
+    f.gate = r ? r->gate : nullptr;
+    f.zero_sums = r ? clear1 && r->copies > 1 : true;
+    f.zero_skip = r ? 1 : 0;
+}
+// The tables side: the search tables of the children * K code vectors the finalize writes to
+// C_next (2: the split, 1: the same K), their host copy, and the tile order where the search
+// that follows is pruned; the context then holds that K's order or none.
+void tables_args(qvq_ctx *ctx, FinArgs &f, uint32_t children, double *C_next, double *host_cb, bool prune) {
+    f.children = children;
+    f.Kpad = pad32(children * f.K);
+    f.C_next = C_next;
+    f.host_cb = host_cb;
+    if (prune) {
+        f.perm = ctx->d_perm;
+        f.tint = ctx->d_tint;
+    }
+    ctx->perm_k = prune ? children * f.K : 0;
+}
+// Every finalize is launched here: one that adds copy 1 of the level's sums, or takes
+// qvq_refine's changed total, has consumed what mark_sums1 announced.
+qvq_status run_finalize(qvq_ctx *ctx, const FinArgs &f) {
+    HIPCHK(launch_finalize(ctx->stream, f));
+    if ((f.sums == ctx->d_sums && f.ncopy > 1) || f.changed64) ctx->sums1_dirty = false;
+    return QVQ_OK;
+}
+
+// Search tables for the K code vectors in d_C64_split (no tile order).
+qvq_status run_prep(qvq_ctx *ctx, uint32_t K) {
+    FinArgs f = finalize_args(ctx, K, false);
+    f.C_src = ctx->d_C64_split;
+    tables_args(ctx, f, 1, nullptr, nullptr, false);
+    return run_finalize(ctx, f);
 }
 
 // fp32 error-bound coefficients for the VALU search flag ("near-tie flags").
@@ -768,33 +857,29 @@ qvq_status all_reduce_sums(qvq_ctx *ctx, uint32_t K, uint64_t *sums = nullptr, u
     return all_reduce(ctx, sums, copies * (2 * (uint64_t)K * ctx->D + K), false);
 }
 
-// Sums of a final assignment through the counting sort (k_misc.hip) from K * D = 1536 (C4 from
-// K = 32: 5.52 -> 5.23 ms against 16384).
-bool use_sorted_sums(const qvq_ctx *ctx, uint32_t K) {
-    return (uint64_t)K * ctx->D >= 1536 && sorted_sums_fits(K) && ctx->N <= 0xFFFFFFFFull;
-}
-
-// Centroid sums under assignment d_A: slabs in d_part (ctx->nslabs of them, for the reduce),
-// or with the sort straight into d_sums (ctx->nslabs = 0).
-qvq_status run_update_slabs(qvq_ctx *ctx, const uint32_t *d_A, uint32_t K) {
-    if (use_sorted_sums(ctx, K)) {
+// Centroid sums under assignment d_A: nslabs slabs in d_part (for the reduce), or with the sort
+// straight into d_sums (nslabs = 0).
+qvq_status run_update_slabs(qvq_ctx *ctx, const LevelPlan &p, const uint32_t *d_A, uint32_t K, uint32_t &nslabs) {
+    if (p.sorted_sums) {
         if (!ctx->d_sortbuf) HIPCHK(hipMalloc(&ctx->d_sortbuf, ctx->N * 2 * sizeof(uint32_t)));
         HIPCHK(launch_sorted_sums(ctx->stream, ctx->Dp, ctx->G, ctx->d_codes, ctx->N, d_A, K, ctx->D, ctx->d_plut,
                                   ctx->d_part_cnt, reinterpret_cast<uint32_t *>(ctx->d_part), ctx->d_sortbuf,
                                   ctx->d_sortbuf + ctx->N, ctx->d_sums));
-        ctx->nslabs = 0;
+        nslabs = 0;
         return QVQ_OK;
     }
     HIPCHK(launch_update(ctx->stream, ctx->Dp, ctx->G, ctx->d_codes, ctx->N, d_A, K, ctx->D, ctx->d_plut, ctx->d_part,
                          ctx->d_part_cnt));
-    ctx->nslabs = ctx->G;
+    nslabs = ctx->G;
     return QVQ_OK;
 }
 
-qvq_status run_update(qvq_ctx *ctx, const uint32_t *d_A, uint32_t K) {
-    qvq_status st = run_update_slabs(ctx, d_A, K);
+// ... and reduced into d_sums.
+qvq_status run_update(qvq_ctx *ctx, const LevelPlan &p, const uint32_t *d_A, uint32_t K) {
+    uint32_t nslabs = 0;
+    qvq_status st = run_update_slabs(ctx, p, d_A, K, nslabs);
     if (st != QVQ_OK) return st;
-    if (ctx->nslabs) HIPCHK(launch_reduce(ctx->stream, ctx->d_part, ctx->d_part_cnt, ctx->nslabs, 0, K, ctx->D, ctx->d_sums));
+    if (nslabs) HIPCHK(launch_reduce(ctx->stream, ctx->d_part, ctx->d_part_cnt, nslabs, 0, K, ctx->D, ctx->d_sums));
     return QVQ_OK;
 }
 
@@ -957,8 +1042,6 @@ qvq_status kahan_chained(qvq_ctx *ctx, const uint32_t *A, uint32_t K_in, const u
     return QVQ_OK;
 }
 
-bool join_tree_job(qvq_ctx *ctx, bool cancel);
-
 // Build the reference kd-tree over the host copy hC of the K code vectors being searched
 // into tree image buffer buf (pinned host memory, DMA-copied to d_tree for kd_resolve_kernel).  An empty
 // view means host resolution (tree too deep/large for the kernel's LDS, or QVQ_KDTREE=host).
@@ -1038,10 +1121,10 @@ void tree_view(qvq_ctx *ctx, int buf, KdView &v) {
     v.vind = reinterpret_cast<const uint32_t *>(v.nodes + v.n_nodes);
 }
 
-void build_tree(qvq_ctx *ctx, const double *hC, uint32_t K, int buf, KdView &kd) {
+void build_tree(qvq_ctx *ctx, const LevelPlan &p, const double *hC, uint32_t K, int buf, KdView &kd) {
     kd = KdView{};
     ctx->tree_kd = KdView{};
-    if (env_is("QVQ_KDTREE", "host")) return;
+    if (p.kd_host) return;
     build_tree_host(ctx, hC, K, buf, kd);
     tree_view(ctx, buf, kd);
     ctx->tree_kd = kd;
@@ -1050,25 +1133,10 @@ void build_tree(qvq_ctx *ctx, const double *hC, uint32_t K, int buf, KdView &kd)
 CommState probe_comm(qvq_ctx *ctx, std::string &msg);
 qvq_status wait_failed(qvq_ctx *ctx, qvq_status st);
 
-// The device build of a level's tree (k_kdbuild.hip), 48-D levels from K = 512 up to KDB_MAXK:
-// opt-in (QVQ_KDTREE=device).  Bit-identical to the host build (tests/test_gpu_kdbuild.py), but
-// slower than it on the GPU box's host: K = 4096 3.7 ms vs 1.8 ms, K = 2048 2.2 vs 0.7 (a node
-// costs ~10-20 us of dependent device round trips and barriers, and C4's trees have ~300 big
-// nodes on one serial path), so the host build, overlapping the search, stays the default
-// (DESIGN.md 8).
-bool device_tree_on() {
-    static const bool on = env_is("QVQ_KDTREE", "device");
-    return on;
-}
-// the shapes the device build takes (its LDS arrays) and is worth a launch for
-bool device_tree_shape(uint32_t K, uint32_t D) { return kd_build_fits(K, D) && (uint64_t)K * D >= KDB_MIN_KD; }
-bool use_device_tree(const qvq_ctx *ctx, uint32_t K) {
-    return device_tree_on() && ctx->kdb_cap >= K && !ctx->exact && device_tree_shape(K, ctx->D);
-}
-
-// Enqueue the device build of the tree over the K code vectors in d_C64_split on kstream, after
-// the work already on the context's stream (the finalize that wrote them); the search then runs
-// beside it.
+// The device build of a level's tree (k_kdbuild.hip; plan_level: QVQ_KDTREE=device, 48-D levels
+// from K = 512 up to KDB_MAXK; bit-identical to the host build, tests/test_gpu_kdbuild.py),
+// enqueued over the K code vectors in d_C64_split on kstream, after the work already on the
+// context's stream (the finalize that wrote them); the search then runs beside it.
 qvq_status start_device_tree(qvq_ctx *ctx, uint32_t K) {
     HIPCHK(hipEventRecord(ctx->ev_kcb, ctx->stream));
     HIPCHK(hipStreamWaitEvent(ctx->kstream, ctx->ev_kcb, 0));
@@ -1149,9 +1217,25 @@ void post_job(qvq_ctx *ctx, std::function<void()> job, qvq_ctx::Worker *wk = nul
     w.cv.notify_one();
 }
 
-void start_tree_job(qvq_ctx *ctx, const double *hC, uint32_t K, int buf, uint64_t wait_seq) {
+bool join_tree_job(qvq_ctx *ctx, bool cancel) {
+    if (!ctx->tree_job) return false;
+    if (cancel) ctx->tree_cancel.store(true);
+    while (ctx->worker.pending.load(std::memory_order_acquire)) std::this_thread::yield();
+    ctx->tree_job = false;
+    if (!ctx->job_ok) {
+        ctx->tree.reset();
+        ctx->tree_kd = KdView{};
+        return false;
+    }
+    KdView v = ctx->job_kd;
+    tree_view(ctx, ctx->job_buf, v);
+    ctx->tree_kd = v;
+    return true;
+}
+
+void start_tree_job(qvq_ctx *ctx, const LevelPlan &p, const double *hC, uint32_t K, int buf, uint64_t wait_seq) {
     join_tree_job(ctx, true);
-    if (env_is("QVQ_KDTREE", "host")) return;
+    if (p.kd_host) return;
     ctx->tree_cancel.store(false);
     ctx->tree_job = true;
     ctx->job_ok = false;
@@ -1176,22 +1260,6 @@ void start_tree_job(qvq_ctx *ctx, const double *hC, uint32_t K, int buf, uint64_
         ctx->tm.wait_ms[slot] = std::chrono::duration<double, std::milli>(t1 - t0).count();
         ctx->tm.tree_ms[slot] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
     });
-}
-
-bool join_tree_job(qvq_ctx *ctx, bool cancel) {
-    if (!ctx->tree_job) return false;
-    if (cancel) ctx->tree_cancel.store(true);
-    while (ctx->worker.pending.load(std::memory_order_acquire)) std::this_thread::yield();
-    ctx->tree_job = false;
-    if (!ctx->job_ok) {
-        ctx->tree.reset();
-        ctx->tree_kd = KdView{};
-        return false;
-    }
-    KdView v = ctx->job_kd;
-    tree_view(ctx, ctx->job_buf, v);
-    ctx->tree_kd = v;
-    return true;
 }
 
 // Copy between a caller's host buffer and device memory at DMA speed: the host range is pinned
@@ -1284,10 +1352,10 @@ qvq_status wait_stream(qvq_ctx *ctx) {
 qvq_status wait_codebook(qvq_ctx *ctx, uint64_t seq) { return wait_flag(ctx, ctx->h_ready, seq); }
 
 // Tie rows listed by the recheck when no device tree was available: answer them with the
-// host tree over hC and write A; with accumulate their terms move from the search's
-// provisional index to the answer (launch_fix_rows).  Synchronous.
-qvq_status resolve_host_ties(qvq_ctx *ctx, const double *hC, uint32_t K, uint32_t nt, bool accumulate,
-                             uint64_t *xsums = nullptr) {
+// host tree over hC and write A; with xslab / xcnt (LevelSums) their terms move from the search's
+// provisional index to the answer, with xsums within finished sums (launch_fix_rows).  Synchronous.
+qvq_status resolve_host_ties(qvq_ctx *ctx, const double *hC, uint32_t K, uint32_t nt, uint64_t *xslab, uint32_t *xcnt,
+                             uint64_t *xsums) {
     const uint32_t D = ctx->D, Dp = ctx->Dp;
     const uint64_t need = (uint64_t)nt * (8 + Dp);
     if (ctx->scatter_bytes < need) {
@@ -1311,69 +1379,68 @@ qvq_status resolve_host_ties(qvq_ctx *ctx, const double *hC, uint32_t K, uint32_
     }
     HIPCHK(hipMemcpyAsync(d_rows, rows.data(), nt * 4, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(d_vals, vals.data(), nt * 4, hipMemcpyHostToDevice, ctx->stream));
-    uint64_t *xslab = accumulate ? ctx->d_part + (uint64_t)ctx->G * K * D : nullptr;
-    uint32_t *xcnt = accumulate ? ctx->d_part_cnt + (uint64_t)ctx->G * K : nullptr;
     HIPCHK(launch_fix_rows(ctx->stream, ctx->d_codes, Dp, D, ctx->d_A, d_rows, d_vals, nt, K, xslab, xcnt,
                            ctx->d_plut, xsums));
     HIPCHK(hipStreamSynchronize(ctx->stream));   // the host vectors must outlive the copies
     return QVQ_OK;
 }
 
-// One level's assignment of every row against the split codebook (d_C64_split, host copy
-// hC, search tables in d_C32/d_rows), K code vectors.  wait_seq != 0: hC is published by a
-// finalize still in flight.  With sums_out the exact centroid sums of the final assignment
-// are left in the first ctx->nslabs slabs of d_part / d_part_cnt, the last ctx->nsub of them
-// to be subtracted (fused: the search's G slabs with every row at its provisional index, slab
-// G with the rows the recheck and the kd-tree move at their new index, slab G + 1 with the
-// same rows at the provisional one; otherwise the update's G).
-// Copy 1 of d_sums sits one capacity-sized copy in, where no level's copy 0 reaches.
-uint64_t sums_cap_stride(const qvq_ctx *ctx) { return 2 * (uint64_t)ctx->Kcap * ctx->D + ctx->Kcap; }
-
 // One rank, fused sums: the kd-tree ties go with the reduce (kd_reduce_kernel: one launch fewer
 // per level).
-bool kd_merge(const qvq_ctx *ctx) {
-    return !ctx->comm && !ctx->host_ar;
-}
+bool kd_merge(const qvq_ctx *ctx) { return !ctx->comm && !ctx->host_ar; }
 
-qvq_status run_level(qvq_ctx *ctx, uint32_t K, int slot, bool sums_out, const double *hC, uint64_t wait_seq,
-                     bool defer_ties = false) {
-    const bool fused = sums_out && use_fused(ctx, K);
-    ctx->kd_pend = false;
-    ctx->sums_copies = 1;
+// One level's assignment of every row against the split codebook (d_C64_split, host copy
+// hC, search tables in d_C32/d_rows), K code vectors.  wait_seq != 0: hC is published by a
+// finalize still in flight.  In: the level's plan p (plan_level of this K) and the call's own
+// facts -- sums_out, defer_ties (the ties wait for the caller's reference-bit step), whether a
+// communicator is joined (kd_merge) and whether the context holds this K's tile order (perm_k),
+// which meet the plan in the first lines below.  Out: with sums_out, ls describes where the
+// exact centroid sums of the final assignment are, for reduce_level (fused: the search's G slabs
+// with every row at its provisional index and the two correction slabs; otherwise the sums
+// pass's G slabs, or the sums themselves, reduced already).
+qvq_status run_level(qvq_ctx *ctx, const LevelPlan &p, uint32_t K, int slot, bool sums_out, const double *hC,
+                     uint64_t wait_seq, bool defer_ties, LevelSums &ls) {
+    ls = LevelSums();
+    const bool fused = sums_out && p.fusable;
     // one rank, sums from a separate pass: that pass (and its reduce) runs before the tree is
     // built -- it overlaps the host build instead of waiting behind it -- and the ties' moves are
     // then applied to the finished sums (move_row_sums)
     const bool early_upd = sums_out && !fused && (kd_merge(ctx) || defer_ties);
+    // the order the finalize before this level left: valid for the search and the recheck
+    const bool pruned = ctx->perm_k == K;
+    // the level's kd-tree on the device, beside the search (every CU holds a search workgroup
+    // and room for the build's)
+    const bool devtree = !defer_ties && p.kd_device && p.tree_shape && ctx->kdb_cap >= K && !ctx->exact;
     uint64_t *sums1 = early_upd ? ctx->d_sums : nullptr;
-    uint64_t *xslab = fused ? ctx->d_part + (uint64_t)ctx->G * K * ctx->D : nullptr;
-    uint32_t *xcnt = fused ? ctx->d_part_cnt + (uint64_t)ctx->G * K : nullptr;
-    ctx->nslabs = fused ? ctx->G + 2 : ctx->G;
-    ctx->nsub = fused ? 1 : 0;
+    if (fused) {
+        ls.xslab = ctx->d_part + (uint64_t)ctx->G * K * ctx->D;
+        ls.xcnt = ctx->d_part_cnt + (uint64_t)ctx->G * K;
+        ls.nslabs = ctx->G + 2;
+        ls.nsub = 1;
+    } else if (sums_out) {
+        ls.nslabs = ctx->G;
+    }
+    const uint32_t *perm = pruned ? ctx->d_perm : nullptr;
+    const int32_t *tint = pruned ? ctx->d_tint : nullptr;
     unsigned *cnt = ctx->d_counters + 2 * slot;
     // HIP events around the search (each record costs a few us of GPU idle): every level,
     // one level, or none (qvq_set_timing)
     const bool timing = ctx->timing_level == -1 || ctx->timing_level == slot;
-    // the level's kd-tree on the device, beside the search (every CU holds a search workgroup
-    // and room for the build's)
-    const bool devtree = !defer_ties && use_device_tree(ctx, K);
     qvq_status st;
     if (devtree && (st = start_device_tree(ctx, K)) != QVQ_OK) return st;
     if (timing) HIPCHK(hipEventRecord(ctx->ev[slot][0], ctx->stream));
-    if (use_mfma(ctx, K)) {
-        const bool prune = ctx->perm_k == K;   // the order qvq_lbg's finalize left for this level
+    if (p.mfma()) {
         // one rank, fused sums: the search clears copy 1 of the final sums (the kd ties' moves,
         // added by the previous level's finalize), covering every smaller level's layout
         const bool clear1 = fused && kd_merge(ctx);
         HIPCHK(launch_assign_mfma(ctx->stream, ctx->num_cu, fused, ctx->d_codes, ctx->N, ctx->d_rows, ctx->d_E32, K,
                                   ctx->d_C32, ctx->d_plut, ctx->mf_th, ctx->d_A, ctx->d_flags, &cnt[0],
-                                  ctx->d_part, ctx->d_part_cnt, prune ? ctx->d_perm : nullptr,
-                                  prune ? ctx->d_tint : nullptr, clear1 ? ctx->d_sums + sums_cap_stride(ctx) : nullptr,
+                                  ctx->d_part, ctx->d_part_cnt, perm, tint,
+                                  clear1 ? ctx->d_sums + sums_cap_stride(ctx) : nullptr,
                                   clear1 ? (uint32_t)(2 * (uint64_t)K * ctx->D + K) : 0u));
-    } else if (use_wide(ctx, K)) {
-        const bool prune = ctx->perm_k == K;
+    } else if (p.search == QVQ_PLAN_SEARCH_WIDE) {
         HIPCHK(launch_assign_wide(ctx->stream, ctx->num_cu, ctx->Dp, ctx->D, ctx->d_codes, ctx->N, ctx->d_rows, K,
-                                  ctx->d_C32, ctx->mf_th, ctx->d_A, ctx->d_flags, &cnt[0],
-                                  prune ? ctx->d_perm : nullptr, prune ? ctx->d_tint : nullptr,
+                                  ctx->d_C32, ctx->mf_th, ctx->d_A, ctx->d_flags, &cnt[0], perm, tint,
                                   std::max<uint32_t>(1, (ctx->col_blocks + 32) / 64), ctx->d_counters + SCHED_COUNTERS));
     } else {
         float alpha, beta, gamma;
@@ -1382,27 +1449,25 @@ qvq_status run_level(qvq_ctx *ctx, uint32_t K, int slot, bool sums_out, const do
                                   ctx->d_lut32, alpha, beta, gamma, ctx->d_A, ctx->d_flags, &cnt[0]));
     }
     if (timing) HIPCHK(hipEventRecord(ctx->ev[slot][1], ctx->stream));
-    if (use_recheck_mf32(ctx, K)) {
+    if (p.recheck == QVQ_PLAN_RECHECK_MF32) {
         HIPCHK(launch_recheck_mf32(ctx->stream, ctx->num_cu, ctx->d_codes, ctx->d_flags, &cnt[0], ctx->d_rows,
                                    ctx->d_C64_split, K, ctx->d_lut64, ctx->mf_th, 1e-12, tie_band(ctx), ctx->d_A, ctx->d_ties,
-                                   &cnt[1], xslab, xcnt, ctx->d_plut));
+                                   &cnt[1], ls.xslab, ls.xcnt, ctx->d_plut));
     } else {
         float alpha, beta, gamma;
         valu_coeffs(ctx, alpha, beta, gamma);
-        const bool pruned = ctx->perm_k == K;   // the search's order is valid for the recheck too
         HIPCHK(launch_recheck(ctx->stream, ctx->num_cu, ctx->d_codes, ctx->Dp, ctx->D, ctx->d_flags, &cnt[0],
                               ctx->d_C64_split, ctx->d_C32, K, ctx->d_lut64, alpha, beta, gamma, 1e-12, tie_band(ctx), ctx->d_A,
-                              ctx->d_ties, &cnt[1], xslab, xcnt, ctx->d_plut, pruned ? ctx->d_perm : nullptr,
-                              pruned ? ctx->d_tint : nullptr,
+                              ctx->d_ties, &cnt[1], ls.xslab, ls.xcnt, ctx->d_plut, perm, tint,
                               (float)((double)ctx->D / (ctx->terms.sx * ctx->terms.sx))));
     }
     if (defer_ties) {   // the level's tie count to the host, before the rest of the level runs
         ctx->pub_seq++;
-        if (fused) {   // published by the slab reduce that follows (qvq_lbg): no launch of its own
-            ctx->pub.cnt = &cnt[1];
-            ctx->pub.dst = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(ctx->dh_ready) + 16);
-            ctx->pub.flag = ctx->dh_ready + 1;
-            ctx->pub.seq = ctx->pub_seq;
+        if (fused) {   // published by the slab reduce that follows (reduce_level): no launch of its own
+            ls.pub.cnt = &cnt[1];
+            ls.pub.dst = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(ctx->dh_ready) + 16);
+            ls.pub.flag = ctx->dh_ready + 1;
+            ls.pub.seq = ctx->pub_seq;
         } else {
             HIPCHK(launch_copy_out(ctx->stream, &cnt[1], reinterpret_cast<uint8_t *>(ctx->dh_ready) + 16, 4, nullptr,
                                    nullptr, 0, nullptr, nullptr, 0, ctx->dh_ready + 1, ctx->pub_seq,
@@ -1411,13 +1476,12 @@ qvq_status run_level(qvq_ctx *ctx, uint32_t K, int slot, bool sums_out, const do
     }
     if (early_upd) {
         HIPCHK(hipEventRecord(ctx->ev[slot][2], ctx->stream));
-        if ((st = run_update(ctx, ctx->d_A, K)) != QVQ_OK) return st;
-        ctx->nslabs = 0;   // reduced already
+        if ((st = run_update(ctx, p, ctx->d_A, K)) != QVQ_OK) return st;
+        ls.nslabs = 0;   // reduced already
         HIPCHK(hipEventRecord(ctx->ev[slot][3], ctx->stream));
     }
     if (defer_ties) {   // qvq_lbg answers the ties after the finalize, if there are any (tree on the worker)
-        start_tree_job(ctx, hC, K, slot & 1, wait_seq);
-        ctx->upd[slot] = false;
+        start_tree_job(ctx, p, hC, K, slot & 1, wait_seq);
         return QVQ_OK;
     }
     // the tree build overlaps the search just enqueued
@@ -1438,55 +1502,51 @@ qvq_status run_level(qvq_ctx *ctx, uint32_t K, int slot, bool sums_out, const do
         if ((st = finish_device_tree(ctx, K, kd, dev_ok)) != QVQ_OK) return st;
         ctx->tree_kd = kd;
     }
-    if (!dev_ok) build_tree(ctx, hC, K, slot & 1, kd);
+    if (!dev_ok) build_tree(ctx, p, hC, K, slot & 1, kd);
     ctx->htrace.mark("K" + std::to_string(K) + (dev_ok ? " device tree in" : " tree built"));
     ctx->tm.wait_ms[slot] = std::chrono::duration<double, std::milli>(tw1 - tw0).count();
     ctx->tm.tree_ms[slot] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw1).count();
     if (kd.depth > 0 && fused && kd_merge(ctx) && kd_reduce_fits(kd, K)) {
-        ctx->kd_pend = true;   // with the reduce (qvq_lbg)
-        ctx->pend_kd = kd;
-        ctx->sums_copies = 2;
+        ls.kd_pend = true;   // with the reduce (reduce_level)
+        ls.kd = kd;
+        ls.copies = 2;
     } else if (kd.depth > 0) {
         HIPCHK(launch_kd_resolve(ctx->stream, ctx->d_codes, ctx->Dp, ctx->D, ctx->d_ties, &cnt[1], ctx->d_C64_split,
-                                 K, ctx->d_lut64, kd, ctx->d_A, xslab, xcnt, ctx->d_plut, sums1));
+                                 K, ctx->d_lut64, kd, ctx->d_A, ls.xslab, ls.xcnt, ctx->d_plut, sums1));
     } else {   // ties answered on the host
         unsigned nt = 0;
         HIPCHK(hipMemcpyAsync(&nt, &cnt[1], sizeof(nt), hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
-        if (nt && (st = resolve_host_ties(ctx, hC, K, nt, fused, sums1)) != QVQ_OK) return st;
+        if (nt && (st = resolve_host_ties(ctx, hC, K, nt, ls.xslab, ls.xcnt, sums1)) != QVQ_OK) return st;
     }
-    ctx->upd[slot] = sums_out && !fused;
-    if (ctx->upd[slot] && !early_upd) {
+    ls.upd = sums_out && !fused;
+    if (ls.upd && !early_upd) {
         HIPCHK(hipEventRecord(ctx->ev[slot][2], ctx->stream));
-        if ((st = run_update_slabs(ctx, ctx->d_A, K)) != QVQ_OK) return st;
+        if ((st = run_update_slabs(ctx, p, ctx->d_A, K, ls.nslabs)) != QVQ_OK) return st;
         HIPCHK(hipEventRecord(ctx->ev[slot][3], ctx->stream));
     }
     return QVQ_OK;
 }
 
-// The sums of the assignment run_level just made, reduced into d_sums: the slabs together with
-// the level's kd-tree ties (kd_reduce_kernel: their moves go to copy 1, which the finalize adds),
-// or the slabs alone; nslabs 0: the sorted sums are in d_sums already.  pub (may be null): a tie
-// count that run_level left to the slab reduce to publish.
-qvq_status reduce_level(qvq_ctx *ctx, uint32_t K, int slot, PubArgs *pub) {
+// The sums of the assignment run_level just made (ls), reduced into d_sums: the slabs together
+// with the level's kd-tree ties (kd_reduce_kernel: their moves go to copy 1, which the finalize
+// adds), or the slabs alone; no slabs: the sums are in d_sums already.  A tie count that run_level
+// left to be published goes out with the slab reduce.  rs: what the finalize adds.
+qvq_status reduce_level(qvq_ctx *ctx, uint32_t K, int slot, const LevelSums &ls, ReducedSums &rs) {
     const unsigned *tcnt = ctx->d_counters + 2 * slot + 1;   // the level's ties
-    const bool reduced = !ctx->kd_pend && ctx->nslabs != 0;
-    if (ctx->kd_pend) {
-        ctx->sums1_dirty = true;
+    rs.copies = ls.copies;
+    rs.gate = ls.copies > 1 ? tcnt : nullptr;
+    if (ls.kd_pend) {
+        mark_sums1(ctx);
         HIPCHK(launch_kd_reduce(ctx->stream, ctx->d_codes, ctx->Dp, ctx->D, ctx->d_ties, tcnt, ctx->d_C64_split, K,
-                                ctx->d_lut64, ctx->pend_kd, ctx->d_A, ctx->d_plut, ctx->d_part, ctx->d_part_cnt,
-                                ctx->nslabs, ctx->nsub, ctx->d_sums, ctx->d_sums + sums_cap_stride(ctx)));
-        ctx->kd_pend = false;
-    } else if (ctx->nslabs) {
-        HIPCHK(launch_reduce(ctx->stream, ctx->d_part, ctx->d_part_cnt, ctx->nslabs, ctx->nsub, K, ctx->D, ctx->d_sums,
-                             pub ? *pub : PubArgs()));
+                                ctx->d_lut64, ls.kd, ctx->d_A, ctx->d_plut, ctx->d_part, ctx->d_part_cnt,
+                                ls.nslabs, ls.nsub, ctx->d_sums, ctx->d_sums + sums_cap_stride(ctx)));
+    } else if (ls.nslabs) {
+        HIPCHK(launch_reduce(ctx->stream, ctx->d_part, ctx->d_part_cnt, ls.nslabs, ls.nsub, K, ctx->D, ctx->d_sums, ls.pub));
     }
-    if (pub && pub->flag) {
-        if (!reduced)   // the slab reduce did not run: a launch of its own
-            HIPCHK(launch_copy_out(ctx->stream, pub->cnt, pub->dst, 4, nullptr, nullptr, 0, nullptr, nullptr, 0, pub->flag,
-                                   pub->seq, ctx->d_counters + COPY_DONE_COUNTER));
-        *pub = PubArgs();
-    }
+    if (ls.pub.flag && (ls.kd_pend || !ls.nslabs))   // the slab reduce did not run: a launch of its own
+        HIPCHK(launch_copy_out(ctx->stream, ls.pub.cnt, ls.pub.dst, 4, nullptr, nullptr, 0, nullptr, nullptr, 0,
+                               ls.pub.flag, ls.pub.seq, ctx->d_counters + COPY_DONE_COUNTER));
     return QVQ_OK;
 }
 
@@ -2081,16 +2141,52 @@ qvq_status ensure_speculation(qvq_ctx *ctx, uint32_t Kmax) {
     return Kmax >= 4 ? ensure_kahan(ctx, Kmax / 2) : QVQ_OK;
 }
 
+// The nt tie rows of a level (in d_ties) answered against the reference's split S_ref (device;
+// copied to h_kc_split): the level's own tree (over the exact-sum split, built during the
+// search) is the reference's tree too when no differing coordinate can move a box, cut or
+// partition (kdtree.cpp); otherwise a tree over the host copy, or the host's answers where there
+// is no device image.  The rows' terms move within the sums at target.
+qvq_status answer_kahan_ties(qvq_ctx *ctx, const LevelPlan &p, uint32_t K, int slot, unsigned nt, const double *S_ref,
+                             uint64_t *target) {
+    const uint32_t D = ctx->D;
+    ctx->h_kc_split.resize((size_t)K * D);
+    HIPCHK(hipMemcpyAsync(ctx->h_kc_split.data(), S_ref, (size_t)K * D * 8, hipMemcpyDeviceToHost, ctx->stream));
+    const qvq_status st = wait_stream(ctx);
+    if (st != QVQ_OK || nt == 0) return st;
+    KdView kd;
+    if (ctx->tree && ctx->tree_kd.depth > 0 && ctx->cb_local.size() == (size_t)K * D &&
+        ctx->tree->unchanged_under(ctx->h_kc_split.data())) {
+        kd = ctx->tree_kd;
+        if (env_is("QVQ_KAHAN_DEBUG", "1")) std::fprintf(stderr, "qvq kahan: K %u the level's tree reused\n", K);
+    } else {
+        build_tree(ctx, p, ctx->h_kc_split.data(), K, slot & 1, kd);
+    }
+    if (kd.depth > 0) {
+        HIPCHK(launch_kd_resolve(ctx->stream, ctx->d_codes, ctx->Dp, D, ctx->d_ties, ctx->d_counters + 2 * slot + 1, S_ref,
+                                 K, ctx->d_lut64, kd, ctx->d_A, nullptr, nullptr, ctx->d_plut, target));
+        return QVQ_OK;
+    }
+    return resolve_host_ties(ctx, ctx->h_kc_split.data(), K, nt, nullptr, nullptr, target);
+}
+
 // The ties of a level run with defer_ties (nt > 0 of them in d_ties): the reference's split
 // codebook -- the previous level's centroids as Kahan sums in row order (k_kahan.hip; for the
 // NORMAL colour space the exact sums are those bits already), split -- its kd-tree, and the
 // ties answered against both (every distance recomputed from the reference's code vectors).
-// The moves go to sums copy 1 (fused: the finalize adds it) or straight into copy 0.
-qvq_status resolve_kahan_ties(qvq_ctx *ctx, uint32_t K, int slot, unsigned nt, bool fused) {
+// The moves go to sums copy 1 (a fusable level: rs then has the finalize add it) or straight
+// into copy 0.
+qvq_status resolve_kahan_ties(qvq_ctx *ctx, const LevelPlan &p, uint32_t K, int slot, unsigned nt, ReducedSums &rs) {
     const uint32_t D = ctx->D, Kc = K / 2;
     const double *S_ref = ctx->d_C64_split;
     qvq_status st;
-    uint64_t *target = fused ? ctx->d_sums + sums_cap_stride(ctx) : ctx->d_sums;
+    uint64_t *target = ctx->d_sums;
+    rs = ReducedSums();
+    if (p.fusable) {
+        mark_sums1(ctx);
+        target += sums_cap_stride(ctx);
+        rs.copies = 2;
+        rs.gate = ctx->d_counters + 2 * slot + 1;
+    }
     if (ctx->cs == QVQ_CS_SCALED) {
         bool done;
         if ((st = certify_kahan_ties(ctx, K, nt, target, done)) != QVQ_OK || done) return st;
@@ -2107,56 +2203,23 @@ qvq_status resolve_kahan_ties(qvq_ctx *ctx, uint32_t K, int slot, unsigned nt, b
                          K, nt, ms[0], ms[1], ms[2]);
         }
     }
-    ctx->h_kc_split.resize((size_t)K * D);
-    HIPCHK(hipMemcpyAsync(ctx->h_kc_split.data(), S_ref, (size_t)K * D * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if ((st = wait_stream(ctx)) != QVQ_OK) return st;
-    KdView kd;
-    // the level's tree (over the exact-sum split, built during the search) is the reference's
-    // tree too when no differing coordinate can move a box, cut or partition (kdtree.cpp)
-    if (ctx->tree && ctx->tree_kd.depth > 0 && ctx->cb_local.size() == (size_t)K * D &&
-        ctx->tree->unchanged_under(ctx->h_kc_split.data())) {
-        kd = ctx->tree_kd;
-        if (env_is("QVQ_KAHAN_DEBUG", "1")) std::fprintf(stderr, "qvq kahan: K %u the level's tree reused\n", K);
-    } else {
-        build_tree(ctx, ctx->h_kc_split.data(), K, slot & 1, kd);
-    }
-    unsigned *cnt = ctx->d_counters + 2 * slot;
-    if (kd.depth > 0) {
-        HIPCHK(launch_kd_resolve(ctx->stream, ctx->d_codes, ctx->Dp, D, ctx->d_ties, &cnt[1], S_ref, K, ctx->d_lut64,
-                                 kd, ctx->d_A, nullptr, nullptr, ctx->d_plut, target));
-        return QVQ_OK;
-    }
-    return resolve_host_ties(ctx, ctx->h_kc_split.data(), K, nt, false, target);
+    return answer_kahan_ties(ctx, p, K, slot, nt, S_ref, target);
 }
 
 // resolve_kahan_ties on several ranks (a level with ties on any rank, every rank calls it): the
 // reference's whole split from the chains over every rank's rows (kahan_chained), its kd-tree,
 // this rank's ties (nt) answered against both, and the ties' moves of every rank summed (sums
-// copy 1, added by the finalize that follows).
-qvq_status resolve_kahan_ties_multi(qvq_ctx *ctx, uint32_t K, int slot, unsigned nt) {
-    const uint32_t D = ctx->D, Kc = K / 2;
+// copy 1, added by the finalize that follows: rs, without a gate).
+qvq_status resolve_kahan_ties_multi(qvq_ctx *ctx, const LevelPlan &p, uint32_t K, int slot, unsigned nt,
+                                    ReducedSums &rs) {
+    const uint32_t Kc = K / 2;
     qvq_status st;
+    mark_sums1(ctx);
     uint64_t *target = ctx->d_sums + sums_cap_stride(ctx);
-    if ((st = kahan_chained(ctx, K == 2 ? nullptr : ctx->d_A_alt, Kc, nullptr, Kc, true)) !=
-        QVQ_OK)
-        return st;
-    ctx->h_kc_split.resize((size_t)K * D);
-    HIPCHK(hipMemcpyAsync(ctx->h_kc_split.data(), ctx->d_kc_split, (size_t)K * D * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if ((st = wait_stream(ctx)) != QVQ_OK) return st;
-    if (nt) {
-        KdView kd;
-        if (ctx->tree && ctx->tree_kd.depth > 0 && ctx->cb_local.size() == (size_t)K * D &&
-            ctx->tree->unchanged_under(ctx->h_kc_split.data()))
-            kd = ctx->tree_kd;
-        else
-            build_tree(ctx, ctx->h_kc_split.data(), K, slot & 1, kd);
-        unsigned *cnt = ctx->d_counters + 2 * slot;
-        if (kd.depth > 0)
-            HIPCHK(launch_kd_resolve(ctx->stream, ctx->d_codes, ctx->Dp, D, ctx->d_ties, &cnt[1], ctx->d_kc_split, K,
-                                     ctx->d_lut64, kd, ctx->d_A, nullptr, nullptr, ctx->d_plut, target));
-        else if ((st = resolve_host_ties(ctx, ctx->h_kc_split.data(), K, nt, false, target)) != QVQ_OK)
-            return st;
-    }
+    rs = ReducedSums();
+    rs.copies = 2;
+    if ((st = kahan_chained(ctx, K == 2 ? nullptr : ctx->d_A_alt, Kc, nullptr, Kc, true)) != QVQ_OK) return st;
+    if ((st = answer_kahan_ties(ctx, p, K, slot, nt, ctx->d_kc_split, target)) != QVQ_OK) return st;
     return all_reduce_sums(ctx, K, target);
 }
 
@@ -2807,6 +2870,7 @@ QVQ_API qvq_status qvq_lbg(qvq_ctx *ctx, uint32_t bits, double eps, double *code
     double dres[3];
     unsigned stats[LEVEL_COUNTERS];
     bool results_copied = false;
+    bool upd[32] = {};   // per level: a separate sums pass was timed (LevelSums::upd)
     auto copy_results = [&]() -> qvq_status {
         uint8_t *h_small = reinterpret_cast<uint8_t *>(ctx->h_ready) + 64;
         const uint64_t cb_bytes = codebook ? (uint64_t)Kmax * ctx->D * 8 : 0;
@@ -2834,42 +2898,28 @@ QVQ_API qvq_status qvq_lbg(qvq_ctx *ctx, uint32_t bits, double eps, double *code
     // finalize (+ split, tables, host codebook and its ready number) / final distortion
     // (K = 1 reads the mean sums and leaves them cleared for the next quantize)
     if ((st = clear_dirty_sums(ctx)) != QVQ_OK) return st;
-    // copies 2: copy 1 holds the ties' moves (added here; the next level's search clears it)
     // the split a finalize writes: with deferred ties the level's own split must survive its
     // (speculative) finalize, so the next one goes to the other buffer and the two swap
     double *split_out = ctx->d_C64_split;
-    // clear1: the finalize also clears sums copy 1 after adding it (no fused search of a later
-    // level clears it: a communicator, or the synchronous Kahan levels' moves)
-    auto finalize = [&](uint32_t K, bool split, uint32_t copies = 1, const unsigned *gate = nullptr,
-                        const TieExport &tx = TieExport(), bool clear1 = false) {
-        if (split || tx.out) ctx->seq++;
-        const bool prune = split && use_prune(ctx, 2 * K);   // the next search's tile order
-        ctx->perm_k = prune ? 2 * K : 0;
+    // The finalize of the K cells whose sums rs describes (K = 1: the mean sums), with the split
+    // and the tables of the next level (its plan: next) or, at the last level (next null), the
+    // distortion term.  clear1: the finalize also clears sums copy 1 after adding it (no fused
+    // search of a later level clears it: a communicator, or the synchronous Kahan levels' moves).
+    auto finalize = [&](uint32_t K, const LevelPlan *next, const ReducedSums &rs = ReducedSums(),
+                        const TieExport &tx = TieExport(), bool clear1 = false) -> qvq_status {
         FinArgs f = finalize_args(ctx, K, true);
-        f.sums = K == 1 ? ctx->d_mean : ctx->d_sums;
-        f.ncopy = K == 1 ? MEAN_COPIES : copies;
-        f.cstride = copies > 1 ? sums_cap_stride(ctx) : 0;
-        f.gate = gate;
-        f.zero_sums = K == 1 || (clear1 && copies > 1);
-        f.zero_skip = K == 1 ? 0 : 1;
-        if (split) {
-            f.children = 2;
-            f.Kpad = pad32(2 * K);
-            f.C_next = split_out;
-            f.host_cb = dev_cb_of(ctx, (uint32_t)__builtin_ctz(K) + 1);
-            if (prune) {
-                f.perm = ctx->d_perm;
-                f.tint = ctx->d_tint;
-            }
-        } else {
-            f.dist_out = d_dist + 2;
-        }
+        sums_args(ctx, f, K == 1 ? nullptr : &rs, clear1);
+        if (next) tables_args(ctx, f, 2, split_out, dev_cb_of(ctx, (uint32_t)__builtin_ctz(K) + 1), next->prunable);
+        else f.dist_out = d_dist + 2;
         f.ties = tx;
-        if (!split && !tx.out) f.ready = nullptr;
+        if (next || tx.out) ctx->seq++;
+        else f.ready = nullptr;
         f.seq = ctx->seq;
-        return launch_finalize(ctx->stream, f);
+        return run_finalize(ctx, f);
     };
-    HIPCHK(finalize(1, bits > 0));
+    // the plan of the level about to run, made once, by the finalize's time before it
+    LevelPlan plan = plan_level(ctx, 2);
+    if ((st = finalize(1, bits > 0 ? &plan : nullptr)) != QVQ_OK) return st;
     // with bits >= 1 the first search writes every row's index
     if (bits == 0) HIPCHK(hipMemsetAsync(ctx->d_A, 0, ctx->N * 4, ctx->stream));
 
@@ -2909,7 +2959,13 @@ QVQ_API qvq_status qvq_lbg(qvq_ctx *ctx, uint32_t bits, double eps, double *code
             std::swap(ctx->d_A, ctx->d_A_alt);   // d_A_alt: the previous level's assignment
         }
         alev[lvl] = ctx->d_A;
-        if ((st = run_level(ctx, K, slot, true, host_cb_of(ctx, lvl), ctx->seq, sync_kahan)) != QVQ_OK) return st;
+        const LevelPlan p = plan;
+        const bool split = lvl < bits;
+        if (split) plan = plan_level(ctx, 2 * K);
+        const LevelPlan *next = split ? &plan : nullptr;
+        LevelSums ls;
+        if ((st = run_level(ctx, p, K, slot, true, host_cb_of(ctx, lvl), ctx->seq, sync_kahan, ls)) != QVQ_OK) return st;
+        upd[slot] = ls.upd;
         if (spec) {   // the level's check: its tree now
             qvq_ctx::Verify &v = ctx->ver[lvl % 3];
             v.K = K;
@@ -2923,24 +2979,21 @@ QVQ_API qvq_status qvq_lbg(qvq_ctx *ctx, uint32_t bits, double eps, double *code
             ctx->cnt_local.clear();
             v.cs = CertState();
         }
-        const bool split = lvl < bits;
         {
-            const uint32_t copies = ctx->sums_copies;
-            const unsigned *tcnt = ctx->d_counters + 2 * slot + 1;   // the level's ties
-            if ((st = reduce_level(ctx, K, slot, &ctx->pub)) != QVQ_OK) return st;
+            ReducedSums rs;
+            if ((st = reduce_level(ctx, K, slot, ls, rs)) != QVQ_OK) return st;
             if ((st = all_reduce_sums(ctx, K)) != QVQ_OK) return st;
             TieExport tx;
             if (spec) {   // the level's tie rows and their indices go out with its codebook
                 tx.rows = ctx->d_ties;
-                tx.cnt = tcnt;
+                tx.cnt = ctx->d_counters + 2 * slot + 1;   // the level's ties
                 tx.A = ctx->d_A;
                 tx.codes = ctx->d_codes;
                 tx.cap = ctx->tx_cap;
                 tx.n_rows = ctx->N;
                 tx.out = ctx->dh_tx[lvl % 3];
             }
-            HIPCHK(finalize(K, split, copies, copies > 1 ? tcnt : nullptr, tx));
-            if (copies > 1) ctx->sums1_dirty = false;
+            if ((st = finalize(K, next, rs, tx)) != QVQ_OK) return st;
             if (spec) {   // the check of this level, on the worker
                 qvq_ctx::Verify &v = ctx->ver[lvl % 3];
                 v.posted = true;
@@ -2963,20 +3016,12 @@ QVQ_API qvq_status qvq_lbg(qvq_ctx *ctx, uint32_t bits, double eps, double *code
                 uint64_t nt_all = nt;   // every rank's ties: the ranks resolve together
                 if (multi && (st = vote(ctx, &nt_all, 1)) != QVQ_OK) return st;
                 join_tree_job(ctx, nt_all == 0);   // the level's tree: needed for ties only
-                if (nt_all) {
-                    const bool fused = use_fused(ctx, K);
-                    if (multi) {   // every rank's moves in copy 1, all-reduced, added by the finalize
-                        ctx->sums1_dirty = true;
-                        if ((st = resolve_kahan_ties_multi(ctx, K, slot, nt)) != QVQ_OK) return st;
-                        HIPCHK(finalize(K, split, 2, nullptr, TieExport(), true));
-                    } else {
-                        if (fused) ctx->sums1_dirty = true;
-                        if ((st = resolve_kahan_ties(ctx, K, slot, nt, fused)) != QVQ_OK) return st;
-                        // (without kd_reduce no fused search clears copy 1 before its next use)
-                        HIPCHK(finalize(K, split, fused ? 2 : 1, fused ? tcnt : nullptr, TieExport(),
-                                        fused && !kd_merge(ctx)));
-                    }
-                    ctx->sums1_dirty = false;
+                if (nt_all) {   // the level's finalize again, over the sums with the ties' moves
+                    // (several ranks: every rank's moves in copy 1, all-reduced, added by the finalize)
+                    st = multi ? resolve_kahan_ties_multi(ctx, p, K, slot, nt, rs) : resolve_kahan_ties(ctx, p, K, slot, nt, rs);
+                    if (st != QVQ_OK) return st;
+                    // (a communicator: without kd_reduce no fused search clears copy 1 before its next use)
+                    if ((st = finalize(K, next, rs, TieExport(), !kd_merge(ctx))) != QVQ_OK) return st;
                 }
                 if (split) {
                     std::swap(ctx->d_C64_split, ctx->d_C64_split_alt);
@@ -3011,8 +3056,6 @@ QVQ_API qvq_status qvq_lbg(qvq_ctx *ctx, uint32_t bits, double eps, double *code
     ctx->deferred.clear();
     if ((st = wait_stream(ctx)) != QVQ_OK) return st;
     if ((st = clear_dirty_sums(ctx)) != QVQ_OK) return st;
-    ctx->kd_pend = false;
-    ctx->pub = PubArgs();
     ctx->tm.kahan_redo++;
     spec = false;
     }
@@ -3036,7 +3079,7 @@ QVQ_API qvq_status qvq_lbg(qvq_ctx *ctx, uint32_t bits, double eps, double *code
             (void)hipEventSynchronize(ctx->ev[lvl - 1][1]);   // complete; the runtime may not know yet
             (void)hipEventElapsedTime(&a, ctx->ev[lvl - 1][0], ctx->ev[lvl - 1][1]);
         }
-        if (ctx->upd[lvl - 1]) {
+        if (upd[lvl - 1]) {
             (void)hipEventSynchronize(ctx->ev[lvl - 1][3]);
             (void)hipEventElapsedTime(&u, ctx->ev[lvl - 1][2], ctx->ev[lvl - 1][3]);
         }
@@ -3097,8 +3140,8 @@ QVQ_API qvq_status qvq_assign(qvq_ctx *ctx, const double *C, uint32_t K, uint32_
     }
     HIPCHK(hipMemsetAsync(ctx->d_counters, 0, 2 * sizeof(unsigned), ctx->stream));
     if ((st = run_prep(ctx, K)) != QVQ_OK) return st;
-    ctx->perm_k = 0;   // (prep writes no tile order)
-    if ((st = run_level(ctx, K, 0, false, C, 0)) != QVQ_OK) return st;
+    LevelSums ls;   // (no sums wanted)
+    if ((st = run_level(ctx, plan_level(ctx, K), K, 0, false, C, 0, false, ls)) != QVQ_OK) return st;
     unsigned stats[2];
     HIPCHK(hipMemcpyAsync(stats, ctx->d_counters, sizeof(stats), hipMemcpyDeviceToHost, ctx->stream));
     if (assign) HIPCHK(hipMemcpyAsync(assign, ctx->d_A, ctx->N * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -3129,11 +3172,12 @@ QVQ_API qvq_status qvq_update(qvq_ctx *ctx, const uint32_t *assign, uint32_t K, 
         if (counts) HIPCHK(hipMemcpyAsync(counts, d_cnt, (uint64_t)K * 8, hipMemcpyDeviceToHost, ctx->stream));
         return wait_stream(ctx);
     }
-    if ((st = run_update(ctx, ctx->d_A, K)) != QVQ_OK) return st;
+    if ((st = run_update(ctx, plan_level(ctx, K), ctx->d_A, K)) != QVQ_OK) return st;
     if ((st = all_reduce_sums(ctx, K)) != QVQ_OK) return st;
     FinArgs f = finalize_args(ctx, K, false);   // the centroids only
-    f.sums = ctx->d_sums;
-    HIPCHK(launch_finalize(ctx->stream, f));
+    const ReducedSums rs;
+    sums_args(ctx, f, &rs, false);
+    if ((st = run_finalize(ctx, f)) != QVQ_OK) return st;
     // results land in context-owned pinned memory and reach the caller only after the bounded
     // wait succeeds (a failed wait can leave these copies queued: wait_failed)
     const uint64_t cB = (uint64_t)K * ctx->D * 8, nB = (uint64_t)K * 8;
@@ -3350,51 +3394,25 @@ QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start, u
     HIPCHK(hipMemsetAsync(ctx->d_counters + CHANGED_COUNTER, 0, 2 * sizeof(unsigned), ctx->stream));
     if ((st = clear_dirty_sums(ctx)) != QVQ_OK) return st;
     if (changed64) HIPCHK(hipMemsetAsync(changed64, 0, 8, ctx->stream));
-    ctx->kd_pend = false;
-    ctx->pub = PubArgs();
-    const bool prune = use_prune(ctx, K);
+    const LevelPlan plan = plan_level(ctx, K);   // every iteration's
     volatile uint64_t *h_pub = ctx->h_ready + 4;   // [4] rows changed, [5] the distortion term
-    // C_t's tables, tile order and host copy (t = 0: from the starting codebook; else the centroid step)
-    auto publish = [&](uint32_t t, bool tables, const uint64_t *sums, const unsigned *gate, unsigned *cnts,
-                       bool count) -> qvq_status {
+    // C_t's tables, tile order and host copy (t = 0, rs null: from the starting codebook; else the
+    // centroid step over the sums rs describes: copy 1, kd_reduce_kernel's moves, is added and then
+    // cleared under its gate), or without tables the distortion term of C_t under those sums
+    auto publish = [&](uint32_t t, bool tables, const ReducedSums *rs, unsigned *cnts, bool count) -> qvq_status {
         FinArgs f = finalize_args(ctx, K, true);
-        f.sums = sums;
+        if (rs) sums_args(ctx, f, rs, true);
         f.C_src = ctx->d_C64_cent;
-        if (gate) {   // copy 1: kd_reduce_kernel's moves, added and then cleared under the gate
-            f.ncopy = 2;
-            f.cstride = sums_cap_stride(ctx);
-            f.gate = gate;
-            f.zero_sums = true;
-            f.zero_skip = 1;
-        }
-        if (tables) {
-            f.children = 1;
-            f.Kpad = pad32(K);
-            f.C_next = ctx->d_C64_split;
-            f.host_cb = dev_cb_of(ctx, t);
-            if (prune) {
-                f.perm = ctx->d_perm;
-                f.tint = ctx->d_tint;
-            }
-        } else {
-            f.measure = true;
-        }
+        if (tables) tables_args(ctx, f, 1, ctx->d_C64_split, dev_cb_of(ctx, t), plan.prunable);
+        else f.measure = true;
         if (count && changed64) f.changed64 = changed64;
         else if (count) f.changed = ctx->d_counters + CHANGED_COUNTER;
         f.clear_cnt = cnts;
         f.pub = ctx->dh_ready + 4;
         f.seq = ++ctx->seq;
-        HIPCHK(launch_finalize(ctx->stream, f));
-        if (tables) ctx->perm_k = prune ? K : 0;
-        return QVQ_OK;
+        return run_finalize(ctx, f);
     };
-    // the sums of the assignment run_level just made, reduced into d_sums (a communicator:
-    // run_level has answered the kd-tree ties itself, the sums are one copy and there is no gate)
-    auto reduce = [&](int slot, const unsigned *&gate) -> qvq_status {
-        gate = ctx->sums_copies > 1 ? ctx->d_counters + 2 * slot + 1 : nullptr;
-        return reduce_level(ctx, K, slot, nullptr);
-    };
-    if ((st = publish(0, true, nullptr, nullptr, nullptr, false)) != QVQ_OK) return st;
+    if ((st = publish(0, true, nullptr, nullptr, false)) != QVQ_OK) return st;
 
     uint32_t t = 0;        // iterations done: C_t is the codebook, A_t (t >= 1, or continuing) in d_A
     int stop = -1;
@@ -3424,16 +3442,18 @@ QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start, u
         }
         const int slot = (int)(t & 1);
         if (have_A) std::swap(ctx->d_A, ctx->d_A_alt);   // d_A_alt: A_t; d_A takes the search against C_t
-        if ((st = run_level(ctx, K, slot, true, host_cb_of(ctx, t), ctx->seq)) != QVQ_OK) return st;
+        LevelSums ls;   // (dropped with the search where the call stops without fresh)
+        if ((st = run_level(ctx, plan, K, slot, true, host_cb_of(ctx, t), ctx->seq, false, ls)) != QVQ_OK) return st;
         if (t >= 1) absorb();   // (run_level waited for C_t)
         else if (max_iters == 0) stop = QVQ_STOP_MAXIT;
-        const unsigned *gate = nullptr;
+        // the sums of the assignment run_level just made, reduced into d_sums (a communicator:
+        // run_level has answered the kd-tree ties itself, the sums are one copy and there is no gate)
+        ReducedSums rs;
         if (stop >= 0) {
             if (fresh) {   // the search in flight is A* = assign(C_t): its sums, the distortion of (C_t, A*)
-                if ((st = reduce(slot, gate)) != QVQ_OK) return st;
+                if ((st = reduce_level(ctx, K, slot, ls, rs)) != QVQ_OK) return st;
                 if ((st = all_reduce_sums(ctx, K)) != QVQ_OK) return st;   // every rank's rows of A*
-                if ((st = publish(t, false, ctx->d_sums, gate, ctx->d_counters + 2 * slot, false)) != QVQ_OK) return st;
-                ctx->sums1_dirty = false;
+                if ((st = publish(t, false, &rs, ctx->d_counters + 2 * slot, false)) != QVQ_OK) return st;
                 if ((st = wait_codebook(ctx, ctx->seq)) != QVQ_OK) return st;
                 std::atomic_thread_fence(std::memory_order_acquire);
                 const uint64_t bits = h_pub[1];
@@ -3441,24 +3461,21 @@ QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start, u
                 std::memcpy(&term, &bits, 8);
                 d_last = std::max(0.0, (xsq - term) / norm);
             } else {   // dropped: A_t stays the assignment
-                ctx->kd_pend = false;
                 if (have_A) std::swap(ctx->d_A, ctx->d_A_alt);
                 if ((st = wait_stream(ctx)) != QVQ_OK) return st;
             }
             break;
         }
-        if ((st = reduce(slot, gate)) != QVQ_OK) return st;
+        if ((st = reduce_level(ctx, K, slot, ls, rs)) != QVQ_OK) return st;
         if (changed64) {   // the level's sums and the rows changed over every rank: one collective
-            ctx->sums1_dirty = true;   // (the slot lies in copy 1's range: cleared if the call ends before the finalize)
+            mark_sums1(ctx);   // (the slot lies in copy 1's range: cleared if the call ends before the finalize)
             if (have_A) HIPCHK(launch_count_changed64(ctx->stream, ctx->num_cu, ctx->d_A, ctx->d_A_alt, ctx->N, changed64));
             if ((st = all_reduce(ctx, ctx->d_sums, cell_u64 + 1, false)) != QVQ_OK) return st;
         } else if (have_A) {
             HIPCHK(launch_count_changed(ctx->stream, ctx->num_cu, ctx->d_A, ctx->d_A_alt, ctx->N,
                                         ctx->d_counters + CHANGED_COUNTER));
         }
-        if ((st = publish(t + 1, true, ctx->d_sums, gate, ctx->d_counters + 2 * slot, have_A || changed64)) != QVQ_OK)
-            return st;
-        ctx->sums1_dirty = false;
+        if ((st = publish(t + 1, true, &rs, ctx->d_counters + 2 * slot, have_A || changed64)) != QVQ_OK) return st;
         have_A = true;
         t++;
     }
@@ -3751,44 +3768,25 @@ QVQ_API qvq_status qvq_host_finalize(const uint64_t *hi, const uint64_t *lo, con
 
 QVQ_API qvq_status qvq_host_plan(uint32_t dim, uint32_t K, uint64_t n, qvq_plan *out) {
     if (!out || dim == 0 || K == 0 || n == 0) return QVQ_EINVAL;
-    std::unique_ptr<qvq_ctx> ctx(new qvq_ctx());   // the shape only: no device work
-    ctx->D = dim;
-    ctx->Dp = (dim + 3) & ~3u;
-    ctx->N = n;
-    if (ctx->Dp > 64) return QVQ_EINVAL;
+    const uint32_t Dp = (dim + 3) & ~3u;
+    if (Dp > 64) return QVQ_EINVAL;
+    const LevelPlan lp = plan_level(dim, Dp, n, K);   // the plan run_level switches on, field by field
     qvq_plan p;
     std::memset(&p, 0, sizeof(p));
-    // run_level's order of questions
-    if (use_mfma(ctx.get(), K)) {
-        p.search = mf_small_search(K) ? QVQ_PLAN_SEARCH_SMALL : QVQ_PLAN_SEARCH_MF32;
-        p.fused = use_fused(ctx.get(), K);
-    } else if (use_wide(ctx.get(), K)) {
-        p.search = QVQ_PLAN_SEARCH_WIDE;
-        p.cb_resident = wide_codebook_resident(ctx->Dp, K);
-    } else {
-        p.search = QVQ_PLAN_SEARCH_VALU;
-        const uint32_t KT = assign_valu_tile(ctx->Dp, K);
-        p.valu_tiles = (K + KT - 1) / KT;
-    }
-    p.prune = use_prune(ctx.get(), K);
-    if (p.search == QVQ_PLAN_SEARCH_MF32) p.c32_staged = mf32_c32_staged(K, false, false);
-    if (use_recheck_mf32(ctx.get(), K)) {
-        p.recheck = QVQ_PLAN_RECHECK_MF32;
-    } else {
-        switch (recheck_path(ctx->Dp, K)) {
-        case RecheckPath::Staged: p.recheck = QVQ_PLAN_RECHECK_STAGED; break;
-        case RecheckPath::Chunked: p.recheck = QVQ_PLAN_RECHECK_CHUNKED; break;
-        case RecheckPath::Global: p.recheck = QVQ_PLAN_RECHECK_GLOBAL; break;
-        }
-    }
-    if (use_sorted_sums(ctx.get(), K)) {
+    p.search = lp.search;
+    p.fused = lp.fusable;
+    p.c32_staged = lp.c32_staged;
+    p.cb_resident = lp.cb_resident;
+    p.valu_tiles = lp.valu_tiles;
+    p.prune = lp.prunable;
+    p.recheck = lp.recheck;
+    if (lp.sorted_sums) {
         p.update = QVQ_PLAN_UPDATE_SORTED;
     } else {
-        const UpdatePlan up = update_plan(K, dim);
-        p.update = up.runs ? QVQ_PLAN_UPDATE_RUNS : QVQ_PLAN_UPDATE_LDS;
-        p.update_copies = up.runs ? up.copies : up.passes;
+        p.update = lp.update.runs ? QVQ_PLAN_UPDATE_RUNS : QVQ_PLAN_UPDATE_LDS;
+        p.update_copies = lp.update.runs ? lp.update.copies : lp.update.passes;
     }
-    p.device_tree = !env_is("QVQ_KDTREE", "host") && device_tree_shape(K, dim);
+    p.device_tree = !lp.kd_host && lp.tree_shape;
     *out = p;
     return QVQ_OK;
 }

@@ -1,6 +1,6 @@
 """The case table of tests/test_gpu_largek.py (tests/helpers/largek_cases.py) against the engine's
-dispatch, on the CPU: quant_amd.host_plan answers from the predicates run_level, launch_recheck,
-launch_assign_valu and launch_update dispatch with, so a case that claims a path really takes it,
+dispatch, on the CPU: quant_amd.host_plan reports the plan (plan_level) that run_level, launch_recheck,
+launch_assign_valu and launch_update dispatch on, so a case that claims a path really takes it,
 and the table as a whole reaches every path.  A pull request that moves a kernel's capacity fails
 here, by the name of the case that no longer covers its path: move the case with the threshold."""
 import pytest
