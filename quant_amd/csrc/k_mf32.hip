@@ -74,23 +74,6 @@ __host__ __device__ inline M32Lds m32_lds_layout(uint32_t K, bool fuse, bool sta
     return L;
 }
 
-// Per-run sums over consecutive lanes with equal key (as in k_assign.hip): returns true on the
-// last lane of each run, which then holds the run's sums.
-__device__ inline bool m32_runs_reduce(uint32_t key, uint32_t (&v)[MF_D + 1], int lane) {
-    const uint32_t prev = wave_prev_u32(key);
-    const uint32_t next = wave_next_u32(key);
-    const bool head = lane == 0 || prev != key;
-    const uint32_t h = wave_scan_max(head ? (uint32_t)lane : 0u);
-    const int src = h == 0 ? 0 : (int)h - 1;
-#pragma unroll
-    for (int i = 0; i <= MF_D; i++) {
-        const uint32_t pre = wave_scan_add(v[i]);
-        const uint32_t before = __shfl(pre, src);
-        v[i] = pre - (h == 0 ? 0u : before);
-    }
-    return lane == 63 || next != key;
-}
-
 // P / Q (LDS, layout above) from the 56-byte rows [hi0..3 lo0..3 | hi4..7 lo4..7 | hi8..11
 // lo8..11 | n] of Kp code vectors.
 __device__ inline void m32_stage_pq(unsigned char *lds, uint32_t qoff, const _Float16 *g_rows, uint32_t Kp, int tid,
@@ -133,9 +116,9 @@ __device__ inline void m32_track_tagged(float m, uint32_t keep, uint32_t u, floa
 
 // TAG: unit indices in the scores' low bits (idbits of them, idbits >= log2 of the units per
 // lane; orrel = 2^(idbits - 22) bounds twice the relative change).
-// copies > 1 (fused): every row adds its terms straight into LDS copy lane % copies of the
-// sums (runs of equal indices then meet copies instead of one address); copies = 1: the
-// wave run reduction first, then one atomic set per run.
+// Fused: every row adds its terms straight into LDS copy lane % copies of the sums (runs of
+// equal indices then meet copies instead of one address); with 8-code-vector units (K > 128,
+// few copies or one) in a staggered component order (below).
 // PRUNE (tiles in the order of perm, tint: finalize's prune_order): a chunk visits its code
 // tiles outward from the one nearest its rows' projection and stops once the tiles left on both
 // sides are provably farther than every row's current best (see the tile loop).
@@ -223,6 +206,22 @@ __global__ __launch_bounds__(M32_THREADS) void assign_mf32_kernel(
     const int32_t tlo = PRUNE && lane < (int)ntiles ? g_tint[2 * lane] : 0x7FFFFFFF;
     const int32_t thi = PRUNE && lane < (int)ntiles ? g_tint[2 * lane + 1] : (int32_t)0x80000000;
     const float sx2 = th.sx * th.sx, dsx = (float)MF_D / sx2;
+
+    // Fused sums, staggered (STAG): the lanes that share a sums copy walk the 12 components as a
+    // ring from different starts -- lane L, g = L / copies, adds component (j + g) % 12 at step
+    // j -- so lanes of one (copy, code vector) meet on 12 addresses (rows K + 1 apart: 12 banks)
+    // in an instruction, not on one.  ring[j]: byte offset of that component's row in the
+    // lane's copy; sga / sgr: the word and byte rotation of the row's 12 bytes.
+    constexpr bool STAG = FUSE && U == 8;
+    const uint32_t scp = (uint32_t)lane & (copies - 1);
+    const uint32_t sg = STAG ? ((uint32_t)lane >> __builtin_ctz(copies)) % MF_D : 0;
+    const uint32_t sga = sg >> 2, sgr = sg & 3;
+    uint32_t ring[MF_D];
+#pragma unroll
+    for (int j = 0; j < MF_D; j++) {
+        const uint32_t d = sg + j < MF_D ? sg + j : sg + j - MF_D;
+        ring[j] = (scp * m32_sum_stride(K, copies) + d * m32_kstride(K)) * 8;
+    }
 
     for (; chunk < nchunks; chunk += stride) {
         const uint64_t base = chunk * M32_ROWS;
@@ -441,7 +440,25 @@ __global__ __launch_bounds__(M32_THREADS) void assign_mf32_kernel(
         }
         if (FUSE) {
             // every row at its provisional index; the recheck / kd-tree move re-assigned ones
-            if (copies > 1) {
+            if constexpr (STAG) {
+                if (valid) {
+                    // the row's 12 bytes rotated by this lane's ring start: step j takes byte j of
+                    // ro, component (j + sg) % 12 -- words by sg / 4, then bytes by sg % 4
+                    const uint32_t y0 = sga == 0 ? own[0] : sga == 1 ? own[1] : own[2];
+                    const uint32_t y1 = sga == 0 ? own[1] : sga == 1 ? own[2] : own[0];
+                    const uint32_t y2 = sga == 0 ? own[2] : sga == 1 ? own[0] : own[1];
+                    const uint32_t ro[3] = {__builtin_amdgcn_alignbyte(y1, y0, sgr), __builtin_amdgcn_alignbyte(y2, y1, sgr),
+                                            __builtin_amdgcn_alignbyte(y0, y2, sgr)};
+                    unsigned char *at = reinterpret_cast<unsigned char *>(sums) + (size_t)rk * 8;
+#pragma unroll
+                    for (int j = 0; j < MF_D; j++) {
+                        const uint32_t b = (ro[j / 4] >> (8 * (j % 4))) & 0xFF;
+                        atomicAdd((unsigned long long *)(at + ring[j]),
+                                  (unsigned long long)((uint64_t)(b ^ 0x80u) << 32 | lo8_at0[b]));
+                    }
+                    atomicAdd(&cnt[scp * m32_cnt_stride(K, copies) + rk], 1u);
+                }
+            } else {
                 if (valid) {
                     const uint32_t cp = (uint32_t)lane & (copies - 1);
                     uint64_t *my = sums + (size_t)cp * m32_sum_stride(K, copies);
@@ -452,22 +469,6 @@ __global__ __launch_bounds__(M32_THREADS) void assign_mf32_kernel(
                                   (unsigned long long)((uint64_t)(b ^ 0x80u) << 32 | lo8_at0[b]));
                     }
                     atomicAdd(&cnt[cp * m32_cnt_stride(K, copies) + rk], 1u);
-                }
-            } else {
-                uint32_t v[MF_D + 1];
-#pragma unroll
-                for (int d = 0; d < MF_D; d++) {
-                    const uint32_t b = (own[d / 4] >> (8 * (d % 4))) & 0xFF;
-                    v[d] = valid ? ((b ^ 0x80u) << 16 | lo8_at0[b]) : 0u;   // <= 64 rows: no carry
-                }
-                v[MF_D] = valid ? 1u : 0u;
-                const bool tail = m32_runs_reduce(valid ? rk : 0xFFFFFFFFu, v, lane);
-                if (tail && valid) {
-#pragma unroll
-                    for (int d = 0; d < MF_D; d++)
-                        atomicAdd((unsigned long long *)&sums[(uint32_t)d * m32_kstride(K) + rk],
-                                  (unsigned long long)((((uint64_t)(v[d] >> 16)) << 32) | (v[d] & 0xFFFF)));
-                    atomicAdd(&cnt[rk], v[MF_D]);
                 }
             }
         }
@@ -734,12 +735,12 @@ hipError_t launch_assign_mf32(hipStream_t s, int grid, bool fuse, const uint8_t 
     const bool prune = perm && tint;
     if (prune && !mf32_prune_fits(K, fuse)) return hipErrorInvalidValue;
     const bool staged = mf32_c32_staged(K, fuse, prune);
-    // sums copies (fused, 64 <= K <= 512): the most, up to 16, that fit.  With the padded copy
-    // strides, C3: K = 64 / 128 / 256 / 512 -6 / -22 / -19 / -16 us against the wave run
-    // reduction; K = 1024 has no room for a second copy (the run reduction at the pruned K = 256:
-    // 123.3-123.9 vs 113.6-116.2 us, profiles/r05ap).
+    // sums copies (fused, K <= 512): the most, up to 16, that fit.  With the padded copy
+    // strides, C3: K = 64 / 128 / 256 / 512 -6 / -22 / -19 / -16 us against a wave run
+    // reduction into one copy; K = 1024 has no room for a second copy and adds into the one in
+    // the staggered order (230 -> 219 us against the run reduction, profiles/sums_stagger).
     uint32_t copies = 1;
-    if (fuse && K >= 64 && K <= 512)
+    if (fuse && K <= 512)
         while (copies < 16 && m32_lds_layout(K, fuse, staged, copies * 2, prune).total <= M32_LDS_MAX) copies *= 2;
     const size_t lds = m32_lds_layout(K, fuse, staged, copies, prune).total;
     // 4-code-vector units while the tile loop is short (the recompute dominates); K = 256 takes
