@@ -98,7 +98,8 @@ QVQ_API qvq_status qvq_set_synthetic(qvq_ctx *ctx, uint32_t S, uint64_t seed0, u
  * When every value is one the NORMAL or SCALED colour space produces from a byte (or 0.0) the
  * fast path applies (exact integer sums: centroids within 1 ulp of the reference's Kahan sums).
  * Any other data (arbitrary finite doubles, CIE1931 values) takes the exact mode of
- * qvq_set_vectors_exact.
+ * qvq_set_vectors_exact.  The rows are uploaded once and classified and packed on the device
+ * (see qvq_set_vectors_device for the rule).
  */
 QVQ_API qvq_status qvq_set_vectors(qvq_ctx *ctx, const double *X, uint64_t n, uint32_t dim);
 /*
@@ -109,6 +110,42 @@ QVQ_API qvq_status qvq_set_vectors(qvq_ctx *ctx, const double *X, uint64_t n, ui
  * byte path; one rank only (QVQ_EUNSUPPORTED with a communicator).  n < 2^31.
  */
 QVQ_API qvq_status qvq_set_vectors_exact(qvq_ctx *ctx, const double *X, uint64_t n, uint32_t dim);
+/*
+ * The same two for rows that are already in device memory (e.g. a float64 torch tensor): d_X is
+ * row-major fp64 n x dim on the context's GPU, 8-byte aligned (a null, misaligned or non-device
+ * pointer is QVQ_EINVAL).  flags = 0 chooses the mode from the values as qvq_set_vectors does;
+ * QVQ_VECTORS_EXACT forces exact mode as qvq_set_vectors_exact.  stream is the hipStream_t whose
+ * queued work produces d_X (NULL = the legacy null stream): the engine records an event on it and
+ * makes its own stream wait for that event -- the mirror image of qvq_decode_device.  The call
+ * returns when the engine has read the rows for the last time: the caller may overwrite or free
+ * d_X on return (exact mode keeps a device-to-device copy of its own).  The argument checks of
+ * qvq_set_vectors (n == 0, dim == 0, dim > 64, n >= 2^32; n >= 2^31 with QVQ_VECTORS_EXACT) run
+ * before any byte of d_X is read; a set that turns out not to be a byte image returns, in this
+ * order, QVQ_EUNSUPPORTED with a communicator joined, QVQ_EINVAL for n >= 2^31, QVQ_EINVAL for a
+ * value that is not finite.  A call that returns an error leaves the resident training set as it
+ * was.  (The host entry points above take the same route: one upload, then the same device pass.)
+ *
+ * Which values are byte images: those whose bits equal the colour space's own table entry
+ * (qvq_host_colorspace_values), and no others -- not -0.0, not a neighbour of a table value.  The
+ * SCALED table is the reference's value under -ffast-math, u * fl(1/255), which is NOT u / 255.0:
+ * the two differ in the last bit for 24 of the 256 bytes (u = 33, 37, 41, ...).  A caller who
+ * builds SCALED rows on the device with a division therefore gets exact mode, not the byte path;
+ * gather the rows from the table instead.
+ */
+enum { QVQ_VECTORS_EXACT = 1 };   /* flags: force exact mode, as qvq_set_vectors_exact */
+QVQ_API qvq_status qvq_set_vectors_device(qvq_ctx *ctx, const void *d_X, uint64_t n, uint32_t dim, uint32_t flags,
+                                          void *stream);
+/* What is resident: the mode the last qvq_set_* call chose, its colour space and shape. */
+typedef struct {
+    uint32_t mode;        /* 0 none, 1 byte path, 2 exact mode */
+    int32_t colorspace;   /* QVQ_CS_*; -1 in exact mode or none */
+    uint64_t n;
+    uint32_t dim;
+} qvq_training_info;
+QVQ_API qvq_status qvq_get_training_info(const qvq_ctx *ctx, qvq_training_info *out);
+/* Device ms of the last qvq_set_vectors* call's two passes over the rows, [0] classify and [1] pack
+ * (0 in exact mode), from HIP events under qvq_set_timing(-3); 0 otherwise. */
+QVQ_API qvq_status qvq_get_ingest_ms(const qvq_ctx *ctx, double ms[2]);
 
 QVQ_API uint64_t qvq_num_vectors(const qvq_ctx *ctx);
 QVQ_API uint32_t qvq_dim(const qvq_ctx *ctx);
@@ -341,6 +378,20 @@ QVQ_API qvq_status qvq_host_exact_plan(uint32_t dim, uint32_t K, qvq_exact_plan 
  * the distortion). */
 typedef struct { uint32_t block, assign_blocks, iota_blocks, dist_blocks; } qvq_exact_grids;
 QVQ_API qvq_status qvq_host_exact_grids(qvq_exact_grids *out);
+/* The colour space's byte -> value table (Terms::v64, the values the reference computes):
+ * out[b] = the value of byte b.  QVQ_EUNSUPPORTED for CIE1931. */
+QVQ_API qvq_status qvq_host_colorspace_values(int colorspace, double out[256]);
+/* The value -> code rule of qvq_set_vectors on the host (quant_amd/csrc/byte_image.hpp, the
+ * function the device pass applies): *colorspace = QVQ_CS_SCALED if every value of X (n x dim) is a
+ * SCALED byte image, else QVQ_CS_NORMAL if every value is a NORMAL one, else -1; codes (n x Dp, Dp =
+ * dim rounded up to 4, may be NULL) gets a byte image's codes, pad bytes the space's zero code
+ * (0x80 SCALED, 0x00 NORMAL), and is left alone for -1. */
+QVQ_API qvq_status qvq_host_classify(const double *X, uint64_t n, uint32_t dim, int32_t *colorspace, uint8_t *codes);
+/* The device pass's launch shape: one lane per 4-byte code word (Dp / 4 words per row), `block`
+ * lanes per block, at most `blocks` blocks: more than block * blocks words take the kernel's
+ * grid-stride loop a second time. */
+typedef struct { uint32_t block, blocks; } qvq_ingest_grid;
+QVQ_API qvq_status qvq_host_ingest_grid(qvq_ingest_grid *out);
 /* The engine's bounded-wait policy (quant_amd/csrc/wait.hpp) driven by scripted probes, for
  * tests: scenario 0 the work publishes after ~5 ms; 1 it never does, no communicator; 2 it
  * never does, a healthy communicator; 3 the communicator reports an error after ~5 ms; 4 the

@@ -50,6 +50,15 @@ class _ExactGrids(ctypes.Structure):
     _fields_ = [(f, ctypes.c_uint32) for f in ("block", "assign_blocks", "iota_blocks", "dist_blocks")]
 
 
+class _TrainingInfo(ctypes.Structure):
+    _fields_ = [("mode", ctypes.c_uint32), ("colorspace", ctypes.c_int32), ("n", ctypes.c_uint64),
+                ("dim", ctypes.c_uint32)]
+
+
+class _IngestGrid(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_uint32) for f in ("block", "blocks")]
+
+
 # qvq_plan enumerators (qvq.h)
 PLAN_SEARCH_SMALL, PLAN_SEARCH_MF32, PLAN_SEARCH_WIDE, PLAN_SEARCH_VALU = 0, 1, 2, 3
 PLAN_RECHECK_MF32, PLAN_RECHECK_STAGED, PLAN_RECHECK_CHUNKED, PLAN_RECHECK_GLOBAL = 0, 1, 2, 3
@@ -64,10 +73,13 @@ EXPORTED = ["qvq_create", "qvq_destroy", "qvq_last_error", "qvq_version", "qvq_s
             "qvq_set_timeout", "qvq_host_wait_probe", "qvq_comm_init_host", "qvq_comm_info", "qvq_set_vectors_exact",
             "qvq_update_kahan_split", "qvq_host_pool_stress", "qvq_kdtree_device_check",
             "qvq_host_kdtree_image", "qvq_refine", "qvq_host_plan", "qvq_host_exact_plan",
-            "qvq_host_exact_grids"]
+            "qvq_host_exact_grids", "qvq_set_vectors_device", "qvq_get_training_info", "qvq_get_ingest_ms",
+            "qvq_host_colorspace_values", "qvq_host_classify", "qvq_host_ingest_grid"]
 
 COMM_NONE, COMM_RCCL, COMM_HOST = 0, 1, 2
 REFINE_FRESH = 1                              # qvq_refine flags
+VECTORS_EXACT = 1                             # qvq_set_vectors_device flags
+MODE_NONE, MODE_BYTE, MODE_EXACT = 0, 1, 2    # qvq_training_info.mode
 STOP_FIXED, STOP_EPS, STOP_MAXIT = 0, 1, 2    # qvq_refine_info.stop
 # int fn(void *buf, uint64_t count, int dtype, void *user) (qvq.h, qvq_comm_init_host)
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p)
@@ -120,6 +132,12 @@ def lib():
             "qvq_host_plan": ([u32, u32, u64, ctypes.POINTER(_Plan)], i),
             "qvq_host_exact_plan": ([u32, u32, ctypes.POINTER(_ExactPlan)], i),
             "qvq_host_exact_grids": ([ctypes.POINTER(_ExactGrids)], i),
+            "qvq_set_vectors_device": ([P, P, u64, u32, u32, P], i),
+            "qvq_get_training_info": ([P, ctypes.POINTER(_TrainingInfo)], i),
+            "qvq_get_ingest_ms": ([P, P], i),
+            "qvq_host_colorspace_values": ([i, P], i),
+            "qvq_host_classify": ([P, u64, u32, ctypes.POINTER(ctypes.c_int32), P], i),
+            "qvq_host_ingest_grid": ([ctypes.POINTER(_IngestGrid)], i),
         }
         for name, (args, res) in sig.items():
             if os.environ.get("QVQ_LIB") and not hasattr(L, name):
@@ -164,6 +182,7 @@ class Engine:
         L = lib()
         _check(L.qvq_create(device, ctypes.byref(h)))
         self._h = h
+        self._device = device
         self._L = L   # held by the engine: at interpreter shutdown the module globals may be gone
 
     def close(self):
@@ -199,10 +218,44 @@ class Engine:
 
     def set_vectors(self, X, exact=False):
         """fp64 training set N x dim.  Byte-image values (NORMAL/SCALED) take the fast path; any
-        other data -- or exact=True -- the exact mode (the reference's Kahan arithmetic, qvq.h)."""
+        other data -- or exact=True -- the exact mode (the reference's Kahan arithmetic, qvq.h).
+        X: anything numpy takes, or a torch tensor.  A CUDA tensor stays on the device
+        (set_vectors_device with its data_ptr() and torch's current stream): it must be float64,
+        2-D, contiguous and on the engine's GPU (QVQError QVQ_EINVAL otherwise, before anything
+        reaches the library).  A CPU tensor goes through numpy."""
+        if getattr(X, "is_cuda", False):
+            import torch
+            if (X.dtype != torch.float64 or X.dim() != 2 or not X.is_contiguous()
+                    or X.device.index != self._device):
+                raise QVQError(1, "a device tensor must be float64, 2-D, contiguous and on the engine's GPU")
+            with torch.cuda.device(X.device):
+                stream = torch.cuda.current_stream().cuda_stream
+            return self.set_vectors_device(X.data_ptr(), X.shape[0], X.shape[1], exact=exact, stream=stream)
+        if hasattr(X, "is_cuda"):   # a CPU tensor
+            X = X.detach().numpy()
         X = np.ascontiguousarray(X, np.float64)
         fn = lib().qvq_set_vectors_exact if exact else lib().qvq_set_vectors
         _check(fn(self._h, _p(X), X.shape[0], X.shape[1]), self._h)
+
+    def set_vectors_device(self, ptr, n, dim, exact=False, stream=None):
+        """fp64 rows n x dim already in device memory (qvq_set_vectors_device): ptr their address,
+        stream the hipStream_t handle whose queued work produces them (None or 0 = the legacy null
+        stream).  The rows may be overwritten or freed once this returns."""
+        _check(lib().qvq_set_vectors_device(self._h, ctypes.c_void_p(ptr), n, dim, VECTORS_EXACT if exact else 0,
+                                            ctypes.c_void_p(stream or 0)), self._h)
+
+    def training_info(self):
+        """What is resident (qvq_get_training_info): {"mode": MODE_NONE / MODE_BYTE / MODE_EXACT,
+        "colorspace": NORMAL / SCALED, or -1 in exact mode or none, "n", "dim"}."""
+        t = _TrainingInfo()
+        _check(lib().qvq_get_training_info(self._h, ctypes.byref(t)), self._h)
+        return {"mode": int(t.mode), "colorspace": int(t.colorspace), "n": int(t.n), "dim": int(t.dim)}
+
+    def ingest_ms(self):
+        """(classify ms, pack ms) of the last set_vectors* call's device passes, under set_timing(-3)."""
+        ms = np.zeros(2, np.float64)
+        _check(lib().qvq_get_ingest_ms(self._h, _p(ms)), self._h)
+        return float(ms[0]), float(ms[1])
 
     @property
     def n(self):
@@ -430,6 +483,33 @@ def host_exact_grids():
     return {f: int(getattr(g, f)) for f, _ in _ExactGrids._fields_}
 
 
+def host_ingest_grid():
+    """The fp64 front door's launch shape (qvq_host_ingest_grid): {"block", "blocks"}; one lane per
+    4-byte code word."""
+    g = _IngestGrid()
+    _check(lib().qvq_host_ingest_grid(ctypes.byref(g)))
+    return {f: int(getattr(g, f)) for f, _ in _IngestGrid._fields_}
+
+
+def colorspace_values(colorspace=SCALED):
+    """The colour space's byte -> value table (qvq_host_colorspace_values): 256 float64, the values
+    a byte-image training set must hold bit for bit."""
+    out = np.empty(256, np.float64)
+    _check(lib().qvq_host_colorspace_values(int(colorspace), _p(out)))
+    return out
+
+
+def host_classify(X, want_codes=True):
+    """The value -> code rule of set_vectors on the host (qvq_host_classify): (colour space or -1,
+    codes [n, Dp] uint8 or None)."""
+    X = np.ascontiguousarray(X, np.float64)
+    n, dim = X.shape
+    cs = ctypes.c_int32(-2)
+    codes = np.zeros((n, (dim + 3) & ~3), np.uint8) if want_codes else None
+    _check(lib().qvq_host_classify(_p(X), n, dim, ctypes.byref(cs), _p(codes) if want_codes else None))
+    return cs.value, (codes if want_codes and cs.value >= 0 else None)
+
+
 # KdbNode (kdtree_dev.hpp) and the image layout of qvq_host_kdtree_image
 KDB_NODE = np.dtype([("child1", "<i4"), ("child2", "<i4"), ("left", "<u4"), ("right", "<u4"), ("divfeat", "<i4"),
                      ("depth", "<u4"), ("divlow", "<f8"), ("divhigh", "<f8"), ("cutval", "<f8"),
@@ -517,7 +597,9 @@ class LBGQuantizer(AbstractQuantizer):
     def quantize(self, trainingSet, n, eps):
         if self._engine is None:
             self._engine = Engine(self._device)
-        self._engine.set_vectors(np.asarray(trainingSet, np.float64))
+        # a CUDA tensor goes straight through (no torch import here when handed numpy)
+        dev = getattr(trainingSet, "is_cuda", False)
+        self._engine.set_vectors(trainingSet if dev else np.asarray(trainingSet, np.float64))
         res = self._engine.lbg(int(n), eps)
         if self._refine_iters > 0 or self._fresh:
             res = self._engine.refine(max_iters=self._refine_iters, eps=eps, fresh=self._fresh)[:3]

@@ -434,6 +434,18 @@ hipError_t launch_fix_rows(hipStream_t s, const uint8_t *codes, uint32_t Dp, uin
 // 256-bin histogram of the first D bytes of every row (hist zeroed first).
 hipError_t launch_byte_hist(hipStream_t s, const uint8_t *codes, uint64_t N, uint32_t D, uint32_t Dp,
                             uint64_t *hist);
+// The fp64 front door (k_ingest.hip, byte_image.hpp): X [n][dim] row-major, 8-byte aligned; tab
+// [2][256] the spaces' Terms::v64, indexed by QVQ_CS_NORMAL / QVQ_CS_SCALED.  One lane per 4-byte
+// code word, ING_THREADS lanes per block, at most ING_GRID_CAP blocks (more words: the grid-stride
+// loop again).  classify: *verdict = the ING_* bits that hold for every value of the set (the
+// launcher sets it first).  pack: codes [n][Dp] under colour space cs, pad bytes the space's pad code.
+constexpr int ING_THREADS = 256;
+constexpr int ING_GRID_CAP = 2048;
+enum : unsigned { ING_SCALED_OK = 1, ING_NORMAL_OK = 2, ING_FINITE = 4 };
+hipError_t launch_ingest_classify(hipStream_t s, const double *X, uint64_t n, uint32_t dim, const double *tab,
+                                  unsigned *verdict);
+hipError_t launch_ingest_pack(hipStream_t s, const double *X, uint64_t n, uint32_t dim, uint32_t cs, const double *tab,
+                              uint8_t *codes);
 // Exact mode (k_exact.hip): fp64 rows X [N][D].
 hipError_t launch_exact_assign(hipStream_t s, const double *X, uint64_t N, uint32_t D, const double *C, uint32_t K,
                                double tie_rel, uint32_t *A, uint32_t *ties, unsigned *tie_cnt);

@@ -34,6 +34,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "byte_image.hpp"
 #include "common.hpp"
 #include "exact_plan.hpp"
 #include "kdtree.hpp"
@@ -310,6 +311,12 @@ struct qvq_ctx {
     int timing_level = -2;   // qvq_set_timing: -1 all levels, -2 none (default), else that level only
     hipEvent_t ev_end = nullptr;
     hipEvent_t ev_sync = nullptr;   // wait_stream
+    // the fp64 front door (k_ingest.hip): both spaces' value tables [2][256], the classify pass's
+    // verdict and its pinned copy; events around the passes and their device ms (qvq_set_timing(-3))
+    double *d_ing_tab = nullptr;
+    unsigned *d_ing_verdict = nullptr, *h_ing_verdict = nullptr;
+    hipEvent_t ev_ing[3] = {nullptr, nullptr, nullptr};
+    double ingest_ms[2] = {0, 0};
     double timeout_s = 120;         // bound of every host wait (qvq_set_timeout, QVQ_TIMEOUT_S)
 
     // multi-GPU: an RCCL communicator, or (tests) a host all-reduce callback
@@ -2375,6 +2382,22 @@ QVQ_API qvq_status qvq_create(int hip_device, qvq_ctx **out) {
     if ((e = hipEventCreate(&ctx->ev_end)) != hipSuccess) return bail(e, "hipEventCreate");
     if ((e = hipEventCreateWithFlags(&ctx->ev_sync, hipEventDisableTiming)) != hipSuccess)
         return bail(e, "hipEventCreate");
+    {
+        std::vector<double> tab(512);
+        for (int cs : {QVQ_CS_NORMAL, QVQ_CS_SCALED}) {
+            Terms t;
+            make_terms(cs, t);
+            std::memcpy(&tab[256 * cs], t.v64, sizeof(t.v64));
+        }
+        if ((e = hipMalloc(&ctx->d_ing_tab, 512 * 8)) != hipSuccess) return bail(e, "hipMalloc");
+        if ((e = hipMemcpy(ctx->d_ing_tab, tab.data(), 512 * 8, hipMemcpyHostToDevice)) != hipSuccess)
+            return bail(e, "hipMemcpy");
+        if ((e = hipMalloc(&ctx->d_ing_verdict, sizeof(unsigned))) != hipSuccess) return bail(e, "hipMalloc");
+        if ((e = hipHostMalloc(&ctx->h_ing_verdict, sizeof(unsigned), hipHostMallocDefault)) != hipSuccess)
+            return bail(e, "hipHostMalloc");
+        for (hipEvent_t &ev : ctx->ev_ing)
+            if ((e = hipEventCreate(&ev)) != hipSuccess) return bail(e, "hipEventCreate");
+    }
     if (const char *t = std::getenv("QVQ_TIMEOUT_S")) ctx->timeout_s = std::max(0.001, std::atof(t));
     ctx->ev_ready = true;
     *out = ctx;
@@ -2437,6 +2460,11 @@ QVQ_API void qvq_destroy(qvq_ctx *ctx) {
             for (int j = 0; j < 4; j++) (void)hipEventDestroy(ctx->ev[l][j]);
     if (ctx->ev_end) (void)hipEventDestroy(ctx->ev_end);
     if (ctx->ev_sync) (void)hipEventDestroy(ctx->ev_sync);
+    dfree(ctx->d_ing_tab);
+    dfree(ctx->d_ing_verdict);
+    if (ctx->h_ing_verdict) (void)hipHostFree(ctx->h_ing_verdict);
+    for (hipEvent_t ev : ctx->ev_ing)
+        if (ev) (void)hipEventDestroy(ev);
     for (auto &v : ctx->ver)
         if (v.ev) (void)hipEventDestroy(v.ev);
     for (uint8_t *h : ctx->h_tx)
@@ -2511,69 +2539,78 @@ QVQ_API qvq_status qvq_set_synthetic(qvq_ctx *ctx, uint32_t S, uint64_t seed0, u
     return st;
 }
 
-QVQ_API qvq_status qvq_set_vectors(qvq_ctx *ctx, const double *X, uint64_t n, uint32_t dim) {
-    if (!ctx) return QVQ_EINVAL;
-    GUARD(ctx);
-    if (!X || n == 0 || dim == 0) return fail(ctx, QVQ_EINVAL, "empty training set");
-    if (dim > 64) return fail(ctx, QVQ_EINVAL, "block dimension above 64 (3*w*h) is not supported");
-    ctx->col_blocks = 0;   // rows without image geometry
-    // Recognise the colour space from the values: every value must be a byte's image
-    // under NORMAL or SCALED (0.0 included), so the exact sums apply.
-    int cs_found = -1;
-    std::vector<uint8_t> codes;
-    const uint32_t Dp = (dim + 3) & ~3u;
-    for (int cs : {QVQ_CS_SCALED, QVQ_CS_NORMAL}) {
-        Terms t;
-        make_terms(cs, t);
-        std::vector<std::pair<double, uint8_t>> inv;
-        for (int b = 0; b < 256; b++) inv.push_back({t.v64[b], (uint8_t)b});
-        std::sort(inv.begin(), inv.end());
-        codes.assign(n * Dp, t.pad_code);
-        bool ok = true;
-        for (uint64_t i = 0; i < n && ok; i++)
-            for (uint32_t d = 0; d < dim; d++) {
-                const double v = X[i * dim + d];
-                auto it = std::lower_bound(inv.begin(), inv.end(), std::make_pair(v, (uint8_t)0));
-                if (it == inv.end() || it->first != v || (v == 0.0 && std::signbit(v))) {   // -0.0 is no byte image
-                    ok = false;
-                    break;
-                }
-                codes[i * Dp + d] = it->second;
-            }
-        if (ok) {
-            cs_found = cs;
-            break;
+// ---------------------------------------------------------------------------------------
+// Training set, way 2: fp64 rows.  Which mode a set takes is decided by the rule of
+// byte_image.hpp over every value: SCALED if the whole set is SCALED-valid, otherwise NORMAL if
+// the whole set is NORMAL-valid, otherwise exact mode (k_exact.hip: any finite fp64 data, the
+// reference's arithmetic bit for bit -- fp64 search in nanoflann's order with kd-tree ties, Kahan
+// sums over each cell's rows in ascending order times fl(1/n), src/Quantizer.cpp:46-87; one rank,
+// host-driven levels).  The rule runs on the device (k_ingest.hip: classify, then pack; DESIGN.md
+// 3.12) over rows that are already there (qvq_set_vectors_device) or that the host entry points
+// upload once; the host form of the rule (host_classify) is the fallback when that upload's buffer
+// cannot be allocated, and qvq_host_classify.
+// ---------------------------------------------------------------------------------------
+
+// The rule over a host array: the colour space (-1: not a byte image), *finite = no Inf / NaN
+// (complete whenever the answer is -1), and the codes [n][Dp] (codes may be null) of a byte image.
+static int host_classify(const double *X, uint64_t n, uint32_t dim, uint8_t *codes, bool *finite) {
+    Terms ts, tn;
+    make_terms(QVQ_CS_SCALED, ts);
+    make_terms(QVQ_CS_NORMAL, tn);
+    bool sc = true, nm = true, fin = true;
+    const uint64_t total = n * dim;
+    for (uint64_t i = 0; i < total && (sc || nm || fin); i++) {
+        const double v = X[i];
+        sc = sc && byte_image_code(v, true, ts.v64) >= 0;
+        nm = nm && byte_image_code(v, false, tn.v64) >= 0;
+        fin = fin && f64_finite(v);
+    }
+    if (finite) *finite = fin;
+    const int cs = sc ? QVQ_CS_SCALED : nm ? QVQ_CS_NORMAL : -1;
+    if (cs >= 0 && codes) {
+        const Terms &t = sc ? ts : tn;
+        const uint32_t Dp = (dim + 3) & ~3u;
+        for (uint64_t i = 0; i < n; i++) {
+            for (uint32_t d = 0; d < dim; d++) codes[i * Dp + d] = (uint8_t)byte_image_code(X[i * dim + d], sc, t.v64);
+            for (uint32_t d = dim; d < Dp; d++) codes[i * Dp + d] = t.pad_code;
         }
     }
-    // other values (arbitrary fp64 data, CIE1931): the reference's own arithmetic (exact mode),
-    // one rank only -- with a communicator the ranks would disagree on the mode: fail fast here
-    // instead of at qvq_lbg, where peers would wait in the first all-reduce
-    if (cs_found < 0) {
-        if (ctx->comm || ctx->host_ar)
-            return fail(ctx, QVQ_EUNSUPPORTED, "values are not byte images (exact mode runs on one rank)");
-        return qvq_set_vectors_exact(ctx, X, n, dim);
-    }
-    HIPCHK(hipSetDevice(ctx->dev));
-    qvq_status st = alloc_training(ctx, n, dim, cs_found);
-    if (st != QVQ_OK) return st;
-    HIPCHK(hipMemcpy(ctx->d_codes, codes.data(), codes.size(), hipMemcpyHostToDevice));
-    return compute_xsq(ctx);
+    return cs;
 }
 
-// ---------------------------------------------------------------------------------------
-// Exact mode (k_exact.hip): any fp64 training set, the reference's arithmetic bit for bit --
-// fp64 search in nanoflann's order with kd-tree ties, Kahan sums over each cell's rows in
-// ascending order times fl(1/n) (src/Quantizer.cpp:46-87).  One rank; host-driven levels.
-// ---------------------------------------------------------------------------------------
-QVQ_API qvq_status qvq_set_vectors_exact(qvq_ctx *ctx, const double *X, uint64_t n, uint32_t dim) {
-    if (!ctx) return QVQ_EINVAL;
-    GUARD(ctx);
+// The checks every fp64 entry point makes before it touches a value.
+static qvq_status check_vector_args(qvq_ctx *ctx, const void *X, uint64_t n, uint32_t dim, bool exact) {
     if (!X || n == 0 || dim == 0) return fail(ctx, QVQ_EINVAL, "empty training set");
     if (dim > 64) return fail(ctx, QVQ_EINVAL, "block dimension above 64 (3*w*h) is not supported");
+    if (exact && n >= (1ull << 31)) return fail(ctx, QVQ_EINVAL, "exact mode: more than 2^31-1 rows");
+    if (n >= (1ull << 32)) return fail(ctx, QVQ_EINVAL, "more than 2^32-1 rows per rank");
+    return QVQ_OK;
+}
+
+// What a set that is no byte image (or is forced to exact mode) must pass, in this order, before the
+// resident set is touched.
+static qvq_status check_exact_set(qvq_ctx *ctx, uint64_t n, bool forced, bool finite) {
+    // one rank only -- with a communicator the ranks would disagree on the mode: fail fast here
+    // instead of at qvq_lbg, where peers would wait in the first all-reduce
+    if (!forced && (ctx->comm || ctx->host_ar))
+        return fail(ctx, QVQ_EUNSUPPORTED, "values are not byte images (exact mode runs on one rank)");
     if (n >= (1ull << 31)) return fail(ctx, QVQ_EINVAL, "exact mode: more than 2^31-1 rows");
-    for (uint64_t i = 0; i < n * dim; i++)
-        if (!std::isfinite(X[i])) return fail(ctx, QVQ_EINVAL, "exact mode: training values must be finite");
-    HIPCHK(hipSetDevice(ctx->dev));
+    if (!finite) return fail(ctx, QVQ_EINVAL, "exact mode: training values must be finite");
+    return QVQ_OK;
+}
+
+// A transient device buffer, freed on every way out unless it was handed on.
+struct DevRows {
+    double *p = nullptr;
+    ~DevRows() {
+        if (p) (void)hipFree(p);
+    }
+};
+
+// The exact-mode set: src's rows (kind: from the host, or from the device on the context's stream)
+// copied into the engine's own d_X64, or *adopt (an upload of the engine's own) taken over as it is.
+static qvq_status install_exact(qvq_ctx *ctx, const double *src, hipMemcpyKind kind, double **adopt, uint64_t n,
+                                uint32_t dim) {
     ctx->rf = qvq_ctx::RefineState();
     free_training(ctx);
     free_levels(ctx);
@@ -2582,7 +2619,12 @@ QVQ_API qvq_status qvq_set_vectors_exact(qvq_ctx *ctx, const double *X, uint64_t
     ctx->Dp = (dim + 3) & ~3u;
     ctx->cs = -1;
     ctx->exact = true;
-    HIPCHK(hipMalloc(&ctx->d_X64, n * dim * 8));
+    if (adopt) {
+        ctx->d_X64 = *adopt;
+        *adopt = nullptr;
+    } else {
+        HIPCHK(hipMalloc(&ctx->d_X64, n * dim * 8));
+    }
     HIPCHK(hipMalloc(&ctx->d_A, n * 4));
     HIPCHK(hipMalloc(&ctx->d_ties, n * 4));
     HIPCHK(hipMalloc(&ctx->d_ex_keys, n * 4));
@@ -2590,12 +2632,132 @@ QVQ_API qvq_status qvq_set_vectors_exact(qvq_ctx *ctx, const double *X, uint64_t
     HIPCHK(hipMalloc(&ctx->d_ex_order, n * 4));
     ctx->ex_temp_bytes = exact_sort_temp_bytes(n);
     HIPCHK(hipMalloc(&ctx->d_ex_temp, std::max<size_t>(ctx->ex_temp_bytes, 16)));
-    HIPCHK(hipMemcpy(ctx->d_X64, X, n * dim * 8, hipMemcpyHostToDevice));
+    if (!adopt) HIPCHK(hipMemcpyAsync(ctx->d_X64, src, n * dim * 8, kind, ctx->stream));
     HIPCHK(launch_exact_iota(ctx->stream, ctx->d_ex_iota, n));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return QVQ_OK;
 }
 
+// The training set from fp64 rows dX [n][dim] that the context's stream may read: classify, then
+// pack under the space found or install the rows as the exact-mode set.  adopt: dX is *adopt, the
+// engine's own upload, which exact mode keeps.  Returns with the stream drained.
+static qvq_status ingest_rows(qvq_ctx *ctx, const double *dX, uint64_t n, uint32_t dim, bool force_exact,
+                              double **adopt) {
+    const bool timed = ctx->timing_level == -3;   // events around the two passes (qvq_get_ingest_ms)
+    ctx->ingest_ms[0] = ctx->ingest_ms[1] = 0;
+    if (timed) HIPCHK(hipEventRecord(ctx->ev_ing[0], ctx->stream));
+    HIPCHK(launch_ingest_classify(ctx->stream, dX, n, dim, ctx->d_ing_tab, ctx->d_ing_verdict));
+    if (timed) HIPCHK(hipEventRecord(ctx->ev_ing[1], ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->h_ing_verdict, ctx->d_ing_verdict, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    const unsigned v = *ctx->h_ing_verdict;
+    float ms = 0;
+    if (timed && hipEventElapsedTime(&ms, ctx->ev_ing[0], ctx->ev_ing[1]) == hipSuccess) ctx->ingest_ms[0] = ms;
+    const int cs = force_exact ? -1 : (v & ING_SCALED_OK) ? QVQ_CS_SCALED : (v & ING_NORMAL_OK) ? QVQ_CS_NORMAL : -1;
+    qvq_status st;
+    if (cs < 0) {
+        if ((st = check_exact_set(ctx, n, force_exact, (v & ING_FINITE) != 0)) != QVQ_OK) return st;
+        return install_exact(ctx, dX, hipMemcpyDeviceToDevice, adopt, n, dim);
+    }
+    ctx->col_blocks = 0;   // rows without image geometry
+    // (the same shape again keeps every buffer; the pack below refills d_codes either way)
+    if ((st = alloc_training(ctx, n, dim, cs)) != QVQ_OK) return st;
+    if (timed) HIPCHK(hipEventRecord(ctx->ev_ing[1], ctx->stream));
+    HIPCHK(launch_ingest_pack(ctx->stream, dX, n, dim, (uint32_t)cs, ctx->d_ing_tab, ctx->d_codes));
+    if (timed) HIPCHK(hipEventRecord(ctx->ev_ing[2], ctx->stream));
+    if ((st = compute_xsq(ctx)) != QVQ_OK) return st;
+    if (timed && hipEventElapsedTime(&ms, ctx->ev_ing[1], ctx->ev_ing[2]) == hipSuccess) ctx->ingest_ms[1] = ms;
+    return QVQ_OK;
+}
+
+// The same from a host array without the transient upload (its allocation failed): the host form
+// of the rule, then the codes' or the rows' upload.
+static qvq_status ingest_host_rule(qvq_ctx *ctx, const double *X, uint64_t n, uint32_t dim, bool force_exact) {
+    ctx->ingest_ms[0] = ctx->ingest_ms[1] = 0;
+    const uint32_t Dp = (dim + 3) & ~3u;
+    std::vector<uint8_t> codes;
+    if (!force_exact) codes.resize(n * Dp);
+    bool finite = true;
+    int cs = -1;
+    if (force_exact)
+        for (uint64_t i = 0; i < n * dim && finite; i++) finite = f64_finite(X[i]);
+    else
+        cs = host_classify(X, n, dim, codes.data(), &finite);
+    qvq_status st;
+    if (cs < 0) {
+        if ((st = check_exact_set(ctx, n, force_exact, finite)) != QVQ_OK) return st;
+        return install_exact(ctx, X, hipMemcpyHostToDevice, nullptr, n, dim);
+    }
+    ctx->col_blocks = 0;
+    if ((st = alloc_training(ctx, n, dim, cs)) != QVQ_OK) return st;
+    HIPCHK(hipMemcpy(ctx->d_codes, codes.data(), codes.size(), hipMemcpyHostToDevice));
+    return compute_xsq(ctx);
+}
+
+static qvq_status set_vectors_host(qvq_ctx *ctx, const double *X, uint64_t n, uint32_t dim, bool force_exact) {
+    if (!ctx) return QVQ_EINVAL;
+    GUARD(ctx);
+    qvq_status st = check_vector_args(ctx, X, n, dim, force_exact);
+    if (st != QVQ_OK) return st;
+    HIPCHK(hipSetDevice(ctx->dev));
+    // one upload into a transient buffer: the pass reads it, exact mode keeps it as d_X64
+    DevRows rows;
+    if (hipMalloc(&rows.p, n * dim * 8) != hipSuccess) {
+        (void)hipGetLastError();
+        rows.p = nullptr;
+        return ingest_host_rule(ctx, X, n, dim, force_exact);
+    }
+    HIPCHK(hipMemcpyAsync(rows.p, X, n * dim * 8, hipMemcpyHostToDevice, ctx->stream));
+    return ingest_rows(ctx, rows.p, n, dim, force_exact, &rows.p);
+}
+
+QVQ_API qvq_status qvq_set_vectors(qvq_ctx *ctx, const double *X, uint64_t n, uint32_t dim) {
+    return set_vectors_host(ctx, X, n, dim, false);
+}
+
+QVQ_API qvq_status qvq_set_vectors_exact(qvq_ctx *ctx, const double *X, uint64_t n, uint32_t dim) {
+    return set_vectors_host(ctx, X, n, dim, true);
+}
+
+QVQ_API qvq_status qvq_set_vectors_device(qvq_ctx *ctx, const void *d_X, uint64_t n, uint32_t dim, uint32_t flags,
+                                          void *stream) {
+    if (!ctx) return QVQ_EINVAL;
+    GUARD(ctx);
+    if (flags & ~(uint32_t)QVQ_VECTORS_EXACT) return fail(ctx, QVQ_EINVAL, "unknown flags");
+    const bool force_exact = (flags & QVQ_VECTORS_EXACT) != 0;
+    qvq_status st = check_vector_args(ctx, d_X, n, dim, force_exact);
+    if (st != QVQ_OK) return st;
+    if ((uintptr_t)d_X % 8) return fail(ctx, QVQ_EINVAL, "rows not 8-byte aligned");
+    HIPCHK(hipSetDevice(ctx->dev));
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, d_X) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != ctx->dev) {
+        (void)hipGetLastError();
+        return fail(ctx, QVQ_EINVAL, "rows are not device memory on the context's GPU");
+    }
+    // ordered after the work that produces the rows: the engine's stream waits for what the
+    // caller's stream holds now (the mirror image of qvq_decode_device)
+    HIPCHK(hipEventRecord(ctx->ev_sync, (hipStream_t)stream));
+    HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_sync, 0));
+    return ingest_rows(ctx, (const double *)d_X, n, dim, force_exact, nullptr);
+}
+
+QVQ_API qvq_status qvq_get_training_info(const qvq_ctx *ctx, qvq_training_info *out) {
+    if (!ctx || !out) return QVQ_EINVAL;
+    out->mode = ctx->exact ? 2u : ctx->d_codes ? 1u : 0u;
+    out->colorspace = out->mode == 1 ? ctx->cs : -1;
+    out->n = ctx->N;
+    out->dim = ctx->D;
+    return QVQ_OK;
+}
+
+QVQ_API qvq_status qvq_get_ingest_ms(const qvq_ctx *ctx, double ms[2]) {
+    if (!ctx || !ms) return QVQ_EINVAL;
+    ms[0] = ctx->ingest_ms[0];
+    ms[1] = ctx->ingest_ms[1];
+    return QVQ_OK;
+}
+
+// Exact mode's host-driven levels (k_exact.hip) ---------------------------------------------
 namespace {
 
 qvq_status exact_single_rank(qvq_ctx *ctx) {
@@ -3809,6 +3971,27 @@ QVQ_API qvq_status qvq_host_exact_grids(qvq_exact_grids *out) {
     out->assign_blocks = EX_ASSIGN_GRID_CAP;
     out->iota_blocks = EX_IOTA_GRID_CAP;
     out->dist_blocks = EX_DIST_GRID_CAP;
+    return QVQ_OK;
+}
+
+QVQ_API qvq_status qvq_host_ingest_grid(qvq_ingest_grid *out) {
+    if (!out) return QVQ_EINVAL;
+    out->block = ING_THREADS;
+    out->blocks = ING_GRID_CAP;
+    return QVQ_OK;
+}
+
+QVQ_API qvq_status qvq_host_colorspace_values(int colorspace, double out[256]) {
+    Terms t;
+    if (!out) return QVQ_EINVAL;
+    if (!make_terms(colorspace, t)) return QVQ_EUNSUPPORTED;
+    std::memcpy(out, t.v64, sizeof(t.v64));
+    return QVQ_OK;
+}
+
+QVQ_API qvq_status qvq_host_classify(const double *X, uint64_t n, uint32_t dim, int32_t *colorspace, uint8_t *codes) {
+    if (!X || !colorspace || n == 0 || dim == 0 || dim > 64) return QVQ_EINVAL;
+    *colorspace = host_classify(X, n, dim, codes, nullptr);
     return QVQ_OK;
 }
 
