@@ -38,8 +38,14 @@ constexpr int M32_WAVES = M32_THREADS / 64;
 constexpr int M32_ROWS = 64;        // rows per wave and chunk: two 32-row data tiles
 constexpr uint32_t M32_LDS_MAX = 160 * 1024;
 
+// A workgroup's flagged rows kept in LDS: what the layout leaves, up to this (0: none; A/B builds)
+#ifndef QVQ_M32_FLAG_CAP
+#define QVQ_M32_FLAG_CAP 384
+#endif
+constexpr uint32_t M32_FLAG_CAP = QVQ_M32_FLAG_CAP;
+
 struct M32Lds {
-    uint32_t q, c32, sums, cnt, perm, plut, total;
+    uint32_t q, c32, sums, cnt, perm, plut, flist, fcap, total;
 };
 // Sums copies (fused, copies > 1): strides one u64 / u32 past K * D / K, so the copies of one
 // (component, code vector) fall on different LDS banks (a 256-byte multiple put them all on
@@ -70,6 +76,13 @@ __host__ __device__ inline M32Lds m32_lds_layout(uint32_t K, bool fuse, bool sta
     L.perm = o;   // pruned searches: the code vector at each tile position (u16)
     if (prune) o += ((Kp * 2 + 7) & ~7u);
     L.plut = 0;
+    // the workgroup's flagged rows (flag_list_add): 8 bytes and up to M32_FLAG_CAP rows in
+    // whatever is left; under 32 rows' room none (every flagged row goes to the global list).
+    // Never the reason a layout does not fit: total <= M32_LDS_MAX exactly when o is.
+    L.flist = o;
+    const uint32_t room = o + 8 < M32_LDS_MAX ? (M32_LDS_MAX - o - 8) / 4 : 0;
+    L.fcap = room >= 32 ? (room < M32_FLAG_CAP ? room : M32_FLAG_CAP) : 0;
+    if (L.fcap) o += 8 + 4 * L.fcap;
     L.total = o;
     return L;
 }
@@ -139,6 +152,7 @@ __global__ __launch_bounds__(M32_THREADS) void assign_mf32_kernel(
     float *c32s = reinterpret_cast<float *>(lds + L.c32);
     uint64_t *sums = reinterpret_cast<uint64_t *>(lds + L.sums);   // [d][k]
     uint32_t *cnt = reinterpret_cast<uint32_t *>(lds + L.cnt);
+    uint32_t *fl = reinterpret_cast<uint32_t *>(lds + L.flist);   // the flagged rows' list (flag_list_add)
     uint8_t *lo8 = lds + L.plut;   // low part of each byte's exact term (high part: b ^ 0x80)
     // The same table addressed as LDS byte 0 (the kernel has no static LDS, so the dynamic
     // block starts there): lookups take the byte as their address.
@@ -174,6 +188,7 @@ __global__ __launch_bounds__(M32_THREADS) void assign_mf32_kernel(
         float4 *dst = reinterpret_cast<float4 *>(c32s);
         for (uint32_t i = tid; i < Kp * (MF_D / 4); i += M32_THREADS) dst[i] = src[i];
     }
+    if (tid == 0) fl[0] = 0;
     if (FUSE) {
         for (uint32_t i = tid; i < copies * m32_sum_stride(K, copies); i += M32_THREADS) sums[i] = 0;
         for (uint32_t i = tid; i < copies * m32_cnt_stride(K, copies); i += M32_THREADS) cnt[i] = 0;
@@ -379,6 +394,7 @@ __global__ __launch_bounds__(M32_THREADS) void assign_mf32_kernel(
         const uint64_t row = base + lane;
         const bool valid = row < N;
         uint32_t rk = 0;
+        bool flagged = false;
         if (valid) {
             // x_d = mu + w_d sx = (mu - 255 sx) + u_d (2 sx) in one fma from the centred byte u,
             // and ||x - mu||^2 = sx^2 sum_d w_d^2 from the exact integer sum (v_sad_u8 / v_dot4:
@@ -436,8 +452,9 @@ __global__ __launch_bounds__(M32_THREADS) void assign_mf32_kernel(
             // orrel / 2 relative, in distance units |sec_m| 2^-t
             if (TAG) thr = __fmaf_rn(orrel * th.inv_scale, fabsf(sec_m), thr);
             A[row] = rk;
-            if (!(sec - r1 > thr)) flags[atomicAdd(flag_cnt, 1u)] = (uint32_t)row;
+            flagged = !(sec - r1 > thr);
         }
+        flag_list_add(flagged, (uint32_t)row, lane, fl, L.fcap, flags, flag_cnt);   // (mfma_util.hpp)
         if (FUSE) {
             // every row at its provisional index; the recheck / kd-tree move re-assigned ones
             if constexpr (STAG) {
@@ -473,8 +490,9 @@ __global__ __launch_bounds__(M32_THREADS) void assign_mf32_kernel(
             }
         }
     }
+    __syncthreads();
+    flag_list_flush(fl, L.fcap, tid, M32_THREADS, flags, flag_cnt);
     if (FUSE) {
-        __syncthreads();
         uint64_t *pdst = part + (uint64_t)blockIdx.x * K * MF_D;   // slab layout [d][k]
         for (uint32_t i = tid; i < K * MF_D; i += M32_THREADS) {
             const uint32_t d = i / K, j = d * m32_kstride(K) + (i - d * K);

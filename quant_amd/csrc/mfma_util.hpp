@@ -197,4 +197,40 @@ __device__ inline void pair_update2(const f32x4 &p0, const f32x4 &p1, uint32_t p
     b1 = min2f(b1, m);
 }
 
+// A workgroup's flagged rows, kept in LDS and appended to the global list with one add per
+// workgroup.  fl (LDS, 8 + 4 cap bytes): [0] rows listed so far (cleared before the first call,
+// behind a barrier), [1] scratch, [2 ..] cap rows.  A returning device-scope atomic per flagged
+// row, all on one counter, parked the row's wave for its round trip behind every other
+// workgroup's adds (C3, K = 64: 7,478 rows, 28 us of the launch's 88).  Rows past the list's end
+// still go that way.  The global list's order was and is arbitrary: the rechecks' sums are
+// integer adds and their tie lists are appended the same way.
+// flag_list_add: every lane of the wave calls it; one LDS add per wave with flagged rows, and a
+// wave without any passes on a scalar branch.
+__device__ inline void flag_list_add(bool flagged, uint32_t row, int lane, uint32_t *fl, uint32_t cap,
+                                     uint32_t *__restrict__ flags, unsigned *__restrict__ flag_cnt) {
+    const uint64_t fm = __ballot(flagged);
+    if (!fm) return;
+    uint32_t at = 0;
+    if (cap) {
+        const int first = __ffsll((unsigned long long)fm) - 1;
+        if (lane == first) at = atomicAdd(&fl[0], (uint32_t)__popcll(fm));
+        at = (uint32_t)__builtin_amdgcn_readlane((int)at, first);
+        at += __builtin_amdgcn_mbcnt_hi((uint32_t)(fm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)fm, 0u));
+    }
+    if (flagged) {
+        if (at < cap) fl[2 + at] = row;
+        else flags[atomicAdd(flag_cnt, 1u)] = row;
+    }
+}
+// flag_list_flush: every thread of the workgroup calls it, behind a barrier after the last add.
+__device__ inline void flag_list_flush(uint32_t *fl, uint32_t cap, uint32_t tid, uint32_t nthreads,
+                                       uint32_t *__restrict__ flags, unsigned *__restrict__ flag_cnt) {
+    const uint32_t n = cap ? min(fl[0], cap) : 0;
+    if (!n) return;   // (the same in every thread)
+    if (tid == 0) fl[1] = atomicAdd(flag_cnt, n);
+    __syncthreads();
+    const uint32_t at = fl[1];
+    for (uint32_t i = tid; i < n; i += nthreads) flags[at + i] = fl[2 + i];
+}
+
 }  // namespace qvq
