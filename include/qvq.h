@@ -46,8 +46,9 @@ typedef enum {
 } qvq_status;
 
 /* Colour spaces, numbered as the reference's enum class ColorSpaces
- * (include/ColorSpace.hpp:6).  Only NORMAL and SCALED map bytes to values the engine
- * can sum exactly; CIE1931 is rejected with QVQ_EUNSUPPORTED. */
+ * (include/ColorSpace.hpp:6).  NORMAL and SCALED map bytes to values the engine can sum
+ * exactly: their rasters take the byte path.  CIE1931 values are not byte images: a
+ * CIE1931 raster becomes an exact-mode training set (qvq_set_images). */
 enum { QVQ_CS_NORMAL = 0, QVQ_CS_SCALED = 1, QVQ_CS_CIE1931 = 2 };
 
 /* Per-level / per-call timings filled by qvq_get_timings (device ms from HIP events
@@ -83,6 +84,20 @@ QVQ_API const char *qvq_version(void);
  * (src/Compressor.cpp:31-62): the raster is read as xSize rows of ySize pixels, columns
  * past ySize wrap into the next row, components past the end of the buffer are 0.
  * Blocks of image i follow all blocks of image i-1.
+ *
+ * QVQ_CS_NORMAL and QVQ_CS_SCALED give a byte-path set.  QVQ_CS_CIE1931 gives an exact-mode set
+ * (qvq_set_vectors_exact: the reference's arithmetic bit for bit, one rank, qvq_refine
+ * unsupported): the bytes are uploaded (or generated) as for the other two, then one kernel tiles
+ * them and maps each pixel's three signed bytes r, g, b to
+ *   X = ((r*0.490 + g*0.310) + b*0.200) / 0.17697
+ *   Y = ((r*0.17697 + g*0.81240) + b*0.01063) / 0.17697
+ *   Z = ((r*0 + g*0.01) + b*0.99) / 0.17697
+ * (the reference's Cie1931::RGBtoColorSpace, src/ColorSpace.cpp:30-33: every product and sum
+ * rounded on its own, a true fp64 division; qvq_host_cie1931 is the same function on the host)
+ * straight into the fp64 rows [N][3*bw*bh]; an entry past the end of its image's buffer is three
+ * +0.0.  After the image arguments' own checks a CIE1931 call fails, in this order and before the
+ * resident set is touched, with QVQ_EINVAL for 3*bw*bh > 64, QVQ_EUNSUPPORTED with a communicator
+ * joined (exact mode is one rank), QVQ_EINVAL for 2^31 rows or more; the resident set stays usable.
  */
 QVQ_API qvq_status qvq_set_images(qvq_ctx *ctx, const uint8_t *rgb, uint32_t n_images, uint32_t xSize,
                                   uint32_t ySize, uint32_t bw, uint32_t bh, int colorspace);
@@ -138,14 +153,23 @@ QVQ_API qvq_status qvq_set_vectors_device(qvq_ctx *ctx, const void *d_X, uint64_
 /* What is resident: the mode the last qvq_set_* call chose, its colour space and shape. */
 typedef struct {
     uint32_t mode;        /* 0 none, 1 byte path, 2 exact mode */
-    int32_t colorspace;   /* QVQ_CS_*; -1 in exact mode or none */
+    int32_t colorspace;   /* byte path: QVQ_CS_NORMAL / _SCALED; exact mode: QVQ_CS_CIE1931 for a set that
+                             came from a CIE1931 raster, -1 for one from qvq_set_vectors*; -1 for none */
     uint64_t n;
     uint32_t dim;
 } qvq_training_info;
 QVQ_API qvq_status qvq_get_training_info(const qvq_ctx *ctx, qvq_training_info *out);
 /* Device ms of the last qvq_set_vectors* call's two passes over the rows, [0] classify and [1] pack
- * (0 in exact mode), from HIP events under qvq_set_timing(-3); 0 otherwise. */
+ * (0 in exact mode), from HIP events under qvq_set_timing(-3); 0 otherwise.  After a CIE1931
+ * qvq_set_images* / qvq_set_synthetic call: [0] = 0, [1] = the tile-to-fp64 kernel. */
 QVQ_API qvq_status qvq_get_ingest_ms(const qvq_ctx *ctx, double ms[2]);
+/* Read back the resident training set: rows row0 .. row0 + nrows - 1 as fp64 [nrows][dim] into out
+ * (host memory).  Exact mode: the rows themselves.  Byte path: the value of each row's dim real
+ * components under the set's colour space (qvq_host_colorspace_values[code]); pad bytes are not
+ * returned.  QVQ_ESTATE with no training set; QVQ_EINVAL for nrows == 0, a range that leaves
+ * [0, qvq_num_vectors) or a null out.  Copied through the context's stream under the bounded wait
+ * (qvq_set_timeout): out is written only after a wait has succeeded.  Changes nothing resident. */
+QVQ_API qvq_status qvq_get_vectors(qvq_ctx *ctx, uint64_t row0, uint64_t nrows, double *out);
 
 QVQ_API uint64_t qvq_num_vectors(const qvq_ctx *ctx);
 QVQ_API uint32_t qvq_dim(const qvq_ctx *ctx);
@@ -199,8 +223,8 @@ QVQ_API const uint32_t *qvq_assign_device(const qvq_ctx *ctx);
  * Outputs (caller-owned host memory, any may be NULL): codebook K x dim, assign n u32, distortion,
  * changed and dist_trace (max_iters entries each, the first info->iters written), info.
  * qvq_assign_device points at the returned assignment.  A later qvq_lbg on the context gives
- * exactly what it gave before.  Exact mode (qvq_set_vectors_exact, or its fallback inside
- * qvq_set_vectors) returns QVQ_EUNSUPPORTED.
+ * exactly what it gave before.  Exact mode (qvq_set_vectors_exact, its fallback inside
+ * qvq_set_vectors, or a CIE1931 raster) returns QVQ_EUNSUPPORTED.
  *
  * With a communicator (qvq_comm_init or qvq_comm_init_host, any nranks >= 1) every rank calls this
  * on its own rows -- consecutive ranges of the global rows, rank 0 first, as for qvq_lbg -- with
@@ -392,6 +416,15 @@ QVQ_API qvq_status qvq_host_classify(const double *X, uint64_t n, uint32_t dim, 
  * grid-stride loop a second time. */
 typedef struct { uint32_t block, blocks; } qvq_ingest_grid;
 QVQ_API qvq_status qvq_host_ingest_grid(qvq_ingest_grid *out);
+/* The CIE1931 map of qvq_set_images on the host (quant_amd/csrc/cie1931.hpp, the function the
+ * tile-to-fp64 kernel and the C++ layer's Cie1931 colour space apply): out [npix][3] = X, Y, Z of
+ * rgb [npix][3], the bytes read as signed chars. */
+QVQ_API qvq_status qvq_host_cie1931(const uint8_t *rgb, uint64_t npix, double *out);
+/* The tile-to-fp64 kernel's launch shape: one lane per (row, pixel in block) slot, n * bw * bh slots,
+ * `block` lanes per block, at most `blocks` blocks: more than block * blocks slots take the kernel's
+ * grid-stride loop a second time.  One kernel serves every block shape. */
+typedef struct { uint32_t block, blocks; } qvq_tile64_grid;
+QVQ_API qvq_status qvq_host_tile64_grid(qvq_tile64_grid *out);
 /* The engine's bounded-wait policy (quant_amd/csrc/wait.hpp) driven by scripted probes, for
  * tests: scenario 0 the work publishes after ~5 ms; 1 it never does, no communicator; 2 it
  * never does, a healthy communicator; 3 the communicator reports an error after ~5 ms; 4 the

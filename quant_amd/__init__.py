@@ -74,7 +74,8 @@ EXPORTED = ["qvq_create", "qvq_destroy", "qvq_last_error", "qvq_version", "qvq_s
             "qvq_update_kahan_split", "qvq_host_pool_stress", "qvq_kdtree_device_check",
             "qvq_host_kdtree_image", "qvq_refine", "qvq_host_plan", "qvq_host_exact_plan",
             "qvq_host_exact_grids", "qvq_set_vectors_device", "qvq_get_training_info", "qvq_get_ingest_ms",
-            "qvq_host_colorspace_values", "qvq_host_classify", "qvq_host_ingest_grid"]
+            "qvq_host_colorspace_values", "qvq_host_classify", "qvq_host_ingest_grid", "qvq_get_vectors",
+            "qvq_host_cie1931", "qvq_host_tile64_grid"]
 
 COMM_NONE, COMM_RCCL, COMM_HOST = 0, 1, 2
 REFINE_FRESH = 1                              # qvq_refine flags
@@ -138,6 +139,9 @@ def lib():
             "qvq_host_colorspace_values": ([i, P], i),
             "qvq_host_classify": ([P, u64, u32, ctypes.POINTER(ctypes.c_int32), P], i),
             "qvq_host_ingest_grid": ([ctypes.POINTER(_IngestGrid)], i),
+            "qvq_get_vectors": ([P, u64, u64, P], i),
+            "qvq_host_cie1931": ([P, u64, P], i),
+            "qvq_host_tile64_grid": ([ctypes.POINTER(_IngestGrid)], i),   # qvq_tile64_grid: the same two fields
         }
         for name, (args, res) in sig.items():
             if os.environ.get("QVQ_LIB") and not hasattr(L, name):
@@ -246,10 +250,22 @@ class Engine:
 
     def training_info(self):
         """What is resident (qvq_get_training_info): {"mode": MODE_NONE / MODE_BYTE / MODE_EXACT,
-        "colorspace": NORMAL / SCALED, or -1 in exact mode or none, "n", "dim"}."""
+        "colorspace": NORMAL / SCALED on the byte path, CIE1931 for an exact set from a CIE1931
+        raster, -1 for one from set_vectors or none, "n", "dim"}."""
         t = _TrainingInfo()
         _check(lib().qvq_get_training_info(self._h, ctypes.byref(t)), self._h)
         return {"mode": int(t.mode), "colorspace": int(t.colorspace), "n": int(t.n), "dim": int(t.dim)}
+
+    def get_vectors(self, row0=0, nrows=None):
+        """The resident rows row0 .. row0 + nrows - 1 (default: to the end) as float64 [nrows, dim]
+        (qvq_get_vectors): exact mode's rows themselves, the byte path's values without padding."""
+        row0 = int(row0)
+        nrows = self.n - row0 if nrows is None else int(nrows)
+        if row0 < 0 or nrows < 0:
+            raise QVQError(1, "rows outside the training set")
+        out = np.empty((nrows, self.dim), np.float64)
+        _check(lib().qvq_get_vectors(self._h, row0, nrows, _p(out)), self._h)
+        return out
 
     def ingest_ms(self):
         """(classify ms, pack ms) of the last set_vectors* call's device passes, under set_timing(-3)."""
@@ -489,6 +505,23 @@ def host_ingest_grid():
     g = _IngestGrid()
     _check(lib().qvq_host_ingest_grid(ctypes.byref(g)))
     return {f: int(getattr(g, f)) for f, _ in _IngestGrid._fields_}
+
+
+def host_tile64_grid():
+    """The tile-to-fp64 kernel's launch shape (qvq_host_tile64_grid): {"block", "blocks"}; one lane per
+    (row, pixel in block) slot."""
+    g = _IngestGrid()
+    _check(lib().qvq_host_tile64_grid(ctypes.byref(g)))
+    return {f: int(getattr(g, f)) for f, _ in _IngestGrid._fields_}
+
+
+def host_cie1931(rgb):
+    """The CIE1931 map of set_images on the host (qvq_host_cie1931): rgb [..., 3] uint8 (read as signed
+    chars) -> float64 [npix, 3]."""
+    rgb = np.ascontiguousarray(rgb, np.uint8).reshape(-1, 3)
+    out = np.empty((rgb.shape[0], 3), np.float64)
+    _check(lib().qvq_host_cie1931(_p(rgb), rgb.shape[0], _p(out)))
+    return out
 
 
 def colorspace_values(colorspace=SCALED):

@@ -4,6 +4,8 @@
 #include <cmath>
 #include <cstdint>
 
+#include "cie1931.hpp"
+
 namespace {
 
 // The reference converts the rounded double straight to char; on its x86 builds that keeps
@@ -26,10 +28,11 @@ public:
 
 class Cie1931Space : public ColorSpace {
 public:
+    // the one statement of the map (quant_amd/csrc/cie1931.hpp), shared with the device kernel
     RGBDouble RGBtoColorSpace(const RGB &c) override {
-        const double r = c[0], g = c[1], b = c[2], n = 0.17697;
-        return {(r * 0.490 + g * 0.310 + b * 0.200) / n, (r * 0.17697 + g * 0.81240 + b * 0.01063) / n,
-                (r * 0 + g * 0.01 + b * 0.99) / n};
+        double v[3];
+        qvq::cie1931_from_rgb((signed char)c[0], (signed char)c[1], (signed char)c[2], v);
+        return {v[0], v[1], v[2]};
     }
     RGB colorSpaceToRGB(const RGBDouble &c) override {
         const double r = c[0] * 0.418 + c[1] * (-0.15866) + c[2] * (-0.082835);

@@ -85,7 +85,12 @@ size_t floor_log2(size_t n) {   // smallestPow2, src/Compressor.cpp:167-172
     return p;
 }
 
-bool engine_sums_exactly(ColorSpaces cs) { return cs == ColorSpaces::NORMAL || cs == ColorSpaces::SCALED; }
+// Colour spaces whose rasters qvq_set_images takes: NORMAL and SCALED on the byte path, CIE1931 as
+// an exact-mode set (tiled and converted on the device; the reference's own centroid bits, so no
+// Kahan substitution).  Exact mode has no qvq_refine: a refined quantizer keeps the host-built vectors.
+bool engine_takes_raster(ColorSpaces cs, bool refined) {
+    return cs == ColorSpaces::NORMAL || cs == ColorSpaces::SCALED || (cs == ColorSpaces::CIE1931 && !refined);
+}
 
 // The SCALED byte of one centroid component (ScaledColor::colorSpaceToRGB, src/ColorSpace.cpp:23-28).
 int scaled_byte(double c) { return (int)std::round((c - 128.0) * 255); }
@@ -180,7 +185,7 @@ std::pair<CompressedImage, CompressionRaport> CompressedImage::compress(const RG
     std::vector<size_t> assigned;
     VectorType distortion = 0;
     const auto t0 = std::chrono::system_clock::now();
-    if (quantizer == Quantizers::LBG && engine_sums_exactly(colorSpace)) {
+    if (quantizer == Quantizers::LBG && engine_takes_raster(colorSpace, false)) {
         std::tie(codebook, assigned, distortion) = quantize_raster(image, colorSpace, blockWidth, blockHeight, eps, N);
     } else {
         QuantizerPtr q = getQuantizer(quantizer);
@@ -207,7 +212,8 @@ std::pair<CompressedImage, CompressionRaport> CompressedImage::compress(const RG
     VectorType distortion = 0;
     const auto t0 = std::chrono::system_clock::now();
     quant_amd::RefineOptions opt;
-    if (quant_amd::engine_lbg_options(quantizer, opt) && engine_sums_exactly(colorSpace)) {
+    if (quant_amd::engine_lbg_options(quantizer, opt) &&
+        engine_takes_raster(colorSpace, opt.maxIters > 0 || opt.fresh)) {
         std::tie(codebook, assigned, distortion) =
             quantize_raster(image, colorSpace, blockWidth, blockHeight, eps, N, opt);
     } else {

@@ -446,6 +446,17 @@ hipError_t launch_ingest_classify(hipStream_t s, const double *X, uint64_t n, ui
                                   unsigned *verdict);
 hipError_t launch_ingest_pack(hipStream_t s, const double *X, uint64_t n, uint32_t dim, uint32_t cs, const double *tab,
                               uint8_t *codes);
+// Rasters to exact mode's rows (k_tile64.hip, cie1931.hpp): launch_tile's tiling of n_images rasters,
+// each pixel through the CIE1931 map, into X [N][3 * bw * bh] fp64 without padding.  One lane per
+// (row, pixel in block) slot, T64_THREADS lanes per block, at most T64_GRID_CAP blocks (more slots:
+// the grid-stride loop again).
+constexpr int T64_THREADS = 256;
+constexpr int T64_GRID_CAP = 2048;
+hipError_t launch_tile64(hipStream_t s, const uint8_t *rgb, double *X, uint32_t n_images, uint32_t xSize,
+                         uint32_t ySize, uint32_t bw, uint32_t bh);
+// out [nrows][D] fp64 = lut64[code] of the first D bytes of rows row0 .. row0 + nrows - 1 of codes [.][Dp].
+hipError_t launch_rows_f64(hipStream_t s, const uint8_t *codes, uint32_t Dp, uint32_t D, uint64_t row0, uint64_t nrows,
+                           const double *lut64, double *out);
 // Exact mode (k_exact.hip): fp64 rows X [N][D].
 hipError_t launch_exact_assign(hipStream_t s, const double *X, uint64_t N, uint32_t D, const double *C, uint32_t K,
                                double tie_rel, uint32_t *A, uint32_t *ties, unsigned *tie_cnt);

@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "byte_image.hpp"
+#include "cie1931.hpp"
 #include "common.hpp"
 #include "exact_plan.hpp"
 #include "kdtree.hpp"
@@ -155,6 +156,7 @@ struct qvq_ctx {
     // exact mode (qvq_set_vectors_exact, or qvq_set_vectors on values that are not byte images):
     // the fp64 rows themselves and the reference's Kahan arithmetic (k_exact.hip)
     bool exact = false;
+    int exact_cs = -1;   // the colour space whose raster the exact rows came from (QVQ_CS_CIE1931), -1: fp64 rows
     double *d_X64 = nullptr;
     uint32_t *d_ex_keys = nullptr, *d_ex_iota = nullptr, *d_ex_order = nullptr;
     void *d_ex_temp = nullptr;
@@ -210,7 +212,7 @@ struct qvq_ctx {
     uint64_t scatter_bytes = 0;
     uint8_t *d_raster = nullptr;          // qvq_set_images' raster upload buffer (grown on demand)
     uint64_t raster_bytes = 0;
-    uint8_t *d_decode = nullptr;          // qvq_decode scratch (grown on demand)
+    uint8_t *d_decode = nullptr;          // qvq_decode's and qvq_get_vectors' scratch (grown on demand)
     uint64_t decode_bytes = 0;
     uint64_t *d_decode_stat = nullptr;    // decode: [squared error, bad-index flag]
     uint64_t *h_decode_stat = nullptr;    // pinned host copy
@@ -509,6 +511,7 @@ void free_training(qvq_ctx *ctx) {
     dfree(ctx->d_ex_koff);
     ctx->ex_kcap = 0;
     ctx->exact = false;
+    ctx->exact_cs = -1;
     dfree(ctx->d_sortbuf);
     dfree(ctx->d_codes);
     dfree(ctx->d_A);
@@ -2323,9 +2326,25 @@ qvq_status tile_into(qvq_ctx *ctx, const uint8_t *d_rgb, uint32_t n_images, uint
     return QVQ_OK;
 }
 
+// What a CIE1931 raster must pass after check_image_args, in this order, before the resident set is
+// touched: its values are no byte images, so it becomes an exact-mode set.
+qvq_status check_cie_raster(qvq_ctx *ctx, uint64_t N, uint32_t bw, uint32_t bh) {
+    if (bw > 64 || bh > 64 || 3 * bw * bh > 64)
+        return fail(ctx, QVQ_EINVAL, "block dimension above 64 (3*w*h) is not supported");
+    if (ctx->comm || ctx->host_ar)
+        return fail(ctx, QVQ_EUNSUPPORTED, "CIE1931 values are not byte images (exact mode runs on one rank)");
+    if (N >= (1ull << 31)) return fail(ctx, QVQ_EINVAL, "exact mode: more than 2^31-1 rows");
+    return QVQ_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+// The exact-mode set of the rasters d_rgb (device memory the context's stream may read) under
+// CIE1931: tiled and converted in one launch into a fresh d_X64 (k_tile64.hip); defined with install_exact.
+static qvq_status install_cie_raster(qvq_ctx *ctx, const uint8_t *d_rgb, uint32_t n_images, uint32_t xSize,
+                                     uint32_t ySize, uint32_t bw, uint32_t bh, uint64_t N, uint32_t D);
 
 QVQ_API const char *qvq_version(void) { return "qvq 0.2 (gfx950, f16 MFMA search)"; }
 
@@ -2486,7 +2505,10 @@ QVQ_API qvq_status qvq_set_images_device(qvq_ctx *ctx, const void *d_rgb, uint32
     if (st != QVQ_OK) return st;
     GUARD(ctx);
     if (!d_rgb) return fail(ctx, QVQ_EINVAL, "null raster");
+    if (colorspace == QVQ_CS_CIE1931 && (st = check_cie_raster(ctx, N, bw, bh)) != QVQ_OK) return st;
     HIPCHK(hipSetDevice(ctx->dev));
+    if (colorspace == QVQ_CS_CIE1931)
+        return install_cie_raster(ctx, (const uint8_t *)d_rgb, n_images, xSize, ySize, bw, bh, N, D);
     if ((st = alloc_training(ctx, N, D, colorspace)) != QVQ_OK) return st;
     if ((st = tile_into(ctx, (const uint8_t *)d_rgb, n_images, xSize, ySize, bw, bh)) != QVQ_OK) return st;
     return compute_xsq(ctx);
@@ -2500,6 +2522,7 @@ QVQ_API qvq_status qvq_set_images(qvq_ctx *ctx, const uint8_t *rgb, uint32_t n_i
     if (st != QVQ_OK) return st;
     GUARD(ctx);
     if (!rgb) return fail(ctx, QVQ_EINVAL, "null raster");
+    if (colorspace == QVQ_CS_CIE1931 && (st = check_cie_raster(ctx, N, bw, bh)) != QVQ_OK) return st;
     HIPCHK(hipSetDevice(ctx->dev));
     const uint64_t bytes = (uint64_t)xSize * ySize * 3 * n_images;
     if (ctx->raster_bytes < bytes) {   // kept across calls (repeated compresses)
@@ -2510,6 +2533,8 @@ QVQ_API qvq_status qvq_set_images(qvq_ctx *ctx, const uint8_t *rgb, uint32_t n_i
     }
     const hipError_t e = host_copy(ctx, ctx->d_raster, rgb, bytes, hipMemcpyHostToDevice);
     if (e != hipSuccess) return fail(ctx, QVQ_EDEVICE, std::string("raster upload: ") + hipGetErrorString(e));
+    if (colorspace == QVQ_CS_CIE1931)
+        return install_cie_raster(ctx, ctx->d_raster, n_images, xSize, ySize, bw, bh, N, D);
     if ((st = alloc_training(ctx, N, D, colorspace)) != QVQ_OK) return st;
     if ((st = tile_into(ctx, ctx->d_raster, n_images, xSize, ySize, bw, bh)) != QVQ_OK) return st;
     return compute_xsq(ctx);
@@ -2524,6 +2549,8 @@ QVQ_API qvq_status qvq_set_synthetic(qvq_ctx *ctx, uint32_t S, uint64_t seed0, u
     if (S < 2) return fail(ctx, QVQ_EINVAL, "synthetic images need S >= 2");
     qvq_status st = check_image_args(ctx, n_images, S, S, bw, bh, N, D);
     if (st != QVQ_OK) return st;
+    const bool cie = colorspace == QVQ_CS_CIE1931;
+    if (cie && (st = check_cie_raster(ctx, N, bw, bh)) != QVQ_OK) return st;
     HIPCHK(hipSetDevice(ctx->dev));
     const uint64_t npix = (uint64_t)S * S * n_images;
     uint8_t *d_rgb = nullptr;
@@ -2531,9 +2558,10 @@ QVQ_API qvq_status qvq_set_synthetic(qvq_ctx *ctx, uint32_t S, uint64_t seed0, u
     st = QVQ_OK;
     const hipError_t e = launch_gen(ctx->stream, d_rgb, S, seed0, npix);
     if (e != hipSuccess) st = fail(ctx, QVQ_EDEVICE, std::string("gen_kernel: ") + hipGetErrorString(e));
-    if (st == QVQ_OK) st = alloc_training(ctx, N, D, colorspace);
-    if (st == QVQ_OK) st = tile_into(ctx, d_rgb, n_images, S, S, bw, bh);
-    if (st == QVQ_OK) st = compute_xsq(ctx);
+    if (st == QVQ_OK && cie) st = install_cie_raster(ctx, d_rgb, n_images, S, S, bw, bh, N, D);
+    if (st == QVQ_OK && !cie) st = alloc_training(ctx, N, D, colorspace);
+    if (st == QVQ_OK && !cie) st = tile_into(ctx, d_rgb, n_images, S, S, bw, bh);
+    if (st == QVQ_OK && !cie) st = compute_xsq(ctx);
     (void)hipStreamSynchronize(ctx->stream);
     (void)hipFree(d_rgb);
     return st;
@@ -2607,10 +2635,12 @@ struct DevRows {
     }
 };
 
-// The exact-mode set: src's rows (kind: from the host, or from the device on the context's stream)
-// copied into the engine's own d_X64, or *adopt (an upload of the engine's own) taken over as it is.
-static qvq_status install_exact(qvq_ctx *ctx, const double *src, hipMemcpyKind kind, double **adopt, uint64_t n,
-                                uint32_t dim) {
+// The exact-mode set of n rows of dim components: *adopt (an upload of the engine's own) taken over
+// as d_X64 as it is, or a fresh d_X64 that fill writes with work on the context's stream (a copy of
+// the caller's rows, or the launch that produces them).  raster_cs: the colour space of the raster
+// the rows come from, -1 for fp64 rows (qvq_get_training_info).  Returns with the stream drained.
+static qvq_status install_exact(qvq_ctx *ctx, uint64_t n, uint32_t dim, int raster_cs, double **adopt,
+                                const std::function<hipError_t(double *)> &fill) {
     ctx->rf = qvq_ctx::RefineState();
     free_training(ctx);
     free_levels(ctx);
@@ -2619,6 +2649,7 @@ static qvq_status install_exact(qvq_ctx *ctx, const double *src, hipMemcpyKind k
     ctx->Dp = (dim + 3) & ~3u;
     ctx->cs = -1;
     ctx->exact = true;
+    ctx->exact_cs = raster_cs;
     if (adopt) {
         ctx->d_X64 = *adopt;
         *adopt = nullptr;
@@ -2632,10 +2663,35 @@ static qvq_status install_exact(qvq_ctx *ctx, const double *src, hipMemcpyKind k
     HIPCHK(hipMalloc(&ctx->d_ex_order, n * 4));
     ctx->ex_temp_bytes = exact_sort_temp_bytes(n);
     HIPCHK(hipMalloc(&ctx->d_ex_temp, std::max<size_t>(ctx->ex_temp_bytes, 16)));
-    if (!adopt) HIPCHK(hipMemcpyAsync(ctx->d_X64, src, n * dim * 8, kind, ctx->stream));
+    if (!adopt) HIPCHK(fill(ctx->d_X64));
     HIPCHK(launch_exact_iota(ctx->stream, ctx->d_ex_iota, n));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return QVQ_OK;
+}
+// ... from src's rows: on the host, or on the device where the context's stream may read them
+static qvq_status install_exact_copy(qvq_ctx *ctx, const double *src, hipMemcpyKind kind, double **adopt, uint64_t n,
+                                     uint32_t dim) {
+    return install_exact(ctx, n, dim, -1, adopt, [&](double *dst) {
+        return hipMemcpyAsync(dst, src, n * dim * 8, kind, ctx->stream);
+    });
+}
+// ... from rasters under CIE1931 (declared above qvq_set_images_device): nothing is classified -- the
+// values are never byte images -- and nothing is copied: the launch writes d_X64.  Under
+// qvq_set_timing(-3) events around the launch give its device ms (qvq_get_ingest_ms()[1]).
+static qvq_status install_cie_raster(qvq_ctx *ctx, const uint8_t *d_rgb, uint32_t n_images, uint32_t xSize,
+                                     uint32_t ySize, uint32_t bw, uint32_t bh, uint64_t N, uint32_t D) {
+    const bool timed = ctx->timing_level == -3;
+    ctx->ingest_ms[0] = ctx->ingest_ms[1] = 0;
+    const qvq_status st = install_exact(ctx, N, D, QVQ_CS_CIE1931, nullptr, [&](double *dst) {
+        hipError_t e = timed ? hipEventRecord(ctx->ev_ing[1], ctx->stream) : hipSuccess;
+        if (e == hipSuccess) e = launch_tile64(ctx->stream, d_rgb, dst, n_images, xSize, ySize, bw, bh);
+        if (e == hipSuccess && timed) e = hipEventRecord(ctx->ev_ing[2], ctx->stream);
+        return e;
+    });
+    float ms = 0;
+    if (st == QVQ_OK && timed && hipEventElapsedTime(&ms, ctx->ev_ing[1], ctx->ev_ing[2]) == hipSuccess)
+        ctx->ingest_ms[1] = ms;
+    return st;
 }
 
 // The training set from fp64 rows dX [n][dim] that the context's stream may read: classify, then
@@ -2657,7 +2713,7 @@ static qvq_status ingest_rows(qvq_ctx *ctx, const double *dX, uint64_t n, uint32
     qvq_status st;
     if (cs < 0) {
         if ((st = check_exact_set(ctx, n, force_exact, (v & ING_FINITE) != 0)) != QVQ_OK) return st;
-        return install_exact(ctx, dX, hipMemcpyDeviceToDevice, adopt, n, dim);
+        return install_exact_copy(ctx, dX, hipMemcpyDeviceToDevice, adopt, n, dim);
     }
     ctx->col_blocks = 0;   // rows without image geometry
     // (the same shape again keeps every buffer; the pack below refills d_codes either way)
@@ -2686,7 +2742,7 @@ static qvq_status ingest_host_rule(qvq_ctx *ctx, const double *X, uint64_t n, ui
     qvq_status st;
     if (cs < 0) {
         if ((st = check_exact_set(ctx, n, force_exact, finite)) != QVQ_OK) return st;
-        return install_exact(ctx, X, hipMemcpyHostToDevice, nullptr, n, dim);
+        return install_exact_copy(ctx, X, hipMemcpyHostToDevice, nullptr, n, dim);
     }
     ctx->col_blocks = 0;
     if ((st = alloc_training(ctx, n, dim, cs)) != QVQ_OK) return st;
@@ -2744,9 +2800,46 @@ QVQ_API qvq_status qvq_set_vectors_device(qvq_ctx *ctx, const void *d_X, uint64_
 QVQ_API qvq_status qvq_get_training_info(const qvq_ctx *ctx, qvq_training_info *out) {
     if (!ctx || !out) return QVQ_EINVAL;
     out->mode = ctx->exact ? 2u : ctx->d_codes ? 1u : 0u;
-    out->colorspace = out->mode == 1 ? ctx->cs : -1;
+    out->colorspace = out->mode == 1 ? ctx->cs : out->mode == 2 ? ctx->exact_cs : -1;
     out->n = ctx->N;
     out->dim = ctx->D;
+    return QVQ_OK;
+}
+
+// The resident rows row0 .. row0 + nrows - 1 as fp64 [nrows][dim]: exact mode's rows themselves, or the
+// byte path's codes through the colour space's table (rows_f64_kernel into the decode scratch).  In
+// pieces of at most GET_PIECE bytes through pinned staging: a piece reaches the caller's memory only
+// after the bounded wait for its copy has succeeded.
+QVQ_API qvq_status qvq_get_vectors(qvq_ctx *ctx, uint64_t row0, uint64_t nrows, double *out) {
+    if (!ctx) return QVQ_EINVAL;
+    GUARD(ctx);
+    if (ctx->N == 0) return fail(ctx, QVQ_ESTATE, "no training set");
+    if (!out || nrows == 0) return fail(ctx, QVQ_EINVAL, "empty read-back");
+    if (row0 >= ctx->N || nrows > ctx->N - row0) return fail(ctx, QVQ_EINVAL, "rows outside the training set");
+    HIPCHK(hipSetDevice(ctx->dev));
+    constexpr uint64_t GET_PIECE = 64ull << 20;
+    const uint64_t row_bytes = (uint64_t)ctx->D * 8;
+    const uint64_t piece_rows = std::min<uint64_t>(nrows, std::max<uint64_t>(1, GET_PIECE / row_bytes));
+    qvq_status st = ensure_pinned(ctx, ctx->h_stage, ctx->stage_bytes, piece_rows * row_bytes);
+    if (st != QVQ_OK) return st;
+    if (!ctx->exact && ctx->decode_bytes < piece_rows * row_bytes) {
+        dfree(ctx->d_decode);
+        ctx->decode_bytes = 0;
+        HIPCHK(hipMalloc(&ctx->d_decode, piece_rows * row_bytes));
+        ctx->decode_bytes = piece_rows * row_bytes;
+    }
+    for (uint64_t r = 0; r < nrows; r += piece_rows) {
+        const uint64_t nr = std::min(piece_rows, nrows - r);
+        const double *src = ctx->d_X64 + (row0 + r) * ctx->D;
+        if (!ctx->exact) {
+            double *d = reinterpret_cast<double *>(ctx->d_decode);
+            HIPCHK(launch_rows_f64(ctx->stream, ctx->d_codes, ctx->Dp, ctx->D, row0 + r, nr, ctx->d_lut64, d));
+            src = d;
+        }
+        HIPCHK(hipMemcpyAsync(ctx->h_stage, src, nr * row_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        if ((st = wait_stream(ctx)) != QVQ_OK) return st;
+        std::memcpy(out + r * ctx->D, ctx->h_stage, nr * row_bytes);
+    }
     return QVQ_OK;
 }
 
@@ -3978,6 +4071,20 @@ QVQ_API qvq_status qvq_host_ingest_grid(qvq_ingest_grid *out) {
     if (!out) return QVQ_EINVAL;
     out->block = ING_THREADS;
     out->blocks = ING_GRID_CAP;
+    return QVQ_OK;
+}
+
+QVQ_API qvq_status qvq_host_tile64_grid(qvq_tile64_grid *out) {
+    if (!out) return QVQ_EINVAL;
+    out->block = T64_THREADS;
+    out->blocks = T64_GRID_CAP;
+    return QVQ_OK;
+}
+
+QVQ_API qvq_status qvq_host_cie1931(const uint8_t *rgb, uint64_t npix, double *out) {
+    if (!rgb || !out) return QVQ_EINVAL;
+    for (uint64_t i = 0; i < npix; i++)
+        cie1931_from_rgb((signed char)rgb[3 * i], (signed char)rgb[3 * i + 1], (signed char)rgb[3 * i + 2], out + 3 * i);
     return QVQ_OK;
 }
 
