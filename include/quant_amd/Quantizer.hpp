@@ -26,5 +26,7 @@ QuantizerPtr getQuantizer(Quantizers);
 // The LBG quantizer followed by Lloyd refinement at the final K on the device (qvq_refine,
 // include/qvq.h): up to maxIters iterations, stopped when no index changes or when the
 // distortion's relative change falls to quantize()'s eps; fresh: the returned indices are the
-// nearest code vectors of the returned codebook (one more assignment).  (0, false) is getQuantizer(LBG).
-QuantizerPtr getRefinedLBGQuantizer(size_t maxIters, bool fresh);
+// nearest code vectors of the returned codebook (one more assignment); reseed: after each
+// iteration's centroid step the empty cells take rows of the worst cells (QVQ_REFINE_RESEED; byte
+// images only, needs maxIters > 0: std::invalid_argument otherwise).  (0, false) is getQuantizer(LBG).
+QuantizerPtr getRefinedLBGQuantizer(size_t maxIters, bool fresh, bool reseed = false);

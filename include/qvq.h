@@ -242,8 +242,36 @@ QVQ_API const uint32_t *qvq_assign_device(const qvq_ctx *ctx);
  * peer rejected the call), and so does every rank when the arguments differ; no rank's state is
  * touched and none waits for a peer that will not come.  A collective that fails returns QVQ_ECOMM
  * as everywhere (qvq_comm_init).
+ *
+ * QVQ_REFINE_RESEED: after each iteration's centroid step the empty cells of C_t take rows of the
+ * worst cells as their code vectors (without the flag an empty cell is the zero vector and, at a
+ * fixed K, never fills again).  From A_t, the centroids C_t as formed above and the cell counts n_k:
+ *   per-row error   for each row, k = A_t[row]: e = 0; for d = 0 .. dim-1 ascending: u = x_d -
+ *                   C_t[k][d], e = e + u*u; every subtraction, product and sum rounded once to fp64,
+ *                   no fused multiply-add; x_d = qvq_host_colorspace_values[code]; pad components
+ *                   take no part (qvq_host_row_error);
+ *   quantised error q_row = floor(e 2^s) as an unsigned integer, s = 24 for SCALED (e <= 64), s = 8
+ *                   for NORMAL (e <= 64 255^2): q_row < 2^31, sums over < 2^32 rows fit u64;
+ *   per cell        E_k = the sum of q_row over the rows of cell k (an exact integer: no order);
+ *                   far_k = the row of cell k with the largest q_row, on equal q_row the lowest row;
+ *   empties         the cells with n_k = 0, in ascending k;
+ *   donors          the cells with n_k >= 2 and E_k > 0, by E_k descending, on equal E_k by k
+ *                   ascending;
+ *   seeds           m = min(empties, donors); for j < m, C_t[empty_j] takes the dim values of row
+ *                   far_{donor_j}.  A donor gives one seed per iteration; its own centroid is not
+ *                   touched (qvq_host_reseed_select).
+ * C_t with its seeds is iteration t's codebook: searched in iteration t + 1, returned as the
+ * call's codebook, and the state a later C_start == NULL call continues from.  d_t and
+ * changed[t-1] are those of the unseeded step (an empty cell owns no row).  Reseeding runs in every
+ * iteration, the last one included.  QVQ_STOP_FIXED then needs changed == 0 and no seed placed in
+ * that iteration; the eps and max_iters tests follow in the order above.  With QVQ_REFINE_FRESH
+ * A* is the assignment for the seeded C_t and the distortion its closed form.
+ * qvq_get_refine_reseeds returns the seeds placed per iteration.  One rank's byte path only: with
+ * a communicator joined (any nranks) the flag is QVQ_EUNSUPPORTED, a verdict that goes through
+ * the entry vote like any other; so is a training set of 2^32 - 1 rows or more.  Without the flag
+ * nothing changes: the launches and the results are those of the call without it.
  */
-enum { QVQ_REFINE_FRESH = 1 };                    /* flags */
+enum { QVQ_REFINE_FRESH = 1, QVQ_REFINE_RESEED = 2 };   /* flags */
 enum { QVQ_STOP_FIXED = 0, QVQ_STOP_EPS = 1, QVQ_STOP_MAXIT = 2 };
 typedef struct { uint32_t iters, stop; } qvq_refine_info;
 QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start /* K x dim, or NULL */,
@@ -252,6 +280,10 @@ QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start /*
                               uint64_t *changed /* max_iters, may be NULL */,
                               double *dist_trace /* max_iters, may be NULL */,
                               qvq_refine_info *info /* may be NULL */);
+/* The seeds QVQ_REFINE_RESEED placed in each iteration of the last qvq_refine (all 0 without the
+ * flag): the first min(cap, iterations) entries of out, *iters = the iterations (either may be
+ * NULL / 0).  QVQ_ESTATE before any qvq_refine on the context. */
+QVQ_API qvq_status qvq_get_refine_reseeds(qvq_ctx *ctx, uint64_t *out, uint32_t cap, uint32_t *iters);
 
 /* Single steps over the current training set, for tests and benchmarks.
  * qvq_assign: nearest code vector of every row for codebook C (K x dim fp64, host),
@@ -425,6 +457,20 @@ QVQ_API qvq_status qvq_host_cie1931(const uint8_t *rgb, uint64_t npix, double *o
  * grid-stride loop a second time.  One kernel serves every block shape. */
 typedef struct { uint32_t block, blocks; } qvq_tile64_grid;
 QVQ_API qvq_status qvq_host_tile64_grid(qvq_tile64_grid *out);
+/* QVQ_REFINE_RESEED's rule on the host (quant_amd/csrc/reseed_rule.hpp, the text the device
+ * passes run).  qvq_host_row_error: *q = the quantised error of the dim values x against the code
+ * vector c under the colour space's shift.  qvq_host_reseed_far_key: the key whose u64 maximum over
+ * a cell's rows names its far row, (q << 32) | (0xFFFFFFFF - row).  qvq_host_reseed_select: from
+ * the K cells' summed errors E, row counts n and far-row keys far, the m seeds in order:
+ * empties_out[j] takes row rows_out[j] (K entries each, either may be NULL). */
+QVQ_API qvq_status qvq_host_row_error(const double *x, const double *c, uint32_t dim, int colorspace, uint32_t *q);
+QVQ_API qvq_status qvq_host_reseed_far_key(uint32_t q, uint32_t row, uint64_t *key);
+QVQ_API qvq_status qvq_host_reseed_select(const uint64_t *E, const uint64_t *n, const uint64_t *far, uint32_t K,
+                                          uint32_t *empties_out, uint32_t *rows_out, uint32_t *m);
+/* The reseed's rows pass: one lane per row, `block` lanes per block, at most `blocks` blocks: more
+ * than block * blocks rows take the kernel's grid-stride loop a second time. */
+typedef struct { uint32_t block, blocks; } qvq_reseed_grid;
+QVQ_API qvq_status qvq_host_reseed_grid(qvq_reseed_grid *out);
 /* The engine's bounded-wait policy (quant_amd/csrc/wait.hpp) driven by scripted probes, for
  * tests: scenario 0 the work publishes after ~5 ms; 1 it never does, no communicator; 2 it
  * never does, a healthy communicator; 3 the communicator reports an error after ~5 ms; 4 the

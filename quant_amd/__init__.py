@@ -75,10 +75,11 @@ EXPORTED = ["qvq_create", "qvq_destroy", "qvq_last_error", "qvq_version", "qvq_s
             "qvq_host_kdtree_image", "qvq_refine", "qvq_host_plan", "qvq_host_exact_plan",
             "qvq_host_exact_grids", "qvq_set_vectors_device", "qvq_get_training_info", "qvq_get_ingest_ms",
             "qvq_host_colorspace_values", "qvq_host_classify", "qvq_host_ingest_grid", "qvq_get_vectors",
-            "qvq_host_cie1931", "qvq_host_tile64_grid"]
+            "qvq_host_cie1931", "qvq_host_tile64_grid", "qvq_get_refine_reseeds", "qvq_host_row_error",
+            "qvq_host_reseed_far_key", "qvq_host_reseed_select", "qvq_host_reseed_grid"]
 
 COMM_NONE, COMM_RCCL, COMM_HOST = 0, 1, 2
-REFINE_FRESH = 1                              # qvq_refine flags
+REFINE_FRESH, REFINE_RESEED = 1, 2            # qvq_refine flags
 VECTORS_EXACT = 1                             # qvq_set_vectors_device flags
 MODE_NONE, MODE_BYTE, MODE_EXACT = 0, 1, 2    # qvq_training_info.mode
 STOP_FIXED, STOP_EPS, STOP_MAXIT = 0, 1, 2    # qvq_refine_info.stop
@@ -142,6 +143,11 @@ def lib():
             "qvq_get_vectors": ([P, u64, u64, P], i),
             "qvq_host_cie1931": ([P, u64, P], i),
             "qvq_host_tile64_grid": ([ctypes.POINTER(_IngestGrid)], i),   # qvq_tile64_grid: the same two fields
+            "qvq_get_refine_reseeds": ([P, P, u32, ctypes.POINTER(u32)], i),
+            "qvq_host_row_error": ([P, P, u32, i, ctypes.POINTER(u32)], i),
+            "qvq_host_reseed_far_key": ([u32, u32, ctypes.POINTER(u64)], i),
+            "qvq_host_reseed_select": ([P, P, P, u32, P, P, ctypes.POINTER(u32)], i),
+            "qvq_host_reseed_grid": ([ctypes.POINTER(_IngestGrid)], i),   # qvq_reseed_grid: the same two fields
         }
         for name, (args, res) in sig.items():
             if os.environ.get("QVQ_LIB") and not hasattr(L, name):
@@ -298,12 +304,14 @@ class Engine:
         self._last_k = K
         return C, A, float(d[0])
 
-    def refine(self, K=None, C=None, max_iters=100, eps=1e-6, fresh=False, want_assign=True):
+    def refine(self, K=None, C=None, max_iters=100, eps=1e-6, fresh=False, want_assign=True, reseed=False):
         """Lloyd refinement at fixed K on the device (qvq_refine): (C, A, distortion, info).
         C=None continues from this engine's last lbg() or refine() (K defaults to that call's K);
         a K x dim array C is a warm start.  fresh=True returns the indices of the final codebook
         (one more assignment) and their distortion.  info: iters, stop (STOP_FIXED / STOP_EPS /
-        STOP_MAXIT), changed (rows that moved, per iteration), distortion (per iteration).
+        STOP_MAXIT), changed (rows that moved, per iteration), distortion (per iteration), reseeded
+        (seeds placed, per iteration: all 0 without reseed).  reseed=True: after each centroid step
+        the empty cells take rows of the worst cells (QVQ_REFINE_RESEED; one rank's byte path).
         want_assign=False leaves the indices on the device (A is None).
         With a communicator joined (comm_init / comm_init_host) every rank calls it with the same
         arguments on its own rows: C, distortion and info are those of one rank over all the rows,
@@ -322,14 +330,27 @@ class Engine:
         d = np.zeros(1, np.float64)
         chg = np.zeros(max(max_iters, 1), np.uint64)
         trace = np.zeros(max(max_iters, 1), np.float64)
+        seeds = np.zeros(max(max_iters, 1), np.uint64)
         inf = np.zeros(2, np.uint32)
         _check(lib().qvq_refine(self._h, K, _p(C) if C is not None else None, max_iters, float(eps),
-                                REFINE_FRESH if fresh else 0, _p(out), _p(A) if want_assign else None, _p(d), _p(chg), _p(trace), _p(inf)),
+                                (REFINE_FRESH if fresh else 0) | (REFINE_RESEED if reseed else 0), _p(out),
+                                _p(A) if want_assign else None, _p(d), _p(chg), _p(trace), _p(inf)),
                self._h)
         self._last_k = K
         it = int(inf[0])
+        if hasattr(lib(), "qvq_get_refine_reseeds"):   # (an older A/B build, QVQ_LIB, has none: it never seeds)
+            _check(lib().qvq_get_refine_reseeds(self._h, _p(seeds), seeds.size, None), self._h)
         return out, A, float(d[0]), {"iters": it, "stop": int(inf[1]), "changed": [int(x) for x in chg[:it]],
-                                     "distortion": [float(x) for x in trace[:it]]}
+                                     "distortion": [float(x) for x in trace[:it]],
+                                     "reseeded": [int(x) for x in seeds[:it]]}
+
+    def refine_reseeds(self):
+        """The seeds the last refine() placed in each iteration (qvq_get_refine_reseeds)."""
+        n = ctypes.c_uint32()
+        _check(lib().qvq_get_refine_reseeds(self._h, None, 0, ctypes.byref(n)), self._h)
+        out = np.zeros(max(n.value, 1), np.uint64)
+        _check(lib().qvq_get_refine_reseeds(self._h, _p(out), n.value, ctypes.byref(n)), self._h)
+        return [int(x) for x in out[:n.value]]
 
     def assign(self, C):
         C = np.ascontiguousarray(C, np.float64)
@@ -524,6 +545,43 @@ def host_cie1931(rgb):
     return out
 
 
+def host_reseed_grid():
+    """The reseed rows pass's launch shape (qvq_host_reseed_grid): {"block", "blocks"}; one lane per row."""
+    g = _IngestGrid()
+    _check(lib().qvq_host_reseed_grid(ctypes.byref(g)))
+    return {f: int(getattr(g, f)) for f, _ in _IngestGrid._fields_}
+
+
+def host_row_error(x, c, colorspace=SCALED):
+    """The quantised per-row error of QVQ_REFINE_RESEED (qvq_host_row_error): values x against code vector c."""
+    x = np.ascontiguousarray(x, np.float64).ravel()
+    c = np.ascontiguousarray(c, np.float64).ravel()
+    assert x.size == c.size
+    q = ctypes.c_uint32()
+    _check(lib().qvq_host_row_error(_p(x), _p(c), x.size, int(colorspace), ctypes.byref(q)))
+    return q.value
+
+
+def host_reseed_far_key(q, row):
+    """The far-row key (qvq_host_reseed_far_key): its maximum over a cell's rows names the far row."""
+    key = ctypes.c_uint64()
+    _check(lib().qvq_host_reseed_far_key(int(q), int(row), ctypes.byref(key)))
+    return key.value
+
+
+def host_reseed_select(E, n, far):
+    """QVQ_REFINE_RESEED's selection (qvq_host_reseed_select) from the cells' summed errors E, row
+    counts n and far-row keys far: (empties, rows), cell empties[j] takes row rows[j]."""
+    E = np.ascontiguousarray(E, np.uint64)
+    n = np.ascontiguousarray(n, np.uint64)
+    far = np.ascontiguousarray(far, np.uint64)
+    K = E.size
+    assert n.size == K and far.size == K
+    em, rows, m = np.zeros(K, np.uint32), np.zeros(K, np.uint32), ctypes.c_uint32()
+    _check(lib().qvq_host_reseed_select(_p(E), _p(n), _p(far), K, _p(em), _p(rows), ctypes.byref(m)))
+    return [int(x) for x in em[:m.value]], [int(x) for x in rows[:m.value]]
+
+
 def colorspace_values(colorspace=SCALED):
     """The colour space's byte -> value table (qvq_host_colorspace_values): 256 float64, the values
     a byte-image training set must hold bit for bit."""
@@ -619,13 +677,17 @@ class AbstractQuantizer:
 class LBGQuantizer(AbstractQuantizer):
     """LBGQuantizer (src/Quantizer.cpp:119-144) on the MI355X engine."""
 
-    def __init__(self, device=0, refine_iters=0, fresh=False):
+    def __init__(self, device=0, refine_iters=0, fresh=False, reseed=False):
         """refine_iters > 0: up to that many Lloyd iterations at the final K after the split
-        levels, stopped by eps (Engine.refine); fresh: the indices of the returned codebook."""
+        levels, stopped by eps (Engine.refine); fresh: the indices of the returned codebook;
+        reseed: the iterations reseed their empty cells (needs refine_iters > 0)."""
+        if reseed and int(refine_iters) <= 0:
+            raise QVQError(1, "reseed needs refine_iters > 0")
         self._device = device
         self._engine = None
         self._refine_iters = int(refine_iters)
         self._fresh = bool(fresh)
+        self._reseed = bool(reseed)
 
     def quantize(self, trainingSet, n, eps):
         if self._engine is None:
@@ -635,7 +697,8 @@ class LBGQuantizer(AbstractQuantizer):
         self._engine.set_vectors(trainingSet if dev else np.asarray(trainingSet, np.float64))
         res = self._engine.lbg(int(n), eps)
         if self._refine_iters > 0 or self._fresh:
-            res = self._engine.refine(max_iters=self._refine_iters, eps=eps, fresh=self._fresh)[:3]
+            res = self._engine.refine(max_iters=self._refine_iters, eps=eps, fresh=self._fresh,
+                                      reseed=self._reseed)[:3]
         return res
 
 

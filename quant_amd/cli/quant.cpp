@@ -3,7 +3,7 @@
 //
 //   quant FILE -o OUT [-n bits=8] [-e eps=1e-6] [-w width=2] [-h height=2] [-r raport=0]
 //                     [-q quantizer=0 (LBG)] [-c colorspace=1 (SCALED)] [--device N]
-//                     [--refine N=0] [--fresh]
+//                     [--refine N=0] [--fresh] [--reseed]
 //
 // FILE.ppm -> OUT.quant compresses, FILE.quant -> OUT.ppm decompresses, FILE.ppm -> OUT.ppm
 // compresses and writes the decoded image (src/main.cpp:73-111); anything else prints "File
@@ -13,6 +13,7 @@
 // on the GPU through libquant_amd.so / libqvq.so.  --refine N runs up to N Lloyd iterations at the
 // final codebook size after the split levels (stopped by eps) and --fresh writes the indices of
 // the codebook in the file (getRefinedLBGQuantizer); with neither the output is the reference's.
+// --reseed (with --refine N > 0) lets the iterations reseed their empty cells (QVQ_REFINE_RESEED).
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
@@ -46,6 +47,7 @@ struct Params {   // include/ProgramParameters.hpp:5-19, defaults of src/main.cp
     bool raport = false;
     int refine = 0;       // --refine: Lloyd iterations at the final K (0: none)
     bool fresh = false;   // --fresh: indices of the written codebook
+    bool reseed = false;  // --reseed: the refinement reseeds its empty cells
     std::string file, saveto;
 };
 
@@ -63,7 +65,8 @@ const char *kHelp =
     "  -c [ --colorspace ] arg (=1) Pick ColorSpace\n"
     "  --device arg (=0)      HIP device of the engine (MI355X build)\n"
     "  --refine arg (=0)      Lloyd iterations at the final codebook size (LBG, stopped by -e)\n"
-    "  --fresh                Indices re-assigned to the written codebook\n";
+    "  --fresh                Indices re-assigned to the written codebook\n"
+    "  --reseed               Empty cells reseeded from the worst cells (with --refine)\n";
 
 bool parse_bool(const std::string &v) {   // program_options' bool values
     if (v == "1" || v == "true" || v == "yes" || v == "on") return true;
@@ -89,8 +92,8 @@ bool parse(int argc, char **argv, Params &p) {
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         if (a == "--help") return true;
-        if (a == "--fresh") {   // the one flag without a value
-            p.fresh = true;
+        if (a == "--fresh" || a == "--reseed") {   // the flags without a value
+            (a == "--fresh" ? p.fresh : p.reseed) = true;
             continue;
         }
         std::string key, val;
@@ -145,6 +148,9 @@ bool parse(int argc, char **argv, Params &p) {
     if (!have_out) throw std::invalid_argument("the option '--saveto' is required but missing");
     if ((p.refine > 0 || p.fresh) && p.quantizer != (int)Quantizers::LBG)
         throw std::invalid_argument("options '--refine' and '--fresh' need the LBG quantizer");
+    if (p.reseed && p.quantizer != (int)Quantizers::LBG)
+        throw std::invalid_argument("option '--reseed' needs the LBG quantizer");
+    if (p.reseed && p.refine <= 0) throw std::invalid_argument("option '--reseed' needs '--refine' > 0");
     return false;
 }
 
@@ -167,7 +173,7 @@ int main(int argc, char **argv) {
         auto run_compression = [&]() {   // src/main.cpp:76-84
             RGBImage img(par.file);
             QuantizerPtr refined;
-            if (par.refine > 0 || par.fresh) refined = getRefinedLBGQuantizer((size_t)par.refine, par.fresh);
+            if (par.refine > 0 || par.fresh) refined = getRefinedLBGQuantizer((size_t)par.refine, par.fresh, par.reseed);
             auto result = refined ? CompressedImage::compress(img, *refined, (ColorSpaces)par.colorspace, par.width,
                                                               par.height, par.eps, par.n)
                                   : CompressedImage::compress(img, (Quantizers)par.quantizer,

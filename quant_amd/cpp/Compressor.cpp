@@ -134,8 +134,8 @@ std::tuple<std::vector<Vector>, std::vector<size_t>, VectorType> quantize_raster
     if (refined) {
         if (opt.maxIters > 0xFFFFFFFFull) throw std::runtime_error("compress: too many refinement iterations");
         EngineHandle::check(qvq_refine(ctx, (uint32_t)K, nullptr, (uint32_t)opt.maxIters, eps,
-                                       opt.fresh ? QVQ_REFINE_FRESH : 0, C.data(), A.data(), &distortion, nullptr,
-                                       nullptr, nullptr),
+                                       (opt.fresh ? QVQ_REFINE_FRESH : 0u) | (opt.reseed ? QVQ_REFINE_RESEED : 0u),
+                                       C.data(), A.data(), &distortion, nullptr, nullptr, nullptr),
                             "qvq_refine");
     } else if (cs == ColorSpaces::SCALED && codebook_near_byte_flip(C)) {
         EngineHandle::check(qvq_update_kahan(ctx, A.data(), (uint32_t)K, C.data()), "qvq_update_kahan");

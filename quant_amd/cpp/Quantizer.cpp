@@ -48,12 +48,12 @@ namespace {
 // returned codebook.
 class HipLBGQuantizer : public AbstractQuantizer {
     size_t maxIters_ = 0;
-    bool fresh_ = false;
+    bool fresh_ = false, reseed_ = false;
 
 public:
     HipLBGQuantizer() = default;
-    HipLBGQuantizer(size_t maxIters, bool fresh) : maxIters_(maxIters), fresh_(fresh) {}
-    quant_amd::RefineOptions options() const { return {maxIters_, fresh_}; }
+    HipLBGQuantizer(size_t maxIters, bool fresh, bool reseed) : maxIters_(maxIters), fresh_(fresh), reseed_(reseed) {}
+    quant_amd::RefineOptions options() const { return {maxIters_, fresh_, reseed_}; }
     std::tuple<std::vector<Vector>, std::vector<size_t>, VectorType> quantize(const std::vector<Vector> &trainingSet,
                                                                               size_t n, VectorType eps) override {
         using quant_amd::EngineHandle;
@@ -74,8 +74,8 @@ public:
         if (maxIters_ > 0 || fresh_) {
             if (maxIters_ > 0xFFFFFFFFull) throw std::runtime_error("LBG quantize: too many refinement iterations");
             EngineHandle::check(qvq_refine(ctx, (uint32_t)K, nullptr, (uint32_t)maxIters_, eps,
-                                           fresh_ ? QVQ_REFINE_FRESH : 0, C.data(), A.data(), &distortion, nullptr,
-                                           nullptr, nullptr),
+                                           (fresh_ ? QVQ_REFINE_FRESH : 0u) | (reseed_ ? QVQ_REFINE_RESEED : 0u),
+                                           C.data(), A.data(), &distortion, nullptr, nullptr, nullptr),
                                 "qvq_refine");
         }
         std::vector<Vector> codebook(K, Vector(D));
@@ -97,6 +97,7 @@ QuantizerPtr getQuantizer(Quantizers q) {
     return nullptr;
 }
 
-QuantizerPtr getRefinedLBGQuantizer(size_t maxIters, bool fresh) {
-    return QuantizerPtr(new HipLBGQuantizer(maxIters, fresh));
+QuantizerPtr getRefinedLBGQuantizer(size_t maxIters, bool fresh, bool reseed) {
+    if (reseed && maxIters == 0) throw std::invalid_argument("getRefinedLBGQuantizer: reseed needs maxIters > 0");
+    return QuantizerPtr(new HipLBGQuantizer(maxIters, fresh, reseed));
 }

@@ -20,6 +20,7 @@ public:
 struct RefineOptions {
     size_t maxIters = 0;
     bool fresh = false;
+    bool reseed = false;
 };
 bool engine_lbg_options(const AbstractQuantizer &q, RefineOptions &out);
 

@@ -424,6 +424,39 @@ hipError_t launch_count_changed(hipStream_t s, int num_cu, const uint32_t *A, co
 // a communicator).
 hipError_t launch_count_changed64(hipStream_t s, int num_cu, const uint32_t *A, const uint32_t *B, uint64_t N,
                                   uint64_t *out);
+// qvq_refine's empty-cell reseed (k_reseed.hip, reseed_rule.hpp; QVQ_REFINE_RESEED): scratch for K
+// cells in one allocation of reseed_layout(K).total bytes (offsets in bytes; the donors' lists
+// hold K rounded up to a power of two).
+struct ReseedWork {
+    unsigned *state = nullptr;     // [0] the iteration's empty cells (count adds, select clears)
+    uint64_t *E = nullptr;         // [K] the cells' summed quantised errors
+    uint64_t *far = nullptr;       // [K] the cells' far-row keys (reseed_far_key)
+    uint64_t *dE = nullptr;        // the donors' E, then sorted
+    uint32_t *cnt = nullptr;       // [K] the cells' rows
+    uint32_t *empties = nullptr;   // [K] the empty cells, ascending
+    uint32_t *dK = nullptr;        // the donors' cells
+};
+struct ReseedLayout {
+    uint64_t E = 0, far = 0, dE = 0, cnt = 0, empties = 0, dK = 0, total = 0;
+};
+ReseedLayout reseed_layout(uint32_t K);
+ReseedWork reseed_work(uint8_t *base, uint32_t K);
+// The rows pass: a lane per row, RSD_THREADS lanes per block, at most RSD_GRID_CAP blocks (more
+// rows: the grid-stride loop again).
+constexpr int RSD_THREADS = 256;
+constexpr int RSD_GRID_CAP = 512;
+// The three launches, in this order after the reduce: count reads the cells' rows from the reduced
+// sums (the finalize's copies, stride and gate: before the finalize that clears them) and leaves
+// the number of empty cells in w.state; rows (after the centroid step wrote C) and select return at
+// once when it is 0.  select writes the seeds into C and the number placed to *pub (mapped memory).
+// N < 2^32 - 1.
+hipError_t launch_reseed_count(hipStream_t s, const uint64_t *sums, uint32_t K, uint32_t D, uint32_t ncopy,
+                               uint64_t cstride, const unsigned *gate, const ReseedWork &w);
+hipError_t launch_reseed_rows(hipStream_t s, const uint8_t *codes, uint32_t Dp, uint32_t D, uint64_t N,
+                              const uint32_t *A, const double *C, uint32_t K, const double *lut64, bool scaled,
+                              const ReseedWork &w);
+hipError_t launch_reseed_select(hipStream_t s, const uint8_t *codes, uint32_t Dp, uint32_t D, uint64_t N,
+                                const double *lut64, double *C, uint32_t K, const ReseedWork &w, uint64_t *pub);
 hipError_t launch_gather_codes(hipStream_t s, const uint8_t *codes, uint32_t Dp, const uint32_t *rows, uint32_t n,
                                uint8_t *out);
 // Host-resolved rows: A[rows[i]] = vals[i]; with xslab their terms move from the

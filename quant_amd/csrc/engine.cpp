@@ -40,6 +40,7 @@
 #include "exact_plan.hpp"
 #include "kdtree.hpp"
 #include "qvq.h"
+#include "reseed_rule.hpp"
 #include "wait.hpp"
 
 namespace qvq {
@@ -345,7 +346,12 @@ struct qvq_ctx {
         double dist = 0;
         bool have_xsq = false;
         double xsq = 0, rows = 0;
+        // the last qvq_refine's seeds placed per iteration (all 0 without QVQ_REFINE_RESEED)
+        bool have_reseeds = false;
+        std::vector<uint64_t> reseeds;
     } rf;
+    uint8_t *d_reseed = nullptr;   // QVQ_REFINE_RESEED's scratch (reseed_layout), grown on demand
+    uint64_t reseed_bytes = 0;
 
     qvq_timings tm;
     HostTrace htrace;
@@ -2467,6 +2473,7 @@ QVQ_API void qvq_destroy(qvq_ctx *ctx) {
     dfree(ctx->d_mean);
     dfree(ctx->d_scatter);
     dfree(ctx->d_decode);
+    dfree(ctx->d_reseed);
     dfree(ctx->d_raster);
     dfree(ctx->d_decode_stat);
     if (ctx->h_decode_stat) (void)hipHostFree(ctx->h_decode_stat);
@@ -3540,6 +3547,7 @@ QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start, u
     if (!ctx) return QVQ_EINVAL;
     GUARD(ctx);
     const bool fresh = (flags & QVQ_REFINE_FRESH) != 0;
+    const bool reseed = (flags & QVQ_REFINE_RESEED) != 0;
     const bool cont = C_start == nullptr;
     const bool sharded = ctx->comm || ctx->host_ar;
     // this rank's own verdict on the call; with a communicator the ranks exchange it (below)
@@ -3551,11 +3559,13 @@ QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start, u
         lmsg = m;
     };
     if (ctx->N == 0) reject(QVQ_ESTATE, "no training set");
-    else if (flags & ~(uint32_t)QVQ_REFINE_FRESH) reject(QVQ_EINVAL, "unknown refine flags");
+    else if (flags & ~(uint32_t)(QVQ_REFINE_FRESH | QVQ_REFINE_RESEED)) reject(QVQ_EINVAL, "unknown refine flags");
     else if (max_iters == 0 && !fresh) reject(QVQ_EINVAL, "max_iters = 0 needs QVQ_REFINE_FRESH");
     else if (K == 0 || K > (1u << 20)) reject(QVQ_EINVAL, "K must be in 1 .. 2^20");
     else if (!(eps >= 0)) reject(QVQ_EINVAL, "eps must be >= 0");
     else if (ctx->exact) reject(QVQ_EUNSUPPORTED, "refinement of an exact-mode training set is not supported");
+    else if (reseed && sharded) reject(QVQ_EUNSUPPORTED, "QVQ_REFINE_RESEED is not supported on a communicator");
+    else if (reseed && ctx->N >= 0xFFFFFFFFull) reject(QVQ_EUNSUPPORTED, "QVQ_REFINE_RESEED takes fewer than 2^32 - 1 rows");
     else if (cont) {
         if (!ctx->rf.valid) reject(QVQ_ESTATE, "no qvq_lbg or qvq_refine result to continue from");
         else if (ctx->rf.K != K) reject(QVQ_EINVAL, "K differs from the result to continue from");
@@ -3600,10 +3610,24 @@ QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start, u
     if (lst != QVQ_OK) return fail(ctx, lst, lmsg);
     const double d0 = ctx->rf.dist;
     ctx->rf.valid = false;
+    ctx->rf.have_reseeds = true;
+    ctx->rf.reseeds.clear();
     HIPCHK(hipSetDevice(ctx->dev));
     qvq_status st = ensure_levels(ctx, std::max<uint32_t>(K, 2));
     if (st != QVQ_OK) return st;
     if (!ctx->d_A_alt) HIPCHK(hipMalloc(&ctx->d_A_alt, ctx->N * 4));
+    ReseedWork rw;
+    if (reseed) {
+        const uint64_t need = reseed_layout(K).total;
+        if (ctx->reseed_bytes < need) {
+            dfree(ctx->d_reseed);
+            ctx->reseed_bytes = 0;
+            HIPCHK(hipMalloc(&ctx->d_reseed, need));
+            ctx->reseed_bytes = need;
+        }
+        rw = reseed_work(ctx->d_reseed, K);
+        HIPCHK(hipMemsetAsync(rw.state, 0, 16, ctx->stream));   // (an abandoned call may have left a count)
+    }
     std::memset(&ctx->tm, 0, sizeof(ctx->tm));
     const uint32_t D = ctx->D;
     const uint64_t KD = (uint64_t)K * D;
@@ -3650,7 +3674,7 @@ QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start, u
     if ((st = clear_dirty_sums(ctx)) != QVQ_OK) return st;
     if (changed64) HIPCHK(hipMemsetAsync(changed64, 0, 8, ctx->stream));
     const LevelPlan plan = plan_level(ctx, K);   // every iteration's
-    volatile uint64_t *h_pub = ctx->h_ready + 4;   // [4] rows changed, [5] the distortion term
+    volatile uint64_t *h_pub = ctx->h_ready + 4;   // [4] rows changed, [5] the distortion term, [6] seeds placed
     // C_t's tables, tile order and host copy (t = 0, rs null: from the starting codebook; else the
     // centroid step over the sums rs describes: copy 1, kd_reduce_kernel's moves, is added and then
     // cleared under its gate), or without tables the distortion term of C_t under those sums
@@ -3668,6 +3692,33 @@ QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start, u
         return run_finalize(ctx, f);
     };
     if ((st = publish(0, true, nullptr, nullptr, false)) != QVQ_OK) return st;
+    // QVQ_REFINE_RESEED: the centroid step in four parts.  The cells' rows and the number of empty
+    // cells (before the finalize clears the sums' further copies and their gate); the centroids
+    // C_{t+1} alone, with the changed count and the distortion term (which the seeds leave as they
+    // are: an empty cell owns no row); the rows pass and the select, which seed C_{t+1} in place and
+    // publish the seeds placed; the tables, tile order and host copy from the seeded codebook, the
+    // form iteration 0 uses, which carries the ready number the host waits for.
+    auto publish_reseeded = [&](uint32_t t, const ReducedSums &rs, unsigned *cnts, bool count) -> qvq_status {
+        HIPCHK(launch_reseed_count(ctx->stream, ctx->d_sums, K, D, rs.copies,
+                                   rs.copies > 1 ? sums_cap_stride(ctx) : 0, rs.gate, rw));
+        FinArgs f = finalize_args(ctx, K, true);
+        sums_args(ctx, f, &rs, true);
+        if (count) f.changed = ctx->d_counters + CHANGED_COUNTER;
+        f.clear_cnt = cnts;
+        f.pub = ctx->dh_ready + 4;
+        f.seq = ++ctx->seq;
+        qvq_status s = run_finalize(ctx, f);
+        if (s != QVQ_OK) return s;
+        HIPCHK(launch_reseed_rows(ctx->stream, ctx->d_codes, ctx->Dp, D, ctx->N, ctx->d_A, ctx->d_C64_cent, K,
+                                  ctx->d_lut64, ctx->cs == QVQ_CS_SCALED, rw));
+        HIPCHK(launch_reseed_select(ctx->stream, ctx->d_codes, ctx->Dp, D, ctx->N, ctx->d_lut64, ctx->d_C64_cent, K, rw,
+                                    ctx->dh_ready + 6));
+        FinArgs g = finalize_args(ctx, K, true);
+        g.C_src = ctx->d_C64_cent;
+        tables_args(ctx, g, 1, ctx->d_C64_split, dev_cb_of(ctx, t), plan.prunable);
+        g.seq = ++ctx->seq;
+        return run_finalize(ctx, g);
+    };
 
     uint32_t t = 0;        // iterations done: C_t is the codebook, A_t (t >= 1, or continuing) in d_A
     int stop = -1;
@@ -3681,9 +3732,11 @@ QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start, u
         double term;
         std::memcpy(&term, &bits, 8);
         const double d = std::max(0.0, (xsq - term) / norm);
+        const uint64_t seeds = reseed ? h_pub[2] : 0;
+        ctx->rf.reseeds.push_back(seeds);
         if (changed) changed[t - 1] = chg;
         if (dist_trace) dist_trace[t - 1] = d;
-        if (chg == 0) stop = QVQ_STOP_FIXED;
+        if (chg == 0 && seeds == 0) stop = QVQ_STOP_FIXED;
         else if (have_dprev && std::fabs(d_prev - d) / d_prev <= eps) stop = QVQ_STOP_EPS;
         else if (t == max_iters) stop = QVQ_STOP_MAXIT;
         d_prev = d_last = d;
@@ -3730,7 +3783,9 @@ QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start, u
             HIPCHK(launch_count_changed(ctx->stream, ctx->num_cu, ctx->d_A, ctx->d_A_alt, ctx->N,
                                         ctx->d_counters + CHANGED_COUNTER));
         }
-        if ((st = publish(t + 1, true, &rs, ctx->d_counters + 2 * slot, have_A || changed64)) != QVQ_OK) return st;
+        if (reseed) st = publish_reseeded(t + 1, rs, ctx->d_counters + 2 * slot, have_A);
+        else st = publish(t + 1, true, &rs, ctx->d_counters + 2 * slot, have_A || changed64);
+        if (st != QVQ_OK) return st;
         have_A = true;
         t++;
     }
@@ -3746,6 +3801,17 @@ QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start, u
     ctx->rf.valid = true;
     ctx->rf.K = K;
     ctx->rf.dist = d_last;
+    return QVQ_OK;
+}
+
+QVQ_API qvq_status qvq_get_refine_reseeds(qvq_ctx *ctx, uint64_t *out, uint32_t cap, uint32_t *iters) {
+    if (!ctx) return QVQ_EINVAL;
+    GUARD(ctx);
+    if (!ctx->rf.have_reseeds) return fail(ctx, QVQ_ESTATE, "no qvq_refine has run");
+    if (cap && !out) return fail(ctx, QVQ_EINVAL, "null output");
+    const uint32_t n = (uint32_t)ctx->rf.reseeds.size();
+    for (uint32_t i = 0; i < std::min(n, cap); i++) out[i] = ctx->rf.reseeds[i];
+    if (iters) *iters = n;
     return QVQ_OK;
 }
 
@@ -4071,6 +4137,44 @@ QVQ_API qvq_status qvq_host_ingest_grid(qvq_ingest_grid *out) {
     if (!out) return QVQ_EINVAL;
     out->block = ING_THREADS;
     out->blocks = ING_GRID_CAP;
+    return QVQ_OK;
+}
+
+QVQ_API qvq_status qvq_host_reseed_grid(qvq_reseed_grid *out) {
+    if (!out) return QVQ_EINVAL;
+    out->block = RSD_THREADS;
+    out->blocks = RSD_GRID_CAP;
+    return QVQ_OK;
+}
+
+QVQ_API qvq_status qvq_host_row_error(const double *x, const double *c, uint32_t dim, int colorspace, uint32_t *q) {
+    if (!x || !c || !q || dim == 0 || dim > 64) return QVQ_EINVAL;
+    if (colorspace != QVQ_CS_NORMAL && colorspace != QVQ_CS_SCALED) return QVQ_EUNSUPPORTED;
+    *q = reseed_row_error([&](uint32_t d) { return x[d]; }, c, dim, reseed_shift(colorspace == QVQ_CS_SCALED));
+    return QVQ_OK;
+}
+
+QVQ_API qvq_status qvq_host_reseed_far_key(uint32_t q, uint32_t row, uint64_t *key) {
+    if (!key) return QVQ_EINVAL;
+    *key = reseed_far_key(q, row);
+    return QVQ_OK;
+}
+
+QVQ_API qvq_status qvq_host_reseed_select(const uint64_t *E, const uint64_t *n, const uint64_t *far, uint32_t K,
+                                          uint32_t *empties_out, uint32_t *rows_out, uint32_t *m) {
+    if (!E || !n || !far || !m || K == 0) return QVQ_EINVAL;
+    std::vector<uint32_t> empties, donors;
+    for (uint32_t k = 0; k < K; k++) {
+        if (n[k] == 0) empties.push_back(k);
+        if (reseed_is_donor(n[k], E[k])) donors.push_back(k);
+    }
+    std::sort(donors.begin(), donors.end(), [&](uint32_t a, uint32_t b) { return reseed_before(E[a], a, E[b], b); });
+    const uint32_t cnt = (uint32_t)std::min(empties.size(), donors.size());
+    for (uint32_t j = 0; j < cnt; j++) {
+        if (empties_out) empties_out[j] = empties[j];
+        if (rows_out) rows_out[j] = reseed_far_row(far[donors[j]]);
+    }
+    *m = cnt;
     return QVQ_OK;
 }
 
