@@ -1,6 +1,5 @@
 // engine.cpp -- host side of the qvq engine: context, per-level schedule, kd-tree builds,
-// RCCL exchange and the C ABI of include/qvq.h.  No kernels here; the HIP kernels and
-// their launch wrappers live in k_assign.hip and k_misc.hip.
+// RCCL exchange and the C ABI of include/qvq.h.  No kernels here.
 //
 // Per split level (LBGIterate, src/Quantizer.cpp:98-108, one effective Lloyd step), all on
 // one stream with no host round trip:
@@ -39,6 +38,7 @@
 #include "common.hpp"
 #include "exact_plan.hpp"
 #include "kdtree.hpp"
+#include "owned.hpp"
 #include "qvq.h"
 #include "reseed_rule.hpp"
 #include "wait.hpp"
@@ -145,102 +145,162 @@ struct HostTrace {
     }
 };
 
+// The context owns its device memory, pinned memory, streams and events through the handles of
+// owned.hpp, grouped by lifetime: what is made with the context, the training set
+// (ts), the level buffers of one Kcap (lv), the Kahan state (kh) and scratch that only grows.  A
+// group is rebuilt in a local and moved in when every allocation has succeeded, and dropped by
+// assigning an empty one.  Members are destroyed in reverse order: the streams come first.
 struct qvq_ctx {
     int dev = 0;
     int num_cu = 256;
-    hipStream_t stream = nullptr;
     std::string err;
+    // stream: every call's work; kstream: the device tree build (first use: ensure_levels);
+    // vstream: the speculative check's selected Kahan sums (first use: ensure_speculation)
+    Stream stream, kstream, vstream;
 
-    // training set
-    uint64_t N = 0;
-    uint32_t D = 0, Dp = 0;
-    // exact mode (qvq_set_vectors_exact, or qvq_set_vectors on values that are not byte images):
-    // the fp64 rows themselves and the reference's Kahan arithmetic (k_exact.hip)
-    bool exact = false;
-    int exact_cs = -1;   // the colour space whose raster the exact rows came from (QVQ_CS_CIE1931), -1: fp64 rows
-    double *d_X64 = nullptr;
-    uint32_t *d_ex_keys = nullptr, *d_ex_iota = nullptr, *d_ex_order = nullptr;
-    void *d_ex_temp = nullptr;
-    size_t ex_temp_bytes = 0;
-    uint32_t *d_ex_koff = nullptr;
-    uint32_t ex_kcap = 0;
-    int cs = -1;
-    Terms terms;
-    int mf_t = 0;            // MFMA score scale exponent
-    MfThresholds mf_th{};
-    uint8_t *d_codes = nullptr;
-    float *d_lut32 = nullptr, *d_w = nullptr;
-    double *d_lut64 = nullptr;
-    uint64_t *d_plut = nullptr;
-    uint32_t *d_A = nullptr, *d_flags = nullptr, *d_ties = nullptr;
-    // the previous level's final assignment (qvq_lbg swaps the two each level): the input of
-    // the reference-bit (Kahan) centroids a level with kd-tree ties needs
-    uint32_t *d_A_alt = nullptr;
-    KahanWork kw;
-    double *d_kc_cent = nullptr, *d_kc_split = nullptr;   // Kahan centroids [K/2][D], their split [K][D]
-    uint32_t kc_kcap = 0;
+    // ---- made with the context (qvq_create), kept to qvq_destroy
+    DevBuf<float> d_lut32, d_w;   // the resident colour space's tables (alloc_training uploads them)
+    DevBuf<double> d_lut64;
+    DevBuf<uint64_t> d_plut;
+    DevBuf<unsigned> d_counters;   // per level: [2l] flagged rows, [2l+1] kd-tree ties; [66], [67] block counters;
+                                   // [68], [69] the pruned wide search's task counters (SCHED_COUNTERS)
+    DevBuf<uint64_t> d_hist;       // byte histogram [256] | its all-reduced copy [256]
+    DevBuf<double> d_dist_part;
+    DevBuf<uint64_t> d_mean;   // MEAN_COPIES x mean sums [hi D][lo D][n]: zero between quantizes (the finalize clears them)
+    DevBuf<uint64_t> d_decode_stat;      // decode: [squared error, bad-index flag]
+    PinnedBuf<uint64_t> h_decode_stat;   // pinned host copy
+    // mapped, coherent: [0, 64) the codebook ready number, [64, 1024) a quantize's small results
+    CoherentBuf<uint64_t> h_ready;
+    Event ev[32][4], ev_end;
+    Event ev_sync;   // wait_stream
+    Event ev_kcb, ev_kdb;   // the device tree build's (first use: ensure_levels)
+    // the fp64 front door (k_ingest.hip): both spaces' value tables [2][256], the classify pass's
+    // verdict and its pinned copy; events around the passes and their device ms (qvq_set_timing(-3))
+    DevBuf<double> d_ing_tab;
+    DevBuf<unsigned> d_ing_verdict;
+    PinnedBuf<unsigned> h_ing_verdict;
+    Event ev_ing[3];
+    double ingest_ms[2] = {0, 0};
+    uint32_t G = 0;   // workgroup slabs
+    // the speculative check's tie exports (TieExport, level % 3), mapped; made once (ensure_speculation)
+    MappedBuf<uint8_t> h_tx[3];
+    uint32_t tx_cap = 0;
+
+    // ---- the training set: replaced as a whole by alloc_training / install_exact (N == 0: none)
+    struct Training {
+        uint64_t N = 0;
+        uint32_t D = 0, Dp = 0;
+        int cs = -1;
+        Terms terms;
+        int mf_t = 0;            // MFMA score scale exponent
+        MfThresholds mf_th{};
+        double tie_abs = 0;      // the recheck's absolute tie band: centroid bits may differ by this much
+        DevBuf<uint8_t> d_codes;
+        DevBuf<uint32_t> d_flags, d_ties;
+        DevBuf<uint32_t> d_sortbuf;   // sorted-order sums: idx [N] | ks [N] (first use: run_update_slabs)
+        // The assignment buffers, N indices each, grown by ensure_apool: one with the set, a second
+        // for the previous level's assignment (Kahan levels, qvq_refine), four for the speculative
+        // check, one per level with several ranks.
+        std::vector<DevBuf<uint32_t>> apool;
+        // Views of apool that qvq_lbg and qvq_refine rotate: d_A the current assignment, d_A_alt the
+        // previous level's (the input of the reference-bit centroids a level with kd-tree ties
+        // needs), d_A3 / d_A4 the two levels the speculative check still reads
+        uint32_t *d_A = nullptr, *d_A_alt = nullptr, *d_A3 = nullptr, *d_A4 = nullptr;
+        // exact mode (qvq_set_vectors_exact, or qvq_set_vectors on values that are not byte images):
+        // the fp64 rows themselves and the reference's Kahan arithmetic (k_exact.hip)
+        bool exact = false;
+        int exact_cs = -1;   // the colour space whose raster the exact rows came from (QVQ_CS_CIE1931), -1: fp64 rows
+        struct Exact {
+            DevBuf<double> d_X64;
+            DevBuf<uint32_t> d_keys, d_iota, d_order, d_koff;
+            DevBuf<uint8_t> d_temp;
+            size_t temp_bytes = 0;
+        } ex;
+    } ts;
+
+    // ---- level buffers for up to Kcap code vectors: replaced as a whole by ensure_levels
+    struct Levels {
+        uint32_t Kcap = 0;
+        DevBuf<double> d_C64_cent, d_C64_split;
+        DevBuf<double> d_C64_split_alt;   // qvq_lbg's next split while d_C64_split may still be needed
+        DevBuf<float> d_C32;
+        DevBuf<float> d_E32;   // D = 12: expanded fp32 terms for the small-K scan
+        DevBuf<_Float16> d_rows;   // MFMA code-vector rows
+        DevBuf<uint32_t> d_perm;   // pruned search: tile order of the split codebook (finalize's prune_order)
+        DevBuf<int32_t> d_tint;    // ... and the tiles' projection envelopes
+        uint32_t perm_k = 0;       // the K whose order d_perm holds (0: none)
+        DevBuf<uint64_t> d_part, d_sums;
+        DevBuf<uint32_t> d_part_cnt;
+        // mapped pinned host memory (coherent): the split codebooks the finalizes publish for the
+        // host, two halves of cb_half doubles (host_cb_of): level L's codebook in half L & 1;
+        // two flattened kd-tree images
+        CoherentBuf<double> h_cb;
+        uint64_t cb_half = 0;
+        CoherentBuf<uint8_t> h_tree[2];
+        DevBuf<uint8_t> d_tree;   // device copy of the level's tree image (one DMA per level)
+        uint64_t tree_cap = 0;
+        // the level's kd-tree built on the device (k_kdbuild.hip) on kstream, beside the search:
+        // scratch (vind, nodes, boxes) and the mapped host image of the whole tree
+        DevBuf<uint32_t> d_kdb_vind;
+        DevBuf<KdbNode> d_kdb_nodes;
+        DevBuf<double> d_kdb_nbox, d_kdb_cbox;
+        CoherentBuf<uint8_t> h_kdb;
+        uint32_t kdb_cap = 0;   // code vectors the scratch takes (0: none)
+    } lv;
+    uint64_t seq = 0;
+    uint64_t kdb_seq = 0;         // the device tree build's launch number
+    uint64_t out_seq = 0;         // quantizes whose results copy_out has published
+    uint64_t pub_seq = 0;         // per-level tie-count publications (h_ready[1] = seq, h_ready[2] = ties)
+    // copy 1 of d_sums may hold moves that no finalize has taken (a call that stopped between the
+    // two): raised by mark_sums1, lowered by run_finalize and clear_dirty_sums, nowhere else
+    bool sums1_dirty = false;
+
+    // ---- Kahan state of the training set: dropped with it, rebuilt in parts by ensure_kahan
+    struct Kahan {
+        struct Cells {   // for up to kcap cells
+            uint32_t kcap = 0;
+            DevBuf<double> d_kc_cent, d_kc_split;   // Kahan centroids [K/2][D], their split [K][D]
+            DevBuf<uint32_t> d_kc_sel;     // [K/2] slot + 1 of the cells a tie certificate sums (0: not summed)
+            PinnedBuf<uint32_t> h_kc_sel;  // its pinned host side
+            MappedBuf<double> h_kc_out;    // [K][D] mapped: the selected cells' split rows
+        } cells;
+        struct Work {   // what kw views (common.hpp KahanWork, the launch wrappers' plain struct)
+            DevBuf<uint32_t> hist, tot, koff, segoff, blkoff;
+            DevBuf<uint8_t> planes, meta, bsum, bfn, sfn, bfn8, tab;
+            DevBuf<unsigned> stats;
+        } work;
+        KahanWork kw;   // view of work, and its capacities
+        DevBuf<uint64_t> d_kc_chain;   // chained Kahan sums: gather | state (k_kahan.hip), grown on demand
+        // several ranks: the checks whose rows wait for cells summed over every rank's rows (status
+        // 2), finished together at the end of qvq_lbg; A_prev stays valid (one assignment buffer per level)
+        struct Deferred {
+            uint32_t level = 0, K = 0;
+            const uint32_t *A_prev = nullptr;   // view of an apool buffer
+            std::unique_ptr<RefKDTree> tree;
+            std::vector<double> cb;
+            CertState cs;
+        };
+        std::vector<Deferred> deferred;
+    } kh;
     std::vector<double> h_kc_split;   // host copy of the split for the tree build
-    uint32_t *d_kc_sel = nullptr;     // [K/2] slot + 1 of the cells a tie certificate sums (0: not summed)
-    uint32_t *h_kc_sel = nullptr;     // its pinned host side
-    double *h_kc_out = nullptr, *dh_kc_out = nullptr;   // [K][D] mapped: the selected cells' split rows
     std::vector<double> cert_kp;      // the reference's split where known (tie certificate)
     std::vector<uint8_t> cert_known;
     std::vector<uint32_t> cert_vals;  // the certified answers (host side of their upload)
-    uint64_t pub_seq = 0;          // per-level tie-count publications (h_ready[1] = seq, h_ready[2] = ties)
-    double tie_abs = 0;            // the recheck's absolute tie band: centroid bits may differ by this much
-    unsigned *d_counters = nullptr;   // per level: [2l] flagged rows, [2l+1] kd-tree ties; [66], [67] block counters;
-                                      // [68], [69] the pruned wide search's task counters (SCHED_COUNTERS)
-    uint64_t *d_hist = nullptr;       // byte histogram [256] | its all-reduced copy [256]
 
-    // level buffers
-    uint32_t Kcap = 0;
-    uint32_t G = 0;   // workgroup slabs
-    double *d_C64_cent = nullptr, *d_C64_split = nullptr;
-    double *d_C64_split_alt = nullptr;   // qvq_lbg's next split while d_C64_split may still be needed
-    float *d_C32 = nullptr;
-    float *d_E32 = nullptr;   // D = 12: expanded fp32 terms for the small-K scan
-    _Float16 *d_rows = nullptr;   // MFMA code-vector rows
-    uint32_t *d_perm = nullptr;   // pruned search: tile order of the split codebook (finalize's prune_order)
-    int32_t *d_tint = nullptr;    // ... and the tiles' projection envelopes
-    uint32_t perm_k = 0;          // the K whose order d_perm holds (0: none)
-    uint64_t *d_part = nullptr, *d_sums = nullptr;
-    uint32_t *d_part_cnt = nullptr;
-    double *d_dist_part = nullptr;
-    uint64_t *d_mean = nullptr;   // MEAN_COPIES x mean sums [hi D][lo D][n]: zero between quantizes (the finalize clears them)
-    uint64_t out_seq = 0;         // quantizes whose results copy_out has published
-    uint32_t *d_scatter = nullptr;
-    uint32_t *d_sortbuf = nullptr;   // sorted-order sums: idx [N] | ks [N]
-    uint64_t scatter_bytes = 0;
-    uint8_t *d_raster = nullptr;          // qvq_set_images' raster upload buffer (grown on demand)
-    uint64_t raster_bytes = 0;
-    uint8_t *d_decode = nullptr;          // qvq_decode's and qvq_get_vectors' scratch (grown on demand)
-    uint64_t decode_bytes = 0;
-    uint64_t *d_decode_stat = nullptr;    // decode: [squared error, bad-index flag]
-    uint64_t *h_decode_stat = nullptr;    // pinned host copy
-    // mapped pinned host memory (coherent): the split codebook finalize writes for the
-    // host's tree build, its ready sequence number, and two flattened kd-tree images
-    // the split codebooks the finalizes publish for the host, two halves of cb_half doubles
-    // (host_cb_of): level L's codebook in half L & 1
-    double *h_cb = nullptr, *dh_cb = nullptr;
-    uint64_t cb_half = 0;
-    uint64_t *h_ready = nullptr, *dh_ready = nullptr;
-    uint64_t seq = 0;
-    uint8_t *h_tree[2] = {nullptr, nullptr}, *dh_tree[2] = {nullptr, nullptr};
-    uint8_t *d_tree = nullptr;   // device copy of the level's tree image (one DMA per level)
-    // the level's kd-tree built on the device (k_kdbuild.hip) on kstream, beside the search:
-    // scratch (vind, nodes, boxes), the mapped host image of the whole tree, its launch number
-    hipStream_t kstream = nullptr;
-    hipEvent_t ev_kcb = nullptr, ev_kdb = nullptr;
-    uint32_t *d_kdb_vind = nullptr;
-    KdbNode *d_kdb_nodes = nullptr;
-    double *d_kdb_nbox = nullptr, *d_kdb_cbox = nullptr;
-    uint8_t *h_kdb = nullptr, *dh_kdb = nullptr;
-    uint32_t kdb_cap = 0;   // code vectors the scratch takes (0: none)
-    uint64_t kdb_seq = 0;
+    // ---- scratch, grown on demand (ensure) and kept to qvq_destroy
+    DevBuf<uint32_t> d_scatter;          // the host-resolved tie rows' uploads
+    DevBuf<uint8_t> d_raster;            // qvq_set_images' raster upload buffer
+    DevBuf<uint8_t> d_decode;            // qvq_decode's and qvq_get_vectors' scratch
+    DevBuf<uint8_t> d_reseed;            // QVQ_REFINE_RESEED's scratch (reseed_layout)
+    DevBuf<uint64_t> d_vote;             // the ranks' small all-reduced decisions (qvq_lbg)
+    PinnedBuf<uint64_t> h_vote;
+    PinnedBuf<uint8_t> h_ar_stage;       // pinned staging of the host all-reduce
+    PinnedBuf<uint8_t> h_stage;          // pinned staging of qvq_update's results
+
     std::vector<double> cb_local;   // host copy of the published codebook for the tree build
     std::vector<uint32_t> cnt_local;   // ... and of its parent cells' row counts (empty: not known)
     std::unique_ptr<RefKDTree> tree;   // the last level's tree over cb_local
-    KdView tree_kd;                    // and its device image (depth 0: none)
+    KdView tree_kd;                    // and its device image: a view of lv.d_tree or lv.h_tree[] (depth 0: none)
     // deferred-tie levels build their tree on this worker, off the launch path (start_tree_job)
     struct Worker {   // one host thread, jobs in order
         std::thread th;
@@ -267,10 +327,6 @@ struct qvq_ctx {
     // the speculative Kahan check (qvq_lbg): level L's ties verified on the worker while the GPU
     // runs levels L + 1 and L + 2; four assignment buffers keep A_{L-1} (the check's cells)
     // until level L + 3, when the check is joined
-    uint32_t *d_A3 = nullptr, *d_A4 = nullptr;
-    uint8_t *h_tx[3] = {nullptr, nullptr, nullptr}, *dh_tx[3] = {nullptr, nullptr, nullptr};   // TieExport, level % 3
-    uint32_t tx_cap = 0;
-    hipStream_t vstream = nullptr;   // the check's selected Kahan sums
     struct Verify {
         bool posted = false;
         std::atomic<bool> done{true}, cancel{false};
@@ -278,63 +334,30 @@ struct qvq_ctx {
         uint32_t K = 0, level = 0;
         uint64_t seq = 0;
         int par = 0;
-        const uint32_t *A_prev = nullptr;
+        const uint32_t *A_prev = nullptr;   // view of an apool buffer
         std::unique_ptr<RefKDTree> tree;
         std::vector<double> cb;
         std::vector<uint32_t> cnt;   // the parent cells' row counts (empty: not known)
         CertState cs;
-        hipEvent_t ev = nullptr;
+        Event ev;   // made once (ensure_speculation)
     } ver[3];   // level % 3
-    // several ranks: the checks whose rows wait for cells summed over every rank's rows (status
-    // 2), finished together at the end of qvq_lbg; A_prev stays valid (one assignment buffer per
-    // level, d_Aext)
-    struct Deferred {
-        uint32_t level = 0, K = 0;
-        const uint32_t *A_prev = nullptr;
-        std::unique_ptr<RefKDTree> tree;
-        std::vector<double> cb;
-        CertState cs;
-    };
-    std::vector<Deferred> deferred;
-    std::vector<uint32_t *> d_Aext;   // assignment buffers beyond the four (several ranks: one per level)
-    uint64_t *d_vote = nullptr, *h_vote = nullptr;   // the ranks' small all-reduced decisions (qvq_lbg)
-    uint64_t vote_cap = 0;
-    uint64_t *d_kc_chain = nullptr;   // chained Kahan sums: gather | state (k_kahan.hip)
-    uint64_t kc_chain_cap = 0;
     std::atomic<bool> tree_cancel{false};
     bool tree_job = false, job_ok = false;
     int job_buf = 0;
-    KdView job_kd;
-    uint64_t tree_cap = 0;
+    KdView job_kd;   // the tree job's image: a view of lv.h_tree[job_buf]
     uint32_t col_blocks = 0;   // blocks per image column (consecutive rows run down a column); 0: no image
-    // copy 1 of d_sums may hold moves that no finalize has taken (a call that stopped between the
-    // two): raised by mark_sums1, lowered by run_finalize and clear_dirty_sums, nowhere else
-    bool sums1_dirty = false;
-    uint64_t sums_bytes = 0;
     int timing_level = -2;   // qvq_set_timing: -1 all levels, -2 none (default), else that level only
-    hipEvent_t ev_end = nullptr;
-    hipEvent_t ev_sync = nullptr;   // wait_stream
-    // the fp64 front door (k_ingest.hip): both spaces' value tables [2][256], the classify pass's
-    // verdict and its pinned copy; events around the passes and their device ms (qvq_set_timing(-3))
-    double *d_ing_tab = nullptr;
-    unsigned *d_ing_verdict = nullptr, *h_ing_verdict = nullptr;
-    hipEvent_t ev_ing[3] = {nullptr, nullptr, nullptr};
-    double ingest_ms[2] = {0, 0};
     double timeout_s = 120;         // bound of every host wait (qvq_set_timeout, QVQ_TIMEOUT_S)
 
     // multi-GPU: an RCCL communicator, or (tests) a host all-reduce callback
     ncclComm_t comm = nullptr;
     qvq_allreduce_fn host_ar = nullptr;
-    void *host_ar_user = nullptr;
-    void *h_ar_stage = nullptr;   // pinned staging of the host all-reduce
-    uint64_t ar_stage_bytes = 0;
+    void *host_ar_user = nullptr;   // the caller's, passed back to host_ar
     int nranks = 1, rank = 0;
     // a bounded wait failed while work may still be queued on the stream: every later call
     // returns QVQ_ESTATE until qvq_destroy (results must not land in freed memory,
     // and the stream's scratch must not be reused under running kernels)
     bool poisoned = false;
-    void *h_stage = nullptr;      // pinned staging of qvq_update's results
-    uint64_t stage_bytes = 0;
 
     // qvq_refine's starting point when it is given none: the last successful qvq_lbg or qvq_refine
     // on the resident rows (K code vectors in d_C64_cent, their assignment in d_A, its distortion);
@@ -350,13 +373,9 @@ struct qvq_ctx {
         bool have_reseeds = false;
         std::vector<uint64_t> reseeds;
     } rf;
-    uint8_t *d_reseed = nullptr;   // QVQ_REFINE_RESEED's scratch (reseed_layout), grown on demand
-    uint64_t reseed_bytes = 0;
 
     qvq_timings tm;
     HostTrace htrace;
-    hipEvent_t ev[32][4];
-    bool ev_ready = false;
 };
 
 namespace {
@@ -390,12 +409,6 @@ qvq_status fail(qvq_ctx *c, qvq_status st, const std::string &msg) {
         if (r_ != ncclSuccess)                                                                        \
             return fail(ctx, QVQ_ECOMM, std::string(#expr) + ": " + ncclGetErrorString(r_));          \
     } while (0)
-
-template <typename T>
-void dfree(T *&p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
 
 uint32_t pad32(uint32_t K) { return (K + 31) & ~31u; }   // MFMA tile pairs
 bool env_is(const char *name, const char *val) {
@@ -473,90 +486,7 @@ LevelPlan plan_level(uint32_t D, uint32_t Dp, uint64_t N, uint32_t K) {
     p.tree_shape = kd_build_fits(K, D) && (uint64_t)K * D >= KDB_MIN_KD;
     return p;
 }
-LevelPlan plan_level(const qvq_ctx *ctx, uint32_t K) { return plan_level(ctx->D, ctx->Dp, ctx->N, K); }
-
-void free_kahan_work(KahanWork &w) {
-    for (uint32_t **p : {&w.hist, &w.tot, &w.koff, &w.segoff, &w.blkoff}) dfree(*p);
-    dfree(w.planes);
-    dfree(w.stats);
-    for (void **p : {&w.meta, &w.bsum, &w.bfn, &w.sfn, &w.bfn8, &w.tab})
-        if (*p) (void)hipFree(*p), *p = nullptr;
-    w.seg_cap = w.blk_cap = w.n_cap = 0;
-    w.k_cap = w.d_cap = 0;
-}
-
-void free_kahan(qvq_ctx *ctx) {
-    free_kahan_work(ctx->kw);
-    dfree(ctx->d_kc_chain);
-    ctx->kc_chain_cap = 0;
-    dfree(ctx->d_kc_cent);
-    dfree(ctx->d_kc_split);
-    dfree(ctx->d_kc_sel);
-    if (ctx->h_kc_sel) (void)hipHostFree(ctx->h_kc_sel);
-    if (ctx->h_kc_out) (void)hipHostFree(ctx->h_kc_out);
-    ctx->h_kc_sel = nullptr;
-    ctx->h_kc_out = ctx->dh_kc_out = nullptr;
-    ctx->kc_kcap = 0;
-}
-
-void free_training(qvq_ctx *ctx) {
-    free_kahan(ctx);
-    dfree(ctx->d_A_alt);
-    dfree(ctx->d_A3);
-    dfree(ctx->d_A4);
-    for (uint32_t *&p : ctx->d_Aext) dfree(p);
-    ctx->d_Aext.clear();
-    ctx->deferred.clear();
-    dfree(ctx->d_X64);
-    dfree(ctx->d_ex_keys);
-    dfree(ctx->d_ex_iota);
-    dfree(ctx->d_ex_order);
-    if (ctx->d_ex_temp) (void)hipFree(ctx->d_ex_temp);
-    ctx->d_ex_temp = nullptr;
-    ctx->ex_temp_bytes = 0;
-    dfree(ctx->d_ex_koff);
-    ctx->ex_kcap = 0;
-    ctx->exact = false;
-    ctx->exact_cs = -1;
-    dfree(ctx->d_sortbuf);
-    dfree(ctx->d_codes);
-    dfree(ctx->d_A);
-    dfree(ctx->d_flags);
-    dfree(ctx->d_ties);
-    ctx->N = 0;
-    ctx->D = ctx->Dp = 0;
-}
-
-void free_levels(qvq_ctx *ctx) {
-    dfree(ctx->d_C64_cent);
-    dfree(ctx->d_C64_split);
-    dfree(ctx->d_C64_split_alt);
-    dfree(ctx->d_C32);
-    dfree(ctx->d_E32);
-    dfree(ctx->d_rows);
-    dfree(ctx->d_perm);
-    dfree(ctx->d_tint);
-    ctx->perm_k = 0;
-    dfree(ctx->d_part);
-    dfree(ctx->d_part_cnt);
-    dfree(ctx->d_sums);
-    if (ctx->h_cb) (void)hipHostFree(ctx->h_cb);
-    ctx->h_cb = ctx->dh_cb = nullptr;
-    for (int b = 0; b < 2; b++) {
-        if (ctx->h_tree[b]) (void)hipHostFree(ctx->h_tree[b]);
-        ctx->h_tree[b] = ctx->dh_tree[b] = nullptr;
-    }
-    dfree(ctx->d_tree);
-    ctx->tree_cap = 0;
-    dfree(ctx->d_kdb_vind);
-    dfree(ctx->d_kdb_nodes);
-    dfree(ctx->d_kdb_nbox);
-    dfree(ctx->d_kdb_cbox);
-    if (ctx->h_kdb) (void)hipHostFree(ctx->h_kdb);
-    ctx->h_kdb = ctx->dh_kdb = nullptr;
-    ctx->kdb_cap = 0;
-    ctx->Kcap = 0;
-}
+LevelPlan plan_level(const qvq_ctx *ctx, uint32_t K) { return plan_level(ctx->ts.D, ctx->ts.Dp, ctx->ts.N, K); }
 
 // Flattened tree: root box lo[D], hi[D] | nodes[<= 2K] | vind[K].
 uint64_t tree_bytes(uint32_t K, uint32_t D) {
@@ -577,9 +507,9 @@ void codebook_range(const Terms &t, double &vmin, double &vmax, double &cmin, do
 }
 
 // MFMA score scale and error bounds for the near-tie flag ("near-tie flags").
-void mfma_setup(qvq_ctx *ctx) {
-    const Terms &t = ctx->terms;
-    const double D = ctx->D;
+void mfma_setup(qvq_ctx::Training &ts) {
+    const Terms &t = ts.terms;
+    const double D = ts.D;
     double vmin, vmax, cmin, cmax, wmax = 0;
     codebook_range(t, vmin, vmax, cmin, cmax);
     for (int b = 0; b < 256; b++) wmax = std::max(wmax, (double)std::fabs(t.w[b]));
@@ -590,18 +520,18 @@ void mfma_setup(qvq_ctx *ctx) {
     int tt = 0;
     while (std::ldexp(n_max, tt + 1) <= 60000.0 && std::ldexp(s_bound, tt + 1) <= 120000.0) tt++;
     while (std::ldexp(n_max, tt) > 60000.0 || std::ldexp(s_bound, tt) > 120000.0) tt--;
-    ctx->mf_t = tt;
+    ts.mf_t = tt;
     const double u = std::ldexp(1.0, -24);
     // one MFMA score: <= (slots + 1) sequential fp32 roundings over the terms (D = 12: 32
     // slots in one MFMA; wide layout: KS chained MFMAs of 32 slots), the f16 hi/lo split
     // (2^-22 relative + 2^-25 absolute per operand, scaled back), the fp32 scale/shift of
     // the score and of ||x - mu||^2, x ~ mu + w*sx (2^-53)
-    const double rounds = ctx->D == MF_D ? 33.0 : 32.0 * wide_ks(ctx->Dp) + 1.0;
+    const double rounds = ts.D == MF_D ? 33.0 : 32.0 * wide_ks(ts.Dp) + 1.0;
     const double e_acc = rounds * u * s_bound;
     const double e_rep = D * wmax * (c2_max * std::ldexp(1.0, -22) + std::ldexp(1.0, -25 - tt)) +
                          n_max * std::ldexp(1.0, -22) + std::ldexp(1.0, -25 - tt);
     const double e_conv = 4 * u * (s_bound + D * cp * cp) + 1e-12 * s_bound;
-    ctx->mf_th.mfma = (float)(1.25 * (e_acc + e_rep + e_conv));
+    ts.mf_th.mfma = (float)(1.25 * (e_acc + e_rep + e_conv));
     // The same bound for one row, with sum_d |w_d| of that row in place of D * wmax (every term
     // above is linear in it): S_row = n_max + c2_max * sum|w| replaces s_bound.
     {
@@ -609,15 +539,15 @@ void mfma_setup(qvq_ctx *ctx) {
         const double a0 = rounds * u * n_max + (n_max * std::ldexp(1.0, -22) + ew) + 4 * u * (n_max + D * cp * cp) +
                           1e-12 * n_max;
         const double a1 = rounds * u * c2_max + (c2_max * std::ldexp(1.0, -22) + ew) + 4 * u * c2_max + 1e-12 * c2_max;
-        ctx->mf_th.m0 = (float)(1.25 * a0 * 1.0001);
-        ctx->mf_th.m1 = (float)(1.25 * a1 * 1.0001);
+        ts.mf_th.m0 = (float)(1.25 * a0 * 1.0001);
+        ts.mf_th.m1 = (float)(1.25 * a1 * 1.0001);
     }
     // direct-form fp32 recompute (same bound as the VALU search)
     const double L = std::sqrt(D) * (std::max(std::fabs(vmin), std::fabs(vmax)) + std::max(std::fabs(cmin), std::fabs(cmax))) * 1.001;
-    ctx->mf_th.alpha = (float)(3.0 * 4.01 * u * L);   // x in fp32 is mu + w*sx: <= 2u relative
-    ctx->mf_th.beta = (float)(2.0 * ((ctx->Dp + 4) * u * 1.01 + 4e-15));
-    ctx->mf_th.gamma = (float)(2.0 * 4.01 * u * u * L * L + 1e-30);
-    ctx->mf_th.inv_scale = (float)std::ldexp(1.0, -tt);
+    ts.mf_th.alpha = (float)(3.0 * 4.01 * u * L);   // x in fp32 is mu + w*sx: <= 2u relative
+    ts.mf_th.beta = (float)(2.0 * ((ts.Dp + 4) * u * 1.01 + 4e-15));
+    ts.mf_th.gamma = (float)(2.0 * 4.01 * u * u * L * L + 1e-30);
+    ts.mf_th.inv_scale = (float)std::ldexp(1.0, -tt);
     // small-K scan (assign_small_kernel): each expanded score is an fp32 fma chain from n over
     // the D terms w_d * c''_d, with n and c'' rounded to fp32 once and w exact, so its error is
     // at most (D + 1) u (1 + u)^D (n + sum_d |w_d| |c''_d|) <= (D + 2) u S_row; two scores are
@@ -625,10 +555,31 @@ void mfma_setup(qvq_ctx *ctx) {
     // reference's own fp64 rounding (as e_conv above).
     const double sc = std::ldexp(1.0, tt);
     const double ks = 2.0 * (D + 2) * u * 1.01;
-    ctx->mf_th.e0 = (float)((ks * n_max + 1e-11 * s_bound) * sc * 1.0001);
-    ctx->mf_th.e1 = (float)(ks * c2_max * sc * 1.0001);
-    ctx->mf_th.mu = (float)t.mu;
-    ctx->mf_th.sx = (float)t.sx;
+    ts.mf_th.e0 = (float)((ks * n_max + 1e-11 * s_bound) * sc * 1.0001);
+    ts.mf_th.e1 = (float)(ks * c2_max * sc * 1.0001);
+    ts.mf_th.mu = (float)t.mu;
+    ts.mf_th.sx = (float)t.sx;
+}
+
+// The assignment pool grown to n buffers of N indices.  A view not yet set takes the buffer at its
+// own position: the views set so far are a permutation of the buffers before it.
+qvq_status ensure_apool(qvq_ctx *ctx, qvq_ctx::Training &ts, size_t n) {
+    while (ts.apool.size() < n) {
+        DevBuf<uint32_t> b;
+        HIPCHK(b.alloc(ts.N));
+        ts.apool.push_back(std::move(b));
+    }
+    uint32_t **views[4] = {&ts.d_A, &ts.d_A_alt, &ts.d_A3, &ts.d_A4};
+    for (size_t i = 0; i < 4 && i < ts.apool.size(); i++)
+        if (!*views[i]) *views[i] = ts.apool[i];
+    return QVQ_OK;
+}
+
+// The resident set and everything sized by it dropped (the context then holds no training set).
+void drop_training(qvq_ctx *ctx) {
+    ctx->kh = {};
+    ctx->ts = {};
+    ctx->lv = {};
 }
 
 // Allocate the per-row buffers and upload the colour-space tables.
@@ -639,114 +590,112 @@ qvq_status alloc_training(qvq_ctx *ctx, uint64_t N, uint32_t D, int cs) {
     const uint32_t Dp = (D + 3) & ~3u;
     if (Dp > 64) return fail(ctx, QVQ_EINVAL, "block dimension above 64 (3*w*h) is not supported");
     // the same shape again (repeated compresses of one image size): keep every buffer
-    if (!ctx->exact && ctx->d_codes && ctx->N == N && ctx->D == D && ctx->cs == cs) return QVQ_OK;
-    free_training(ctx);
-    free_levels(ctx);
-    if (!make_terms(cs, ctx->terms)) return fail(ctx, QVQ_EUNSUPPORTED, "colour space has no exact byte sums");
-    ctx->N = N;
-    ctx->D = D;
-    ctx->Dp = Dp;
-    ctx->cs = cs;
-    mfma_setup(ctx);
-    HIPCHK(hipMalloc(&ctx->d_codes, N * Dp));
-    HIPCHK(hipMalloc(&ctx->d_A, N * 4));
-    HIPCHK(hipMalloc(&ctx->d_flags, N * 4));
-    HIPCHK(hipMalloc(&ctx->d_ties, N * 4));
+    if (!ctx->ts.exact && ctx->ts.d_codes && ctx->ts.N == N && ctx->ts.D == D && ctx->ts.cs == cs) return QVQ_OK;
+    drop_training(ctx);   // before the new set's allocations: peak memory is one set
+    qvq_ctx::Training ts;   // moved into the context when it is complete
+    if (!make_terms(cs, ts.terms)) return fail(ctx, QVQ_EUNSUPPORTED, "colour space has no exact byte sums");
+    ts.N = N;
+    ts.D = D;
+    ts.Dp = Dp;
+    ts.cs = cs;
+    mfma_setup(ts);
+    HIPCHK(ts.d_codes.alloc(N * Dp));
+    qvq_status st = ensure_apool(ctx, ts, 1);
+    if (st != QVQ_OK) return st;
+    HIPCHK(ts.d_flags.alloc(N));
+    HIPCHK(ts.d_ties.alloc(N));
     uint64_t plut[256];
-    for (int b = 0; b < 256; b++) plut[b] = ((uint64_t)ctx->terms.hi[b] << 32) | ctx->terms.lo[b];
-    HIPCHK(hipMemcpy(ctx->d_lut32, ctx->terms.v32, sizeof(ctx->terms.v32), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(ctx->d_w, ctx->terms.w, sizeof(ctx->terms.w), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(ctx->d_lut64, ctx->terms.v64, sizeof(ctx->terms.v64), hipMemcpyHostToDevice));
+    for (int b = 0; b < 256; b++) plut[b] = ((uint64_t)ts.terms.hi[b] << 32) | ts.terms.lo[b];
+    HIPCHK(hipMemcpy(ctx->d_lut32, ts.terms.v32, sizeof(ts.terms.v32), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(ctx->d_w, ts.terms.w, sizeof(ts.terms.w), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(ctx->d_lut64, ts.terms.v64, sizeof(ts.terms.v64), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(ctx->d_plut, plut, sizeof(plut), hipMemcpyHostToDevice));
     // the band of rows whose answer can depend on the centroids' last bits:
     // |c_kahan - c_exact| <= delta per component, so a distance moves by at most
     // 2 delta sqrt(D) sqrt(d) + D delta^2
     const double delta = cs == QVQ_CS_SCALED ? std::ldexp(1.0, -49) : 0.0;
-    ctx->tie_abs = 2 * delta * std::sqrt((double)D);
+    ts.tie_abs = 2 * delta * std::sqrt((double)D);
+    ctx->ts = std::move(ts);
     return QVQ_OK;
 }
 
 qvq_status ensure_levels(qvq_ctx *ctx, uint32_t Kmax) {
-    if (ctx->Kcap >= Kmax) return QVQ_OK;
-    free_levels(ctx);
-    const uint64_t KD = (uint64_t)Kmax * ctx->D;
+    if (ctx->lv.Kcap >= Kmax) return QVQ_OK;
+    ctx->lv = {};   // before the new buffers' allocations; a failure below leaves Kcap == 0
+    qvq_ctx::Levels lv;
+    const uint32_t D = ctx->ts.D, Dp = ctx->ts.Dp;
+    const uint64_t KD = (uint64_t)Kmax * D;
     const uint64_t Kp = pad32(Kmax);
-    HIPCHK(hipMalloc(&ctx->d_C64_cent, KD * 8));
-    HIPCHK(hipMalloc(&ctx->d_C64_split, KD * 8));
-    HIPCHK(hipMalloc(&ctx->d_C64_split_alt, KD * 8));
-    HIPCHK(hipMalloc(&ctx->d_C32, Kp * ctx->Dp * 4));
-    if (ctx->D == MF_D) HIPCHK(hipMalloc(&ctx->d_E32, Kp * 16 * 4));
-    HIPCHK(hipMalloc(&ctx->d_rows, Kp * 2 * cb_row_f16(ctx->D, ctx->Dp)));
-    HIPCHK(hipMalloc(&ctx->d_perm, Kp * 4));
-    HIPCHK(hipMalloc(&ctx->d_tint, tint_bytes((uint32_t)Kp)));
+    HIPCHK(lv.d_C64_cent.alloc(KD));
+    HIPCHK(lv.d_C64_split.alloc(KD));
+    HIPCHK(lv.d_C64_split_alt.alloc(KD));
+    HIPCHK(lv.d_C32.alloc(Kp * Dp));
+    if (D == MF_D) HIPCHK(lv.d_E32.alloc(Kp * 16));
+    HIPCHK(lv.d_rows.alloc(Kp * cb_row_f16(D, Dp)));
+    HIPCHK(lv.d_perm.alloc(Kp));
+    HIPCHK(lv.d_tint.alloc(tint_bytes((uint32_t)Kp) / 4));
     // G per-CU slabs + two correction slabs (fused path: rows the recheck / kd-tree move, at
     // the new index (+) and at the search's provisional one (-))
-    HIPCHK(hipMalloc(&ctx->d_part, (uint64_t)(ctx->G + 2) * KD * 8));
-    HIPCHK(hipMalloc(&ctx->d_part_cnt, (uint64_t)(ctx->G + 2) * Kmax * 4));
+    HIPCHK(lv.d_part.alloc((uint64_t)(ctx->G + 2) * KD));
+    HIPCHK(lv.d_part_cnt.alloc((uint64_t)(ctx->G + 2) * Kmax));
     // two copies of the final sums: copy 1 takes the kd-tree ties' moves (kd_reduce_kernel) and
     // is cleared, over the level's region, by each fused search before the level's kd_reduce
-    HIPCHK(hipMalloc(&ctx->d_sums, 2 * (2 * KD + Kmax) * 8));
-    HIPCHK(hipMemset(ctx->d_sums, 0, 2 * (2 * KD + Kmax) * 8));
-    ctx->sums_bytes = 2 * (2 * KD + Kmax) * 8;
-    const unsigned mflags = hipHostMallocMapped | hipHostMallocCoherent;
+    HIPCHK(lv.d_sums.alloc(2 * (2 * KD + Kmax)));
+    HIPCHK(hipMemset(lv.d_sums, 0, lv.d_sums.bytes()));
     // two halves, each split rows | parent counts (host_cb_of)
-    ctx->cb_half = (KD + (uint64_t)Kmax / 2 + 1 + 7) / 8 * 8;
-    HIPCHK(hipHostMalloc(&ctx->h_cb, 2 * ctx->cb_half * 8, mflags));
-    HIPCHK(hipHostGetDevicePointer((void **)&ctx->dh_cb, ctx->h_cb, 0));
-    ctx->tree_cap = tree_bytes(Kmax, ctx->D);
-    for (int b = 0; b < 2; b++) {
-        HIPCHK(hipHostMalloc(&ctx->h_tree[b], ctx->tree_cap, mflags));
-        HIPCHK(hipHostGetDevicePointer((void **)&ctx->dh_tree[b], ctx->h_tree[b], 0));
-    }
-    HIPCHK(hipMalloc(&ctx->d_tree, ctx->tree_cap));
+    lv.cb_half = (KD + (uint64_t)Kmax / 2 + 1 + 7) / 8 * 8;
+    HIPCHK(lv.h_cb.alloc(2 * lv.cb_half));
+    lv.tree_cap = tree_bytes(Kmax, D);
+    for (auto &h : lv.h_tree) HIPCHK(h.alloc(lv.tree_cap));
+    HIPCHK(lv.d_tree.alloc(lv.tree_cap));
     {   // the device tree build's scratch (levels of up to KDB_MAXK code vectors)
         const uint32_t Kb = std::min<uint32_t>(Kmax, KDB_MAXK);
-        if (plan_level(ctx, Kb).kd_device && kd_build_fits(Kb, ctx->D) && (uint64_t)Kmax * ctx->D >= KDB_MIN_KD) {
-            HIPCHK(hipMalloc(&ctx->d_kdb_vind, (uint64_t)Kb * 4));
-            HIPCHK(hipMalloc(&ctx->d_kdb_nodes, 2ull * Kb * sizeof(KdbNode)));
-            HIPCHK(hipMalloc(&ctx->d_kdb_nbox, 2ull * Kb * 2 * ctx->D * 8));
-            HIPCHK(hipMalloc(&ctx->d_kdb_cbox, 2ull * Kb * 2 * ctx->D * 8));
-            HIPCHK(hipHostMalloc(&ctx->h_kdb, kdb_host_layout(Kb, ctx->D).total, mflags));
-            HIPCHK(hipHostGetDevicePointer((void **)&ctx->dh_kdb, ctx->h_kdb, 0));
-            std::memset(ctx->h_kdb, 0, sizeof(KdbHeader));
-            ctx->kdb_cap = Kb;
-            if (!ctx->kstream) HIPCHK(hipStreamCreateWithFlags(&ctx->kstream, hipStreamNonBlocking));
-            if (!ctx->ev_kcb) HIPCHK(hipEventCreateWithFlags(&ctx->ev_kcb, hipEventDisableTiming));
-            if (!ctx->ev_kdb) HIPCHK(hipEventCreateWithFlags(&ctx->ev_kdb, hipEventDisableTiming));
+        if (plan_level(ctx, Kb).kd_device && kd_build_fits(Kb, D) && (uint64_t)Kmax * D >= KDB_MIN_KD) {
+            HIPCHK(lv.d_kdb_vind.alloc(Kb));
+            HIPCHK(lv.d_kdb_nodes.alloc(2ull * Kb));
+            HIPCHK(lv.d_kdb_nbox.alloc(2ull * Kb * 2 * D));
+            HIPCHK(lv.d_kdb_cbox.alloc(2ull * Kb * 2 * D));
+            HIPCHK(lv.h_kdb.alloc(kdb_host_layout(Kb, D).total));
+            std::memset(lv.h_kdb, 0, sizeof(KdbHeader));
+            lv.kdb_cap = Kb;
+            if (!ctx->kstream) HIPCHK(hipStreamCreateWithFlags(ctx->kstream.put(), hipStreamNonBlocking));
+            if (!ctx->ev_kcb) HIPCHK(hipEventCreateWithFlags(ctx->ev_kcb.put(), hipEventDisableTiming));
+            if (!ctx->ev_kdb) HIPCHK(hipEventCreateWithFlags(ctx->ev_kdb.put(), hipEventDisableTiming));
         }
     }
-    ctx->Kcap = Kmax;
+    lv.Kcap = Kmax;
+    ctx->lv = std::move(lv);
     return QVQ_OK;
 }
 
 // What every finalize launch takes from the context: the terms, the centroids' and the tables'
 // buffers and, with last_block, the end-of-kernel scratch, block counter and ready number.
 FinArgs finalize_args(const qvq_ctx *ctx, uint32_t K, bool last_block) {
-    const Terms &T = ctx->terms;
+    const Terms &T = ctx->ts.terms;
     FinArgs f;
     f.K = K;
-    f.D = ctx->D;
-    f.Dp = ctx->Dp;
+    f.D = ctx->ts.D;
+    f.Dp = ctx->ts.Dp;
     f.R = T.R;
     f.bias = T.bias;
     f.scale = T.scale;
     f.mu = T.mu;
     f.sx = T.sx;
-    f.t = ctx->mf_t;
-    f.C_cent = ctx->d_C64_cent;
-    f.C32 = ctx->d_C32;
-    f.rows = ctx->d_rows;
-    f.E32 = ctx->d_E32;
+    f.t = ctx->ts.mf_t;
+    f.C_cent = ctx->lv.d_C64_cent;
+    f.C32 = ctx->lv.d_C32;
+    f.rows = ctx->lv.d_rows;
+    f.E32 = ctx->lv.d_E32;
     if (last_block) {
         f.dist_part = ctx->d_dist_part + 8;
         f.done = ctx->d_counters + FIN_DONE_COUNTER;
-        f.ready = ctx->dh_ready;
+        f.ready = ctx->h_ready.dev();
     }
     return f;
 }
 
 // Copy 1 of d_sums sits one capacity-sized copy in, where no level's copy 0 reaches.
-uint64_t sums_cap_stride(const qvq_ctx *ctx) { return 2 * (uint64_t)ctx->Kcap * ctx->D + ctx->Kcap; }
+uint64_t sums_cap_stride(const qvq_ctx *ctx) { return 2 * (uint64_t)ctx->lv.Kcap * ctx->ts.D + ctx->lv.Kcap; }
 
 // What run_level left of the level's sums, for reduce_level: a value that ends with the level
 // (a level that is abandoned leaves nothing behind but, possibly, sums1_dirty).
@@ -777,7 +726,7 @@ void mark_sums1(qvq_ctx *ctx) { ctx->sums1_dirty = true; }
 // the sums cleared before they are used again.
 qvq_status clear_dirty_sums(qvq_ctx *ctx) {
     if (ctx->sums1_dirty) {
-        HIPCHK(hipMemsetAsync(ctx->d_sums, 0, ctx->sums_bytes, ctx->stream));
+        HIPCHK(hipMemsetAsync(ctx->lv.d_sums, 0, ctx->lv.d_sums.bytes(), ctx->stream));
         ctx->sums1_dirty = false;
     }
     return QVQ_OK;
@@ -787,7 +736,7 @@ qvq_status clear_dirty_sums(qvq_ctx *ctx) {
 // after adding it, where no fused search of a later level does), or, r null, the mean sums at
 // K = 1, which it leaves cleared for the next quantize.
 void sums_args(const qvq_ctx *ctx, FinArgs &f, const ReducedSums *r, bool clear1) {
-    f.sums = r ? ctx->d_sums : ctx->d_mean;
+    f.sums = r ? ctx->lv.d_sums : ctx->d_mean;
     f.ncopy = r ? r->copies : MEAN_COPIES;
     f.cstride = r && r->copies > 1 ? sums_cap_stride(ctx) : 0;
     f.gate = r ? r->gate : nullptr;
@@ -803,23 +752,23 @@ void tables_args(qvq_ctx *ctx, FinArgs &f, uint32_t children, double *C_next, do
     f.C_next = C_next;
     f.host_cb = host_cb;
     if (prune) {
-        f.perm = ctx->d_perm;
-        f.tint = ctx->d_tint;
+        f.perm = ctx->lv.d_perm;
+        f.tint = ctx->lv.d_tint;
     }
-    ctx->perm_k = prune ? children * f.K : 0;
+    ctx->lv.perm_k = prune ? children * f.K : 0;
 }
 // Every finalize is launched here: one that adds copy 1 of the level's sums, or takes
 // qvq_refine's changed total, has consumed what mark_sums1 announced.
 qvq_status run_finalize(qvq_ctx *ctx, const FinArgs &f) {
     HIPCHK(launch_finalize(ctx->stream, f));
-    if ((f.sums == ctx->d_sums && f.ncopy > 1) || f.changed64) ctx->sums1_dirty = false;
+    if ((f.sums == ctx->lv.d_sums && f.ncopy > 1) || f.changed64) ctx->sums1_dirty = false;
     return QVQ_OK;
 }
 
 // Search tables for the K code vectors in d_C64_split (no tile order).
 qvq_status run_prep(qvq_ctx *ctx, uint32_t K) {
     FinArgs f = finalize_args(ctx, K, false);
-    f.C_src = ctx->d_C64_split;
+    f.C_src = ctx->lv.d_C64_split;
     tables_args(ctx, f, 1, nullptr, nullptr, false);
     return run_finalize(ctx, f);
 }
@@ -827,22 +776,11 @@ qvq_status run_prep(qvq_ctx *ctx, uint32_t K) {
 // fp32 error-bound coefficients for the VALU search flag ("near-tie flags").
 void valu_coeffs(const qvq_ctx *ctx, float &alpha, float &beta, float &gamma) {
     const double u = std::ldexp(1.0, -24);
-    const double vmax = ctx->terms.vmax;
-    const double L = std::sqrt((double)ctx->D) * (vmax + 1.2 * vmax) * 1.001;   // >= || |x| + |c| ||
+    const double vmax = ctx->ts.terms.vmax;
+    const double L = std::sqrt((double)ctx->ts.D) * (vmax + 1.2 * vmax) * 1.001;   // >= || |x| + |c| ||
     alpha = (float)(2.0 * 4.01 * u * L);
-    beta = (float)(2.0 * ((ctx->Dp + 4) * u * 1.01 + 4e-15));
+    beta = (float)(2.0 * ((ctx->ts.Dp + 4) * u * 1.01 + 4e-15));
     gamma = (float)(2.0 * 4.01 * u * u * L * L + 1e-30);
-}
-
-// Grow a pinned host buffer (h, bytes) to at least need bytes.
-qvq_status ensure_pinned(qvq_ctx *ctx, void *&h, uint64_t &bytes, uint64_t need) {
-    if (bytes >= need) return QVQ_OK;
-    if (h) (void)hipHostFree(h);
-    h = nullptr;
-    bytes = 0;
-    HIPCHK(hipHostMalloc(&h, need, hipHostMallocDefault));
-    bytes = need;
-    return QVQ_OK;
 }
 
 qvq_status wait_stream(qvq_ctx *ctx);
@@ -857,8 +795,8 @@ qvq_status all_reduce(qvq_ctx *ctx, void *buf, uint64_t count, bool f64) {
         return QVQ_OK;
     }
     if (!ctx->host_ar) return QVQ_OK;
-    qvq_status st = ensure_pinned(ctx, ctx->h_ar_stage, ctx->ar_stage_bytes, count * 8);
-    if (st != QVQ_OK) return st;
+    HIPCHK(ctx->h_ar_stage.ensure(count * 8));
+    qvq_status st;
     HIPCHK(hipMemcpyAsync(ctx->h_ar_stage, buf, count * 8, hipMemcpyDeviceToHost, ctx->stream));
     if ((st = wait_stream(ctx)) != QVQ_OK) return st;
     const int rc = ctx->host_ar(ctx->h_ar_stage, count, f64 ? 1 : 0, ctx->host_ar_user);
@@ -869,23 +807,23 @@ qvq_status all_reduce(qvq_ctx *ctx, void *buf, uint64_t count, bool f64) {
 }
 
 qvq_status all_reduce_sums(qvq_ctx *ctx, uint32_t K, uint64_t *sums = nullptr, uint32_t copies = 1) {
-    if (!sums) sums = ctx->d_sums;
-    return all_reduce(ctx, sums, copies * (2 * (uint64_t)K * ctx->D + K), false);
+    if (!sums) sums = ctx->lv.d_sums;
+    return all_reduce(ctx, sums, copies * (2 * (uint64_t)K * ctx->ts.D + K), false);
 }
 
 // Centroid sums under assignment d_A: nslabs slabs in d_part (for the reduce), or with the sort
 // straight into d_sums (nslabs = 0).
 qvq_status run_update_slabs(qvq_ctx *ctx, const LevelPlan &p, const uint32_t *d_A, uint32_t K, uint32_t &nslabs) {
     if (p.sorted_sums) {
-        if (!ctx->d_sortbuf) HIPCHK(hipMalloc(&ctx->d_sortbuf, ctx->N * 2 * sizeof(uint32_t)));
-        HIPCHK(launch_sorted_sums(ctx->stream, ctx->Dp, ctx->G, ctx->d_codes, ctx->N, d_A, K, ctx->D, ctx->d_plut,
-                                  ctx->d_part_cnt, reinterpret_cast<uint32_t *>(ctx->d_part), ctx->d_sortbuf,
-                                  ctx->d_sortbuf + ctx->N, ctx->d_sums));
+        HIPCHK(ctx->ts.d_sortbuf.ensure(ctx->ts.N * 2));
+        HIPCHK(launch_sorted_sums(ctx->stream, ctx->ts.Dp, ctx->G, ctx->ts.d_codes, ctx->ts.N, d_A, K, ctx->ts.D, ctx->d_plut,
+                                  ctx->lv.d_part_cnt, reinterpret_cast<uint32_t *>(ctx->lv.d_part.get()), ctx->ts.d_sortbuf,
+                                  ctx->ts.d_sortbuf + ctx->ts.N, ctx->lv.d_sums));
         nslabs = 0;
         return QVQ_OK;
     }
-    HIPCHK(launch_update(ctx->stream, ctx->Dp, ctx->G, ctx->d_codes, ctx->N, d_A, K, ctx->D, ctx->d_plut, ctx->d_part,
-                         ctx->d_part_cnt));
+    HIPCHK(launch_update(ctx->stream, ctx->ts.Dp, ctx->G, ctx->ts.d_codes, ctx->ts.N, d_A, K, ctx->ts.D, ctx->d_plut, ctx->lv.d_part,
+                         ctx->lv.d_part_cnt));
     nslabs = ctx->G;
     return QVQ_OK;
 }
@@ -895,7 +833,7 @@ qvq_status run_update(qvq_ctx *ctx, const LevelPlan &p, const uint32_t *d_A, uin
     uint32_t nslabs = 0;
     qvq_status st = run_update_slabs(ctx, p, d_A, K, nslabs);
     if (st != QVQ_OK) return st;
-    if (nslabs) HIPCHK(launch_reduce(ctx->stream, ctx->d_part, ctx->d_part_cnt, nslabs, 0, K, ctx->D, ctx->d_sums));
+    if (nslabs) HIPCHK(launch_reduce(ctx->stream, ctx->lv.d_part, ctx->lv.d_part_cnt, nslabs, 0, K, ctx->ts.D, ctx->lv.d_sums));
     return QVQ_OK;
 }
 
@@ -905,68 +843,67 @@ qvq_status run_update(qvq_ctx *ctx, const LevelPlan &p, const uint32_t *d_A, uin
 // them (A/B).
 bool kahan_mode(const qvq_ctx *ctx) {
     static const bool off = env_is("QVQ_KAHAN", "0");
-    return !off && !ctx->exact;
+    return !off && !ctx->ts.exact;
 }
 // The recheck's absolute tie band: only where a reference-bit step follows (kahan_mode)
-double tie_band(const qvq_ctx *ctx) { return kahan_mode(ctx) ? ctx->tie_abs : 0.0; }
+double tie_band(const qvq_ctx *ctx) { return kahan_mode(ctx) ? ctx->ts.tie_abs : 0.0; }
 
-qvq_status alloc_kahan_work(qvq_ctx *ctx, KahanWork &w, uint32_t Kc);
-
+// The Kahan outputs for Kc cells and a workspace for N rows, Kc cells and D components, each kept
+// while it fits and otherwise rebuilt whole: released first, built in a local, moved in complete.
 qvq_status ensure_kahan(qvq_ctx *ctx, uint32_t Kc) {
-    KahanWork &w = ctx->kw;
-    const uint32_t D = ctx->D;
-    if (ctx->kc_kcap < Kc) {
-        dfree(ctx->d_kc_cent);
-        dfree(ctx->d_kc_split);
-        dfree(ctx->d_kc_sel);
-        if (ctx->h_kc_sel) (void)hipHostFree(ctx->h_kc_sel);
-        if (ctx->h_kc_out) (void)hipHostFree(ctx->h_kc_out);
-        HIPCHK(hipMalloc(&ctx->d_kc_cent, (uint64_t)Kc * D * 8));
-        HIPCHK(hipMalloc(&ctx->d_kc_split, 2ull * Kc * D * 8));
-        HIPCHK(hipMalloc(&ctx->d_kc_sel, (uint64_t)Kc * 4));
-        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&ctx->h_kc_sel), (uint64_t)Kc * 4, hipHostMallocDefault));
-        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&ctx->h_kc_out), 2ull * Kc * D * 8, hipHostMallocMapped));
-        HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void **>(&ctx->dh_kc_out), ctx->h_kc_out, 0));
-        ctx->kc_kcap = Kc;
+    qvq_ctx::Kahan &kh = ctx->kh;
+    const uint64_t N = ctx->ts.N;
+    const uint32_t D = ctx->ts.D;
+    if (kh.cells.kcap < Kc) {
+        kh.cells = {};
+        qvq_ctx::Kahan::Cells c;
+        HIPCHK(c.d_kc_cent.alloc((uint64_t)Kc * D));
+        HIPCHK(c.d_kc_split.alloc(2ull * Kc * D));
+        HIPCHK(c.d_kc_sel.alloc(Kc));
+        HIPCHK(c.h_kc_sel.alloc(Kc));
+        HIPCHK(c.h_kc_out.alloc(2ull * Kc * D));
+        c.kcap = Kc;
+        kh.cells = std::move(c);
     }
-    return alloc_kahan_work(ctx, w, Kc);
-}
-
-// A Kahan workspace for N rows, Kc cells and D components (kept while it fits).
-qvq_status alloc_kahan_work(qvq_ctx *ctx, KahanWork &w, uint32_t Kc) {
-    const uint64_t N = ctx->N;
-    const uint32_t D = ctx->D;
-    if (w.n_cap == N && w.k_cap >= Kc && w.d_cap == D) return QVQ_OK;
-    const uint32_t kcap = std::max(Kc, w.k_cap);
-    free_kahan_work(w);
+    if (kh.kw.n_cap == N && kh.kw.k_cap >= Kc && kh.kw.d_cap == D) return QVQ_OK;
+    const uint32_t kcap = std::max(Kc, kh.kw.k_cap);
+    kh.work = {};
+    kh.kw = KahanWork();
+    qvq_ctx::Kahan::Work b;
     uint64_t segs, blks;
     KahanWork::caps(N, kcap, segs, blks);
-    HIPCHK(hipMalloc(&w.hist, (uint64_t)KahanWork::sort_blocks(N) * kcap * 4));
-    HIPCHK(hipMalloc(&w.tot, (uint64_t)kcap * 4));
-    for (uint32_t **p : {&w.koff, &w.segoff, &w.blkoff}) HIPCHK(hipMalloc(p, ((uint64_t)kcap + 1) * 4));
-    HIPCHK(hipMalloc(&w.planes, (uint64_t)D * KahanWork::plane_len(N)));
-    HIPCHK(hipMemset(w.planes, 0, (uint64_t)D * KahanWork::plane_len(N)));
-    HIPCHK(hipMalloc(&w.meta, (uint64_t)D * segs * KahanWork::meta_bytes()));
-    HIPCHK(hipMalloc(&w.bsum, (uint64_t)D * blks * 16));
-    HIPCHK(hipMalloc(&w.bfn, (uint64_t)D * blks * KahanWork::fn_bytes()));
-    HIPCHK(hipMalloc(&w.sfn, (uint64_t)D * segs * KahanWork::segfn_bytes()));
-    HIPCHK(hipMalloc(&w.bfn8, (uint64_t)D * blks * 8 * KahanWork::fn_bytes()));
-    HIPCHK(hipMalloc(&w.stats, 4 * sizeof(unsigned)));
-    HIPCHK(hipMemset(w.stats, 0, 4 * sizeof(unsigned)));
+    HIPCHK(b.hist.alloc((uint64_t)KahanWork::sort_blocks(N) * kcap));
+    HIPCHK(b.tot.alloc(kcap));
+    for (auto *p : {&b.koff, &b.segoff, &b.blkoff}) HIPCHK(p->alloc((uint64_t)kcap + 1));
+    HIPCHK(b.planes.alloc((uint64_t)D * KahanWork::plane_len(N)));
+    HIPCHK(hipMemset(b.planes, 0, b.planes.bytes()));
+    HIPCHK(b.meta.alloc((uint64_t)D * segs * KahanWork::meta_bytes()));
+    HIPCHK(b.bsum.alloc((uint64_t)D * blks * 16));
+    HIPCHK(b.bfn.alloc((uint64_t)D * blks * KahanWork::fn_bytes()));
+    HIPCHK(b.sfn.alloc((uint64_t)D * segs * KahanWork::segfn_bytes()));
+    HIPCHK(b.bfn8.alloc((uint64_t)D * blks * 8 * KahanWork::fn_bytes()));
+    HIPCHK(b.stats.alloc(4));
+    HIPCHK(hipMemset(b.stats, 0, b.stats.bytes()));
     {   // the byte table: SCALED values in units of 2^-60
         uint64_t kx[256];
-        for (int b = 0; b < 256; b++) kx[b] = (uint64_t)std::ldexp(ctx->terms.v64[b], 60);
+        for (int i = 0; i < 256; i++) kx[i] = (uint64_t)std::ldexp(ctx->ts.terms.v64[i], 60);
         std::vector<uint8_t> tab(KahanWork::tab_bytes());
         KahanWork::make_tab(kx, tab.data());
-        HIPCHK(hipMalloc(&w.tab, tab.size()));
-        HIPCHK(hipMemcpy(w.tab, tab.data(), tab.size(), hipMemcpyHostToDevice));
+        HIPCHK(b.tab.alloc(tab.size()));
+        HIPCHK(hipMemcpy(b.tab, tab.data(), tab.size(), hipMemcpyHostToDevice));
     }
+    KahanWork w;
+    w.hist = b.hist, w.tot = b.tot, w.koff = b.koff, w.segoff = b.segoff, w.blkoff = b.blkoff;
+    w.planes = b.planes, w.meta = b.meta, w.bsum = b.bsum, w.bfn = b.bfn, w.sfn = b.sfn, w.bfn8 = b.bfn8;
+    w.tab = b.tab, w.stats = b.stats;
     w.n_one = (uint32_t)N;
     w.seg_cap = segs;
     w.blk_cap = blks;
     w.n_cap = N;
     w.k_cap = kcap;
     w.d_cap = D;
+    kh.work = std::move(b);
+    kh.kw = w;
     return QVQ_OK;
 }
 
@@ -976,15 +913,8 @@ qvq_status alloc_kahan_work(qvq_ctx *ctx, KahanWork &w, uint32_t Kc) {
 // branch.  One rank: nothing to do.
 qvq_status vote(qvq_ctx *ctx, uint64_t *vals, uint64_t n) {
     if (ctx->nranks <= 1 || (!ctx->comm && !ctx->host_ar) || n == 0) return QVQ_OK;
-    if (ctx->vote_cap < n) {
-        dfree(ctx->d_vote);
-        if (ctx->h_vote) (void)hipHostFree(ctx->h_vote);
-        ctx->h_vote = nullptr;
-        ctx->vote_cap = 0;
-        HIPCHK(hipMalloc(&ctx->d_vote, n * 8));
-        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&ctx->h_vote), n * 8, hipHostMallocDefault));
-        ctx->vote_cap = n;
-    }
+    HIPCHK(ctx->d_vote.ensure(n));
+    HIPCHK(ctx->h_vote.ensure(n));
     std::memcpy(ctx->h_vote, vals, n * 8);
     HIPCHK(hipMemcpyAsync(ctx->d_vote, ctx->h_vote, n * 8, hipMemcpyHostToDevice, ctx->stream));
     qvq_status st = all_reduce(ctx, ctx->d_vote, n, false);
@@ -1014,7 +944,7 @@ qvq_status vote(qvq_ctx *ctx, uint64_t *vals, uint64_t n) {
 // offsets, run one after another on the device (no collective).
 qvq_status kahan_chained(qvq_ctx *ctx, const uint32_t *A, uint32_t K_in, const uint32_t *sel, uint32_t S,
                          bool want_split, const std::vector<uint64_t> *splits = nullptr) {
-    const uint32_t D = ctx->D, Dp = ctx->Dp;
+    const uint32_t D = ctx->ts.D, Dp = ctx->ts.Dp;
     const bool virt = splits != nullptr;
     const uint32_t R = virt ? (uint32_t)splits->size() - 1 : (uint32_t)ctx->nranks;
     const uint32_t rank = virt ? 0u : (uint32_t)ctx->rank;
@@ -1022,34 +952,29 @@ qvq_status kahan_chained(qvq_ctx *ctx, const uint32_t *A, uint32_t K_in, const u
     if (!A && (K_in != 1 || S != 1 || sel)) return fail(ctx, QVQ_EINVAL, "kahan_chained: the mean is one cell");
     qvq_status st = ensure_kahan(ctx, std::max(K_in, S));   // (may reallocate the outputs below)
     if (st != QVQ_OK) return st;
-    double *C_out = ctx->d_kc_cent, *split_out = want_split ? ctx->d_kc_split : nullptr;
+    double *C_out = ctx->kh.cells.d_kc_cent, *split_out = want_split ? ctx->kh.cells.d_kc_split : nullptr;
     const uint64_t gcount = 2ull * R * S * D + (uint64_t)R * S, scount = 2ull * S * D;
-    if (ctx->kc_chain_cap < gcount + scount) {
-        dfree(ctx->d_kc_chain);
-        ctx->kc_chain_cap = 0;
-        HIPCHK(hipMalloc(&ctx->d_kc_chain, (gcount + scount) * 8));
-        ctx->kc_chain_cap = gcount + scount;
-    }
-    uint64_t *gather = ctx->d_kc_chain, *state = gather + gcount;
+    HIPCHK(ctx->kh.d_kc_chain.ensure(gcount + scount));
+    uint64_t *gather = ctx->kh.d_kc_chain, *state = gather + gcount;
     hipStream_t s = ctx->stream;
     HIPCHK(hipMemsetAsync(gather, 0, (gcount + scount) * 8, s));
-    const KahanWork &w = ctx->kw;
+    const KahanWork &w = ctx->kh.kw;
     if (virt) {
         for (uint32_t v = 0; v < R; v++) {
             const uint64_t off = (*splits)[v], n = (*splits)[v + 1] - off;
             if (!n) continue;
-            const uint8_t *codes = ctx->d_codes + off * Dp;
+            const uint8_t *codes = ctx->ts.d_codes + off * Dp;
             const uint32_t *Av = A ? A + off : nullptr;
             HIPCHK(launch_kahan_chain_local(s, w, codes, Dp, D, n, Av, Ks, sel, K_in, gather, v, R));
             HIPCHK(launch_kahan_chain_build(s, w, D, n, Ks, gather, v));
             HIPCHK(launch_kahan_chain_eval(s, w, D, n, Ks, state, gather, v));
         }
     } else {
-        HIPCHK(launch_kahan_chain_local(s, w, ctx->d_codes, Dp, D, ctx->N, A, Ks, sel, K_in, gather, rank, R));
+        HIPCHK(launch_kahan_chain_local(s, w, ctx->ts.d_codes, Dp, D, ctx->ts.N, A, Ks, sel, K_in, gather, rank, R));
         if (R > 1 && (st = all_reduce(ctx, gather, gcount, false)) != QVQ_OK) return st;
-        HIPCHK(launch_kahan_chain_build(s, w, D, ctx->N, Ks, gather, rank));
+        HIPCHK(launch_kahan_chain_build(s, w, D, ctx->ts.N, Ks, gather, rank));
         for (uint32_t q = 0; q < R; q++) {
-            if (q == rank) HIPCHK(launch_kahan_chain_eval(s, w, D, ctx->N, Ks, state, gather, rank));
+            if (q == rank) HIPCHK(launch_kahan_chain_eval(s, w, D, ctx->ts.N, Ks, state, gather, rank));
             else HIPCHK(hipMemsetAsync(state, 0, scount * 8, s));
             if (R > 1 && (st = all_reduce(ctx, state, scount, false)) != QVQ_OK) return st;
         }
@@ -1073,8 +998,8 @@ uint32_t cb_half_of(uint32_t level) {
     static const bool single = env_is("QVQ_CB_SINGLE", "1");
     return single ? 0u : (level & 1);
 }
-double *host_cb_of(const qvq_ctx *ctx, uint32_t level) { return ctx->h_cb + (uint64_t)cb_half_of(level) * ctx->cb_half; }
-double *dev_cb_of(const qvq_ctx *ctx, uint32_t level) { return ctx->dh_cb + (uint64_t)cb_half_of(level) * ctx->cb_half; }
+double *host_cb_of(const qvq_ctx *ctx, uint32_t level) { return ctx->lv.h_cb + (uint64_t)cb_half_of(level) * ctx->lv.cb_half; }
+double *dev_cb_of(const qvq_ctx *ctx, uint32_t level) { return ctx->lv.h_cb.dev() + (uint64_t)cb_half_of(level) * ctx->lv.cb_half; }
 
 // The host part: the tree (ctx->tree over ctx->cb_local) and its flattened image in h_tree[buf];
 // v.bytes = 0 when there is no device image (too large, or too deep for the kernel's LDS).
@@ -1084,28 +1009,28 @@ void build_tree_host(qvq_ctx *ctx, const double *hC, uint32_t K, int buf, KdView
     v = KdView{};
     // the build reads the codebook many times; mapped memory the GPU just wrote is read
     // once, sequentially, into ordinary memory first
-    ctx->cb_local.assign(hC, hC + (size_t)K * ctx->D);
+    ctx->cb_local.assign(hC, hC + (size_t)K * ctx->ts.D);
     if ((hC == host_cb_of(ctx, 0) || hC == host_cb_of(ctx, 1)) && K >= 2) {   // a finalize's split: the parent counts follow it
-        const uint32_t *cnt = reinterpret_cast<const uint32_t *>(hC + (size_t)K * ctx->D);
+        const uint32_t *cnt = reinterpret_cast<const uint32_t *>(hC + (size_t)K * ctx->ts.D);
         ctx->cnt_local.assign(cnt, cnt + K / 2);
     } else {
         ctx->cnt_local.clear();
     }
     ctx->htrace.mark("K" + std::to_string(K) + " codebook copied");
-    ctx->tree.reset(new RefKDTree(ctx->cb_local.data(), K, (int)ctx->D, cancel));
+    ctx->tree.reset(new RefKDTree(ctx->cb_local.data(), K, (int)ctx->ts.D, cancel));
     ctx->htrace.mark("K" + std::to_string(K) + " tree structure");
     const RefKDTree &tree = *ctx->tree;
     if (tree.cancelled()) return;
-    const uint32_t D = ctx->D;
+    const uint32_t D = ctx->ts.D;
     const size_t nn = tree.num_nodes();
     KdView t;
     t.depth = tree.depth();
     t.n_nodes = (uint32_t)nn;
     const uint64_t bytes = 16ull * D + nn * sizeof(KdNodeDev) + 4ull * K;
-    if (bytes > ctx->tree_cap) return;
+    if (bytes > ctx->lv.tree_cap) return;
     t.bytes = (uint32_t)bytes;
     if (!kd_resolve_fits(t, K)) return;
-    double *lo = reinterpret_cast<double *>(ctx->h_tree[buf]), *hi = lo + D;
+    double *lo = reinterpret_cast<double *>(ctx->lv.h_tree[buf].get()), *hi = lo + D;
     KdNodeDev *nodes = reinterpret_cast<KdNodeDev *>(hi + D);
     uint32_t *vind = reinterpret_cast<uint32_t *>(nodes + nn);
     tree.flatten(nodes, vind, lo, hi);
@@ -1121,15 +1046,15 @@ void tree_view(qvq_ctx *ctx, int buf, KdView &v) {
         v = KdView{};
         return;
     }
-    const uint32_t D = ctx->D;
-    const double *dlo = reinterpret_cast<const double *>(ctx->dh_tree[buf]);
+    const uint32_t D = ctx->ts.D;
+    const double *dlo = reinterpret_cast<const double *>(ctx->lv.h_tree[buf].dev());
     constexpr uint64_t dma_min = 32768;
     if (v.bytes > dma_min) {
-        if (hipMemcpyAsync(ctx->d_tree, ctx->h_tree[buf], v.bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
+        if (hipMemcpyAsync(ctx->lv.d_tree, ctx->lv.h_tree[buf], v.bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
             v = KdView{};
             return;
         }
-        dlo = reinterpret_cast<const double *>(ctx->d_tree);
+        dlo = reinterpret_cast<const double *>(ctx->lv.d_tree.get());
     }
     v.lo = dlo;
     v.hi = dlo + D;
@@ -1156,8 +1081,8 @@ qvq_status wait_failed(qvq_ctx *ctx, qvq_status st);
 qvq_status start_device_tree(qvq_ctx *ctx, uint32_t K) {
     HIPCHK(hipEventRecord(ctx->ev_kcb, ctx->stream));
     HIPCHK(hipStreamWaitEvent(ctx->kstream, ctx->ev_kcb, 0));
-    HIPCHK(launch_kd_build(ctx->kstream, ctx->d_C64_split, K, ctx->D, ctx->d_kdb_vind, ctx->d_kdb_nodes,
-                           ctx->d_kdb_nbox, ctx->d_kdb_cbox, ctx->d_tree, ctx->dh_kdb, ++ctx->kdb_seq));
+    HIPCHK(launch_kd_build(ctx->kstream, ctx->lv.d_C64_split, K, ctx->ts.D, ctx->lv.d_kdb_vind, ctx->lv.d_kdb_nodes,
+                           ctx->lv.d_kdb_nbox, ctx->lv.d_kdb_cbox, ctx->lv.d_tree, ctx->lv.h_kdb.dev(), ++ctx->kdb_seq));
     HIPCHK(hipEventRecord(ctx->ev_kdb, ctx->kstream));
     return QVQ_OK;
 }
@@ -1169,7 +1094,7 @@ qvq_status start_device_tree(qvq_ctx *ctx, uint32_t K) {
 qvq_status finish_device_tree(qvq_ctx *ctx, uint32_t K, KdView &kd, bool &ok) {
     ok = false;
     kd = KdView{};
-    const KdbHeader *h = reinterpret_cast<const KdbHeader *>(ctx->h_kdb);
+    const KdbHeader *h = reinterpret_cast<const KdbHeader *>(ctx->lv.h_kdb.get());
     std::string err;
     const qvq_status st = wait_until(
         [&] { return *reinterpret_cast<const volatile uint64_t *>(&h->seq) >= ctx->kdb_seq; },
@@ -1185,19 +1110,19 @@ qvq_status finish_device_tree(qvq_ctx *ctx, uint32_t K, KdView &kd, bool &ok) {
     std::atomic_thread_fence(std::memory_order_acquire);
     HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_kdb, 0));
     if (h->status != 1) return QVQ_OK;
-    ctx->tree.reset(new RefKDTree(ctx->cb_local.data(), K, (int)ctx->D, ctx->h_kdb));
+    ctx->tree.reset(new RefKDTree(ctx->cb_local.data(), K, (int)ctx->ts.D, ctx->lv.h_kdb));
     KdView t;
     t.depth = (int)h->depth;
     t.n_nodes = h->n_nodes;
-    const uint64_t bytes = 16ull * ctx->D + (uint64_t)h->n_nodes * sizeof(KdNodeDev) + 4ull * K;
+    const uint64_t bytes = 16ull * ctx->ts.D + (uint64_t)h->n_nodes * sizeof(KdNodeDev) + 4ull * K;
     ok = true;
-    if (bytes > ctx->tree_cap) return QVQ_OK;
+    if (bytes > ctx->lv.tree_cap) return QVQ_OK;
     t.bytes = (uint32_t)bytes;
     if (!kd_resolve_fits(t, K)) return QVQ_OK;
-    const double *dlo = reinterpret_cast<const double *>(ctx->d_tree);
+    const double *dlo = reinterpret_cast<const double *>(ctx->lv.d_tree.get());
     t.lo = dlo;
-    t.hi = dlo + ctx->D;
-    t.nodes = reinterpret_cast<const KdNodeDev *>(dlo + 2 * ctx->D);
+    t.hi = dlo + ctx->ts.D;
+    t.nodes = reinterpret_cast<const KdNodeDev *>(dlo + 2 * ctx->ts.D);
     t.vind = reinterpret_cast<const uint32_t *>(t.nodes + t.n_nodes);
     kd = t;
     return QVQ_OK;
@@ -1372,30 +1297,26 @@ qvq_status wait_codebook(qvq_ctx *ctx, uint64_t seq) { return wait_flag(ctx, ctx
 // provisional index to the answer, with xsums within finished sums (launch_fix_rows).  Synchronous.
 qvq_status resolve_host_ties(qvq_ctx *ctx, const double *hC, uint32_t K, uint32_t nt, uint64_t *xslab, uint32_t *xcnt,
                              uint64_t *xsums) {
-    const uint32_t D = ctx->D, Dp = ctx->Dp;
+    const uint32_t D = ctx->ts.D, Dp = ctx->ts.Dp;
     const uint64_t need = (uint64_t)nt * (8 + Dp);
-    if (ctx->scatter_bytes < need) {
-        dfree(ctx->d_scatter);
-        HIPCHK(hipMalloc(&ctx->d_scatter, need));
-        ctx->scatter_bytes = need;
-    }
+    HIPCHK(ctx->d_scatter.ensure(need / 4));
     uint32_t *d_rows = ctx->d_scatter, *d_vals = ctx->d_scatter + nt;
     uint8_t *d_gath = reinterpret_cast<uint8_t *>(ctx->d_scatter + 2 * (uint64_t)nt);
     std::vector<uint32_t> rows(nt), vals(nt);
     std::vector<uint8_t> code((uint64_t)nt * Dp);
-    HIPCHK(launch_gather_codes(ctx->stream, ctx->d_codes, Dp, ctx->d_ties, nt, d_gath));
-    HIPCHK(hipMemcpyAsync(rows.data(), ctx->d_ties, nt * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(launch_gather_codes(ctx->stream, ctx->ts.d_codes, Dp, ctx->ts.d_ties, nt, d_gath));
+    HIPCHK(hipMemcpyAsync(rows.data(), ctx->ts.d_ties, nt * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(code.data(), d_gath, code.size(), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     std::vector<double> q(D);
     RefKDTree tree(hC, K, (int)D);
     for (uint32_t i = 0; i < nt; i++) {
-        for (uint32_t d = 0; d < D; d++) q[d] = ctx->terms.v64[code[(uint64_t)i * Dp + d]];
+        for (uint32_t d = 0; d < D; d++) q[d] = ctx->ts.terms.v64[code[(uint64_t)i * Dp + d]];
         vals[i] = tree.nearest(q.data());
     }
     HIPCHK(hipMemcpyAsync(d_rows, rows.data(), nt * 4, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(d_vals, vals.data(), nt * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(launch_fix_rows(ctx->stream, ctx->d_codes, Dp, D, ctx->d_A, d_rows, d_vals, nt, K, xslab, xcnt,
+    HIPCHK(launch_fix_rows(ctx->stream, ctx->ts.d_codes, Dp, D, ctx->ts.d_A, d_rows, d_vals, nt, K, xslab, xcnt,
                            ctx->d_plut, xsums));
     HIPCHK(hipStreamSynchronize(ctx->stream));   // the host vectors must outlive the copies
     return QVQ_OK;
@@ -1423,21 +1344,21 @@ qvq_status run_level(qvq_ctx *ctx, const LevelPlan &p, uint32_t K, int slot, boo
     // then applied to the finished sums (move_row_sums)
     const bool early_upd = sums_out && !fused && (kd_merge(ctx) || defer_ties);
     // the order the finalize before this level left: valid for the search and the recheck
-    const bool pruned = ctx->perm_k == K;
+    const bool pruned = ctx->lv.perm_k == K;
     // the level's kd-tree on the device, beside the search (every CU holds a search workgroup
     // and room for the build's)
-    const bool devtree = !defer_ties && p.kd_device && p.tree_shape && ctx->kdb_cap >= K && !ctx->exact;
-    uint64_t *sums1 = early_upd ? ctx->d_sums : nullptr;
+    const bool devtree = !defer_ties && p.kd_device && p.tree_shape && ctx->lv.kdb_cap >= K && !ctx->ts.exact;
+    uint64_t *sums1 = early_upd ? ctx->lv.d_sums : nullptr;
     if (fused) {
-        ls.xslab = ctx->d_part + (uint64_t)ctx->G * K * ctx->D;
-        ls.xcnt = ctx->d_part_cnt + (uint64_t)ctx->G * K;
+        ls.xslab = ctx->lv.d_part + (uint64_t)ctx->G * K * ctx->ts.D;
+        ls.xcnt = ctx->lv.d_part_cnt + (uint64_t)ctx->G * K;
         ls.nslabs = ctx->G + 2;
         ls.nsub = 1;
     } else if (sums_out) {
         ls.nslabs = ctx->G;
     }
-    const uint32_t *perm = pruned ? ctx->d_perm : nullptr;
-    const int32_t *tint = pruned ? ctx->d_tint : nullptr;
+    const uint32_t *perm = pruned ? ctx->lv.d_perm : nullptr;
+    const int32_t *tint = pruned ? ctx->lv.d_tint : nullptr;
     unsigned *cnt = ctx->d_counters + 2 * slot;
     // HIP events around the search (each record costs a few us of GPU idle): every level,
     // one level, or none (qvq_set_timing)
@@ -1449,50 +1370,50 @@ qvq_status run_level(qvq_ctx *ctx, const LevelPlan &p, uint32_t K, int slot, boo
         // one rank, fused sums: the search clears copy 1 of the final sums (the kd ties' moves,
         // added by the previous level's finalize), covering every smaller level's layout
         const bool clear1 = fused && kd_merge(ctx);
-        HIPCHK(launch_assign_mfma(ctx->stream, ctx->num_cu, fused, ctx->d_codes, ctx->N, ctx->d_rows, ctx->d_E32, K,
-                                  ctx->d_C32, ctx->d_plut, ctx->mf_th, ctx->d_A, ctx->d_flags, &cnt[0],
-                                  ctx->d_part, ctx->d_part_cnt, perm, tint,
-                                  clear1 ? ctx->d_sums + sums_cap_stride(ctx) : nullptr,
-                                  clear1 ? (uint32_t)(2 * (uint64_t)K * ctx->D + K) : 0u));
+        HIPCHK(launch_assign_mfma(ctx->stream, ctx->num_cu, fused, ctx->ts.d_codes, ctx->ts.N, ctx->lv.d_rows, ctx->lv.d_E32, K,
+                                  ctx->lv.d_C32, ctx->d_plut, ctx->ts.mf_th, ctx->ts.d_A, ctx->ts.d_flags, &cnt[0],
+                                  ctx->lv.d_part, ctx->lv.d_part_cnt, perm, tint,
+                                  clear1 ? ctx->lv.d_sums + sums_cap_stride(ctx) : nullptr,
+                                  clear1 ? (uint32_t)(2 * (uint64_t)K * ctx->ts.D + K) : 0u));
     } else if (p.search == QVQ_PLAN_SEARCH_WIDE) {
-        HIPCHK(launch_assign_wide(ctx->stream, ctx->num_cu, ctx->Dp, ctx->D, ctx->d_codes, ctx->N, ctx->d_rows, K,
-                                  ctx->d_C32, ctx->mf_th, ctx->d_A, ctx->d_flags, &cnt[0], perm, tint,
+        HIPCHK(launch_assign_wide(ctx->stream, ctx->num_cu, ctx->ts.Dp, ctx->ts.D, ctx->ts.d_codes, ctx->ts.N, ctx->lv.d_rows, K,
+                                  ctx->lv.d_C32, ctx->ts.mf_th, ctx->ts.d_A, ctx->ts.d_flags, &cnt[0], perm, tint,
                                   std::max<uint32_t>(1, (ctx->col_blocks + 32) / 64), ctx->d_counters + SCHED_COUNTERS));
     } else {
         float alpha, beta, gamma;
         valu_coeffs(ctx, alpha, beta, gamma);
-        HIPCHK(launch_assign_valu(ctx->stream, ctx->num_cu, ctx->Dp, ctx->d_codes, ctx->N, ctx->d_C32, K,
-                                  ctx->d_lut32, alpha, beta, gamma, ctx->d_A, ctx->d_flags, &cnt[0]));
+        HIPCHK(launch_assign_valu(ctx->stream, ctx->num_cu, ctx->ts.Dp, ctx->ts.d_codes, ctx->ts.N, ctx->lv.d_C32, K,
+                                  ctx->d_lut32, alpha, beta, gamma, ctx->ts.d_A, ctx->ts.d_flags, &cnt[0]));
     }
     if (timing) HIPCHK(hipEventRecord(ctx->ev[slot][1], ctx->stream));
     if (p.recheck == QVQ_PLAN_RECHECK_MF32) {
-        HIPCHK(launch_recheck_mf32(ctx->stream, ctx->num_cu, ctx->d_codes, ctx->d_flags, &cnt[0], ctx->d_rows,
-                                   ctx->d_C64_split, K, ctx->d_lut64, ctx->mf_th, 1e-12, tie_band(ctx), ctx->d_A, ctx->d_ties,
+        HIPCHK(launch_recheck_mf32(ctx->stream, ctx->num_cu, ctx->ts.d_codes, ctx->ts.d_flags, &cnt[0], ctx->lv.d_rows,
+                                   ctx->lv.d_C64_split, K, ctx->d_lut64, ctx->ts.mf_th, 1e-12, tie_band(ctx), ctx->ts.d_A, ctx->ts.d_ties,
                                    &cnt[1], ls.xslab, ls.xcnt, ctx->d_plut));
     } else {
         float alpha, beta, gamma;
         valu_coeffs(ctx, alpha, beta, gamma);
-        HIPCHK(launch_recheck(ctx->stream, ctx->num_cu, ctx->d_codes, ctx->Dp, ctx->D, ctx->d_flags, &cnt[0],
-                              ctx->d_C64_split, ctx->d_C32, K, ctx->d_lut64, alpha, beta, gamma, 1e-12, tie_band(ctx), ctx->d_A,
-                              ctx->d_ties, &cnt[1], ls.xslab, ls.xcnt, ctx->d_plut, perm, tint,
-                              (float)((double)ctx->D / (ctx->terms.sx * ctx->terms.sx))));
+        HIPCHK(launch_recheck(ctx->stream, ctx->num_cu, ctx->ts.d_codes, ctx->ts.Dp, ctx->ts.D, ctx->ts.d_flags, &cnt[0],
+                              ctx->lv.d_C64_split, ctx->lv.d_C32, K, ctx->d_lut64, alpha, beta, gamma, 1e-12, tie_band(ctx), ctx->ts.d_A,
+                              ctx->ts.d_ties, &cnt[1], ls.xslab, ls.xcnt, ctx->d_plut, perm, tint,
+                              (float)((double)ctx->ts.D / (ctx->ts.terms.sx * ctx->ts.terms.sx))));
     }
     if (defer_ties) {   // the level's tie count to the host, before the rest of the level runs
         ctx->pub_seq++;
         if (fused) {   // published by the slab reduce that follows (reduce_level): no launch of its own
             ls.pub.cnt = &cnt[1];
-            ls.pub.dst = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(ctx->dh_ready) + 16);
-            ls.pub.flag = ctx->dh_ready + 1;
+            ls.pub.dst = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(ctx->h_ready.dev()) + 16);
+            ls.pub.flag = ctx->h_ready.dev() + 1;
             ls.pub.seq = ctx->pub_seq;
         } else {
-            HIPCHK(launch_copy_out(ctx->stream, &cnt[1], reinterpret_cast<uint8_t *>(ctx->dh_ready) + 16, 4, nullptr,
-                                   nullptr, 0, nullptr, nullptr, 0, ctx->dh_ready + 1, ctx->pub_seq,
+            HIPCHK(launch_copy_out(ctx->stream, &cnt[1], reinterpret_cast<uint8_t *>(ctx->h_ready.dev()) + 16, 4, nullptr,
+                                   nullptr, 0, nullptr, nullptr, 0, ctx->h_ready.dev() + 1, ctx->pub_seq,
                                    ctx->d_counters + COPY_DONE_COUNTER));
         }
     }
     if (early_upd) {
         HIPCHK(hipEventRecord(ctx->ev[slot][2], ctx->stream));
-        if ((st = run_update(ctx, p, ctx->d_A, K)) != QVQ_OK) return st;
+        if ((st = run_update(ctx, p, ctx->ts.d_A, K)) != QVQ_OK) return st;
         ls.nslabs = 0;   // reduced already
         HIPCHK(hipEventRecord(ctx->ev[slot][3], ctx->stream));
     }
@@ -1508,9 +1429,9 @@ qvq_status run_level(qvq_ctx *ctx, const LevelPlan &p, uint32_t K, int slot, boo
     KdView kd;
     bool dev_ok = false;
     if (devtree) {   // the host copies of the codebook and parent counts, then the device's tree
-        ctx->cb_local.assign(hC, hC + (size_t)K * ctx->D);
+        ctx->cb_local.assign(hC, hC + (size_t)K * ctx->ts.D);
         if ((hC == host_cb_of(ctx, 0) || hC == host_cb_of(ctx, 1)) && K >= 2) {
-            const uint32_t *pc = reinterpret_cast<const uint32_t *>(hC + (size_t)K * ctx->D);
+            const uint32_t *pc = reinterpret_cast<const uint32_t *>(hC + (size_t)K * ctx->ts.D);
             ctx->cnt_local.assign(pc, pc + K / 2);
         } else {
             ctx->cnt_local.clear();
@@ -1527,8 +1448,8 @@ qvq_status run_level(qvq_ctx *ctx, const LevelPlan &p, uint32_t K, int slot, boo
         ls.kd = kd;
         ls.copies = 2;
     } else if (kd.depth > 0) {
-        HIPCHK(launch_kd_resolve(ctx->stream, ctx->d_codes, ctx->Dp, ctx->D, ctx->d_ties, &cnt[1], ctx->d_C64_split,
-                                 K, ctx->d_lut64, kd, ctx->d_A, ls.xslab, ls.xcnt, ctx->d_plut, sums1));
+        HIPCHK(launch_kd_resolve(ctx->stream, ctx->ts.d_codes, ctx->ts.Dp, ctx->ts.D, ctx->ts.d_ties, &cnt[1], ctx->lv.d_C64_split,
+                                 K, ctx->d_lut64, kd, ctx->ts.d_A, ls.xslab, ls.xcnt, ctx->d_plut, sums1));
     } else {   // ties answered on the host
         unsigned nt = 0;
         HIPCHK(hipMemcpyAsync(&nt, &cnt[1], sizeof(nt), hipMemcpyDeviceToHost, ctx->stream));
@@ -1538,7 +1459,7 @@ qvq_status run_level(qvq_ctx *ctx, const LevelPlan &p, uint32_t K, int slot, boo
     ls.upd = sums_out && !fused;
     if (ls.upd && !early_upd) {
         HIPCHK(hipEventRecord(ctx->ev[slot][2], ctx->stream));
-        if ((st = run_update_slabs(ctx, p, ctx->d_A, K, ls.nslabs)) != QVQ_OK) return st;
+        if ((st = run_update_slabs(ctx, p, ctx->ts.d_A, K, ls.nslabs)) != QVQ_OK) return st;
         HIPCHK(hipEventRecord(ctx->ev[slot][3], ctx->stream));
     }
     return QVQ_OK;
@@ -1554,11 +1475,11 @@ qvq_status reduce_level(qvq_ctx *ctx, uint32_t K, int slot, const LevelSums &ls,
     rs.gate = ls.copies > 1 ? tcnt : nullptr;
     if (ls.kd_pend) {
         mark_sums1(ctx);
-        HIPCHK(launch_kd_reduce(ctx->stream, ctx->d_codes, ctx->Dp, ctx->D, ctx->d_ties, tcnt, ctx->d_C64_split, K,
-                                ctx->d_lut64, ls.kd, ctx->d_A, ctx->d_plut, ctx->d_part, ctx->d_part_cnt,
-                                ls.nslabs, ls.nsub, ctx->d_sums, ctx->d_sums + sums_cap_stride(ctx)));
+        HIPCHK(launch_kd_reduce(ctx->stream, ctx->ts.d_codes, ctx->ts.Dp, ctx->ts.D, ctx->ts.d_ties, tcnt, ctx->lv.d_C64_split, K,
+                                ctx->d_lut64, ls.kd, ctx->ts.d_A, ctx->d_plut, ctx->lv.d_part, ctx->lv.d_part_cnt,
+                                ls.nslabs, ls.nsub, ctx->lv.d_sums, ctx->lv.d_sums + sums_cap_stride(ctx)));
     } else if (ls.nslabs) {
-        HIPCHK(launch_reduce(ctx->stream, ctx->d_part, ctx->d_part_cnt, ls.nslabs, ls.nsub, K, ctx->D, ctx->d_sums, ls.pub));
+        HIPCHK(launch_reduce(ctx->stream, ctx->lv.d_part, ctx->lv.d_part_cnt, ls.nslabs, ls.nsub, K, ctx->ts.D, ctx->lv.d_sums, ls.pub));
     }
     if (ls.pub.flag && (ls.kd_pend || !ls.nslabs))   // the slab reduce did not run: a launch of its own
         HIPCHK(launch_copy_out(ctx->stream, ls.pub.cnt, ls.pub.dst, 4, nullptr, nullptr, 0, nullptr, nullptr, 0,
@@ -1715,7 +1636,7 @@ template <class Sync>
 qvq_status certify_rows(qvq_ctx *ctx, const RefKDTree &tree, const double *cb, const std::vector<uint32_t> &pcnt,
                         uint32_t K, const uint32_t *A_prev, hipStream_t stream, Sync sync, CertState &cs, bool defer,
                         uint32_t &open_rows) {
-    const uint32_t D = ctx->D, Kc = K / 2, nu = cs.nu;
+    const uint32_t D = ctx->ts.D, Kc = K / 2, nu = cs.nu;
     const std::vector<double> &qs = cs.qs;
     std::vector<int64_t> &ans = cs.ans;
     if (!cs.prepared) cert_init(tree, cs, cb, pcnt, K, D, false);
@@ -1803,20 +1724,20 @@ qvq_status certify_rows(qvq_ctx *ctx, const RefKDTree &tree, const double *cb, c
         if ((s2 = ensure_kahan(ctx, Kc)) != QVQ_OK) return s2;
         cell_of.clear();
         for (uint32_t c = 0; c < Kc; c++) {
-            ctx->h_kc_sel[c] = pick[c] ? (uint32_t)cell_of.size() + 1 : 0u;
+            ctx->kh.cells.h_kc_sel[c] = pick[c] ? (uint32_t)cell_of.size() + 1 : 0u;
             if (pick[c]) cell_of.push_back(c);
         }
         if (A_prev) {
             // the longest chain (the finalize's parent counts): short ones run step by step
             uint64_t max_rows = pcnt.size() == Kc ? 1 : 0;
             for (uint32_t c : cell_of) max_rows = max_rows ? std::max<uint64_t>(max_rows, pcnt[c]) : 0;
-            HIPCHK(hipMemcpyAsync(ctx->d_kc_sel, ctx->h_kc_sel, (size_t)Kc * 4, hipMemcpyHostToDevice, stream));
-            HIPCHK(launch_kahan_centroids(stream, ctx->kw, ctx->d_codes, ctx->Dp, D, ctx->N, A_prev,
-                                          (uint32_t)cell_of.size(), ctx->d_kc_cent, ctx->dh_kc_out, ctx->d_kc_sel, Kc,
+            HIPCHK(hipMemcpyAsync(ctx->kh.cells.d_kc_sel, ctx->kh.cells.h_kc_sel, (size_t)Kc * 4, hipMemcpyHostToDevice, stream));
+            HIPCHK(launch_kahan_centroids(stream, ctx->kh.kw, ctx->ts.d_codes, ctx->ts.Dp, D, ctx->ts.N, A_prev,
+                                          (uint32_t)cell_of.size(), ctx->kh.cells.d_kc_cent, ctx->kh.cells.h_kc_out.dev(), ctx->kh.cells.d_kc_sel, Kc,
                                           max_rows));
         } else {   // K = 2: the one parent cell is the mean of every row
-            HIPCHK(launch_kahan_centroids(stream, ctx->kw, ctx->d_codes, ctx->Dp, D, ctx->N, nullptr, 1,
-                                          ctx->d_kc_cent, ctx->dh_kc_out, nullptr, 0, ctx->N));
+            HIPCHK(launch_kahan_centroids(stream, ctx->kh.kw, ctx->ts.d_codes, ctx->ts.Dp, D, ctx->ts.N, nullptr, 1,
+                                          ctx->kh.cells.d_kc_cent, ctx->kh.cells.h_kc_out.dev(), nullptr, 0, ctx->ts.N));
         }
         cert_trace.mark("launched");
         return QVQ_OK;
@@ -1825,7 +1746,7 @@ qvq_status certify_rows(qvq_ctx *ctx, const RefKDTree &tree, const double *cb, c
         qvq_status s2;
         if ((s2 = sync()) != QVQ_OK) return s2;
         cert_trace.mark("sums");
-        cert_apply_cells(tree, cs, Kc, D, cell_of, ctx->h_kc_out);
+        cert_apply_cells(tree, cs, Kc, D, cell_of, ctx->kh.cells.h_kc_out);
         return QVQ_OK;
     };
     open.clear();
@@ -1914,35 +1835,31 @@ uint32_t distinct_rows(const qvq_ctx *ctx, const uint8_t *code, size_t stride, u
     qs.clear();
     for (uint32_t i = 0; i < n; i++) {
         const uint8_t *c = code + (size_t)i * stride;
-        const auto it = uniq.emplace(std::string(reinterpret_cast<const char *>(c), ctx->D), (uint32_t)uniq.size());
+        const auto it = uniq.emplace(std::string(reinterpret_cast<const char *>(c), ctx->ts.D), (uint32_t)uniq.size());
         of[i] = it.first->second;
         if (it.second)
-            for (uint32_t d = 0; d < ctx->D; d++) qs.push_back(ctx->terms.v64[c[d]]);
+            for (uint32_t d = 0; d < ctx->ts.D; d++) qs.push_back(ctx->ts.terms.v64[c[d]]);
     }
     return (uint32_t)uniq.size();
 }
 
 qvq_status certify_kahan_ties(qvq_ctx *ctx, uint32_t K, unsigned nt, uint64_t *target, bool &done) {
     done = false;
-    if (!ctx->tree || ctx->cb_local.size() != (size_t)K * ctx->D || K < 2) return QVQ_OK;
-    const uint32_t D = ctx->D, Dp = ctx->Dp;
+    if (!ctx->tree || ctx->cb_local.size() != (size_t)K * ctx->ts.D || K < 2) return QVQ_OK;
+    const uint32_t D = ctx->ts.D, Dp = ctx->ts.Dp;
     const uint64_t need = (uint64_t)nt * (4 + Dp);
-    if (ctx->scatter_bytes < need) {
-        dfree(ctx->d_scatter);
-        HIPCHK(hipMalloc(&ctx->d_scatter, need));
-        ctx->scatter_bytes = need;
-    }
+    HIPCHK(ctx->d_scatter.ensure(need / 4));
     uint32_t *d_vals = ctx->d_scatter;
     uint8_t *d_gath = reinterpret_cast<uint8_t *>(ctx->d_scatter + nt);
     std::vector<uint8_t> code((uint64_t)nt * Dp);
-    HIPCHK(launch_gather_codes(ctx->stream, ctx->d_codes, Dp, ctx->d_ties, nt, d_gath));
+    HIPCHK(launch_gather_codes(ctx->stream, ctx->ts.d_codes, Dp, ctx->ts.d_ties, nt, d_gath));
     HIPCHK(hipMemcpyAsync(code.data(), d_gath, code.size(), hipMemcpyDeviceToHost, ctx->stream));
     qvq_status st;
     if ((st = wait_stream(ctx)) != QVQ_OK) return st;
     CertState cs;
     cs.nu = distinct_rows(ctx, code.data(), Dp, nt, cs.qs, cs.of);
     uint32_t open = 0;
-    if ((st = certify_rows(ctx, *ctx->tree, ctx->cb_local.data(), ctx->cnt_local, K, K == 2 ? nullptr : ctx->d_A_alt, ctx->stream,
+    if ((st = certify_rows(ctx, *ctx->tree, ctx->cb_local.data(), ctx->cnt_local, K, K == 2 ? nullptr : ctx->ts.d_A_alt, ctx->stream,
                            [ctx] { return wait_stream(ctx); }, cs, false, open)) != QVQ_OK)
         return st;
     if (open) {
@@ -1955,7 +1872,7 @@ qvq_status certify_kahan_ties(qvq_ctx *ctx, uint32_t K, unsigned nt, uint64_t *t
     vals.resize(nt);
     for (uint32_t i = 0; i < nt; i++) vals[i] = (uint32_t)cs.ans[cs.of[i]];
     HIPCHK(hipMemcpyAsync(d_vals, vals.data(), nt * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(launch_fix_rows(ctx->stream, ctx->d_codes, Dp, D, ctx->d_A, ctx->d_ties, d_vals, nt, K, nullptr, nullptr,
+    HIPCHK(launch_fix_rows(ctx->stream, ctx->ts.d_codes, Dp, D, ctx->ts.d_A, ctx->ts.d_ties, d_vals, nt, K, nullptr, nullptr,
                            ctx->d_plut, target));
     if (env_is("QVQ_KAHAN_DEBUG", "1"))
         std::fprintf(stderr, "qvq kahan: K %u ties %u (%u distinct) certified, cells summed %u in %u rounds\n", K, nt,
@@ -1986,9 +1903,9 @@ void verify_level(qvq_ctx *ctx, qvq_ctx::Verify &v) {
     // replay too (C3: the last level's 2 tie rows took ~95 us after the export, r05i)
     // (C3 1.241 -> 1.197 ms, C4 7.51 -> 7.18, profiles/r05p)
     if (!v.cs.prepared && v.tree && !v.tree->cancelled() && v.K >= 2 &&
-        v.cb.size() == (size_t)v.K * ctx->D) {
-        const bool full = (uint64_t)v.K * ctx->D < 65536;
-        cert_init(*v.tree, v.cs, v.cb.data(), v.cnt, v.K, ctx->D, full, ctx);
+        v.cb.size() == (size_t)v.K * ctx->ts.D) {
+        const bool full = (uint64_t)v.K * ctx->ts.D < 65536;
+        cert_init(*v.tree, v.cs, v.cb.data(), v.cnt, v.K, ctx->ts.D, full, ctx);
         ctx->htrace.mark("check K" + std::to_string(v.K) + " known split set");
         if (!full)
             v.tree->cert_warm(KAHAN_DELTA, v.cs.kp.data(), v.cs.known.data(), cert_helpers(ctx),
@@ -2009,7 +1926,7 @@ void verify_level(qvq_ctx *ctx, qvq_ctx::Verify &v) {
     cert_trace.on = trace;
     cert_trace.t0 = std::chrono::steady_clock::now();
     cert_trace.s.clear();
-    const uint32_t *tx = reinterpret_cast<const uint32_t *>(ctx->h_tx[v.par]);
+    const uint32_t *tx = reinterpret_cast<const uint32_t *>(ctx->h_tx[v.par].get());
     const uint32_t nt = tx[0];
     if (nt == 0) {
         v.status = 0;
@@ -2020,7 +1937,7 @@ void verify_level(qvq_ctx *ctx, qvq_ctx::Verify &v) {
         return;
     }
     if (!v.tree || v.tree->cancelled() || v.K < 2) return;
-    const uint32_t Dp = ctx->Dp, words = 2 + Dp / 4;
+    const uint32_t Dp = ctx->ts.Dp, words = 2 + Dp / 4;
     std::vector<uint32_t> rec(tx + 2, tx + 2 + (size_t)nt * words);   // out of the mapped buffer at once
     CertState &cs = v.cs;
     cs.rows.resize(nt);
@@ -2028,7 +1945,7 @@ void verify_level(qvq_ctx *ctx, qvq_ctx::Verify &v) {
     for (uint32_t i = 0; i < nt; i++) {
         cs.rows[i] = rec[(size_t)i * words];
         cs.spec[i] = rec[(size_t)i * words + 1];
-        if (cs.rows[i] >= ctx->N || cs.spec[i] >= v.K) return;
+        if (cs.rows[i] >= ctx->ts.N || cs.spec[i] >= v.K) return;
     }
     cs.nu = distinct_rows(ctx, reinterpret_cast<const uint8_t *>(rec.data() + 2), (size_t)words * 4, nt, cs.qs, cs.of);
     uint32_t open = 0;
@@ -2076,7 +1993,7 @@ void verify_level(qvq_ctx *ctx, qvq_ctx::Verify &v) {
 }
 
 // The check's verdict (status 0 / 1 / 2, -1: none posted); its tree and rows are released,
-// except a deferred check's (status 2, several ranks), which moves to ctx->deferred.
+// except a deferred check's (status 2, several ranks), which moves to ctx->kh.deferred.
 
 // free_on_worker: the check's tree and state are destroyed on the worker, not here (the last
 // level's at the end of a call: C4's K = 4096 tree and certificate free ~30 us of buffers, with
@@ -2087,14 +2004,14 @@ int join_verify(qvq_ctx *ctx, qvq_ctx::Verify &v, bool free_on_worker = false) {
     v.posted = false;
     const int status = v.status;
     if (status == 2) {
-        qvq_ctx::Deferred d;
+        qvq_ctx::Kahan::Deferred d;
         d.level = v.level;
         d.K = v.K;
         d.A_prev = v.A_prev;
         d.tree = std::move(v.tree);
         d.cb = std::move(v.cb);
         d.cs = std::move(v.cs);
-        ctx->deferred.push_back(std::move(d));
+        ctx->kh.deferred.push_back(std::move(d));
     }
     if (free_on_worker && v.tree) {
         RefKDTree *t = v.tree.release();
@@ -2131,29 +2048,22 @@ qvq_status join_verify_bounded(qvq_ctx *ctx, qvq_ctx::Verify &v, bool &ok, bool 
     return QVQ_OK;
 }
 
-// The speculative check's buffers (once per context): the third assignment buffer, the mapped
-// tie exports, the check's stream and events, and the Kahan work for the largest level.
+// The speculative check's buffers: four assignment buffers (per training set), once per context
+// the mapped tie exports, the check's stream and events, and the Kahan work for the largest level.
 qvq_status ensure_speculation(qvq_ctx *ctx, uint32_t Kmax) {
-    if (!ctx->d_A_alt) HIPCHK(hipMalloc(&ctx->d_A_alt, ctx->N * 4));
-    if (!ctx->d_A3) HIPCHK(hipMalloc(&ctx->d_A3, ctx->N * 4));
-    if (!ctx->d_A4) HIPCHK(hipMalloc(&ctx->d_A4, ctx->N * 4));
-    if (!ctx->h_tx[0]) {
-        ctx->tx_cap = 65536;
-        const size_t bytes = 8 + (size_t)ctx->tx_cap * (8 + 64);
-        for (int i = 0; i < 3; i++) {
-            HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&ctx->h_tx[i]), bytes, hipHostMallocMapped));
-            HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void **>(&ctx->dh_tx[i]), ctx->h_tx[i], 0));
-        }
-    }
+    qvq_status st = ensure_apool(ctx, ctx->ts, 4);
+    if (st != QVQ_OK) return st;
+    ctx->tx_cap = 65536;
+    for (auto &h : ctx->h_tx) HIPCHK(h.ensure(8 + (size_t)ctx->tx_cap * (8 + 64)));
     if (!ctx->vstream) {   // high priority: the check's few short kernels go ahead of the next search's queued blocks
         int lo = 0, hi = 0;
         if (hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && hi != lo)
-            HIPCHK(hipStreamCreateWithPriority(&ctx->vstream, hipStreamNonBlocking, hi));
+            HIPCHK(hipStreamCreateWithPriority(ctx->vstream.put(), hipStreamNonBlocking, hi));
         else
-            HIPCHK(hipStreamCreateWithFlags(&ctx->vstream, hipStreamNonBlocking));
+            HIPCHK(hipStreamCreateWithFlags(ctx->vstream.put(), hipStreamNonBlocking));
     }
     for (auto &v : ctx->ver)
-        if (!v.ev) HIPCHK(hipEventCreateWithFlags(&v.ev, hipEventDisableTiming));
+        if (!v.ev) HIPCHK(hipEventCreateWithFlags(v.ev.put(), hipEventDisableTiming));
     return Kmax >= 4 ? ensure_kahan(ctx, Kmax / 2) : QVQ_OK;
 }
 
@@ -2164,7 +2074,7 @@ qvq_status ensure_speculation(qvq_ctx *ctx, uint32_t Kmax) {
 // is no device image.  The rows' terms move within the sums at target.
 qvq_status answer_kahan_ties(qvq_ctx *ctx, const LevelPlan &p, uint32_t K, int slot, unsigned nt, const double *S_ref,
                              uint64_t *target) {
-    const uint32_t D = ctx->D;
+    const uint32_t D = ctx->ts.D;
     ctx->h_kc_split.resize((size_t)K * D);
     HIPCHK(hipMemcpyAsync(ctx->h_kc_split.data(), S_ref, (size_t)K * D * 8, hipMemcpyDeviceToHost, ctx->stream));
     const qvq_status st = wait_stream(ctx);
@@ -2178,8 +2088,8 @@ qvq_status answer_kahan_ties(qvq_ctx *ctx, const LevelPlan &p, uint32_t K, int s
         build_tree(ctx, p, ctx->h_kc_split.data(), K, slot & 1, kd);
     }
     if (kd.depth > 0) {
-        HIPCHK(launch_kd_resolve(ctx->stream, ctx->d_codes, ctx->Dp, D, ctx->d_ties, ctx->d_counters + 2 * slot + 1, S_ref,
-                                 K, ctx->d_lut64, kd, ctx->d_A, nullptr, nullptr, ctx->d_plut, target));
+        HIPCHK(launch_kd_resolve(ctx->stream, ctx->ts.d_codes, ctx->ts.Dp, D, ctx->ts.d_ties, ctx->d_counters + 2 * slot + 1, S_ref,
+                                 K, ctx->d_lut64, kd, ctx->ts.d_A, nullptr, nullptr, ctx->d_plut, target));
         return QVQ_OK;
     }
     return resolve_host_ties(ctx, ctx->h_kc_split.data(), K, nt, nullptr, nullptr, target);
@@ -2192,10 +2102,10 @@ qvq_status answer_kahan_ties(qvq_ctx *ctx, const LevelPlan &p, uint32_t K, int s
 // The moves go to sums copy 1 (a fusable level: rs then has the finalize add it) or straight
 // into copy 0.
 qvq_status resolve_kahan_ties(qvq_ctx *ctx, const LevelPlan &p, uint32_t K, int slot, unsigned nt, ReducedSums &rs) {
-    const uint32_t D = ctx->D, Kc = K / 2;
-    const double *S_ref = ctx->d_C64_split;
+    const uint32_t D = ctx->ts.D, Kc = K / 2;
+    const double *S_ref = ctx->lv.d_C64_split;
     qvq_status st;
-    uint64_t *target = ctx->d_sums;
+    uint64_t *target = ctx->lv.d_sums;
     rs = ReducedSums();
     if (p.fusable) {
         mark_sums1(ctx);
@@ -2203,17 +2113,17 @@ qvq_status resolve_kahan_ties(qvq_ctx *ctx, const LevelPlan &p, uint32_t K, int 
         rs.copies = 2;
         rs.gate = ctx->d_counters + 2 * slot + 1;
     }
-    if (ctx->cs == QVQ_CS_SCALED) {
+    if (ctx->ts.cs == QVQ_CS_SCALED) {
         bool done;
         if ((st = certify_kahan_ties(ctx, K, nt, target, done)) != QVQ_OK || done) return st;
         if ((st = ensure_kahan(ctx, Kc)) != QVQ_OK) return st;
-        HIPCHK(launch_kahan_centroids(ctx->stream, ctx->kw, ctx->d_codes, ctx->Dp, D, ctx->N,
-                                      K == 2 ? nullptr : ctx->d_A_alt, Kc, ctx->d_kc_cent, ctx->d_kc_split));
-        S_ref = ctx->d_kc_split;
+        HIPCHK(launch_kahan_centroids(ctx->stream, ctx->kh.kw, ctx->ts.d_codes, ctx->ts.Dp, D, ctx->ts.N,
+                                      K == 2 ? nullptr : ctx->ts.d_A_alt, Kc, ctx->kh.cells.d_kc_cent, ctx->kh.cells.d_kc_split));
+        S_ref = ctx->kh.cells.d_kc_split;
         if (env_is("QVQ_KAHAN_DEBUG", "1")) {   // blocks not composable, block misses, segment replays
             unsigned ms[4];
-            HIPCHK(hipMemcpyAsync(ms, ctx->kw.stats, sizeof(ms), hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(hipMemsetAsync(ctx->kw.stats, 0, sizeof(ms), ctx->stream));
+            HIPCHK(hipMemcpyAsync(ms, ctx->kh.kw.stats, sizeof(ms), hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(hipMemsetAsync(ctx->kh.kw.stats, 0, sizeof(ms), ctx->stream));
             HIPCHK(hipStreamSynchronize(ctx->stream));
             std::fprintf(stderr, "qvq kahan: K %u level ties %u blocks not composable %u block misses %u replays %u\n",
                          K, nt, ms[0], ms[1], ms[2]);
@@ -2231,29 +2141,29 @@ qvq_status resolve_kahan_ties_multi(qvq_ctx *ctx, const LevelPlan &p, uint32_t K
     const uint32_t Kc = K / 2;
     qvq_status st;
     mark_sums1(ctx);
-    uint64_t *target = ctx->d_sums + sums_cap_stride(ctx);
+    uint64_t *target = ctx->lv.d_sums + sums_cap_stride(ctx);
     rs = ReducedSums();
     rs.copies = 2;
-    if ((st = kahan_chained(ctx, K == 2 ? nullptr : ctx->d_A_alt, Kc, nullptr, Kc, true)) != QVQ_OK) return st;
-    if ((st = answer_kahan_ties(ctx, p, K, slot, nt, ctx->d_kc_split, target)) != QVQ_OK) return st;
+    if ((st = kahan_chained(ctx, K == 2 ? nullptr : ctx->ts.d_A_alt, Kc, nullptr, Kc, true)) != QVQ_OK) return st;
+    if ((st = answer_kahan_ties(ctx, p, K, slot, nt, ctx->kh.cells.d_kc_split, target)) != QVQ_OK) return st;
     return all_reduce_sums(ctx, K, target);
 }
 
 // Several ranks, at the end of a speculative qvq_lbg: the checks whose rows wait
-// for cells summed over every rank's rows (ctx->deferred).  A vote of every rank's failure and,
+// for cells summed over every rank's rows (ctx->kh.deferred).  A vote of every rank's failure and,
 // per level, of the cells its open rows need; then for each level with cells wanted (ascending,
 // every rank the same), their reference bits from the chains over every rank's rows
 // (kahan_chained on the level's parent assignment, alev[L - 1]) and this rank's open rows
 // replayed with them (cert_finish); a second vote of the failures.  failed: in, this rank's
 // failure so far; out, any rank's (the quantize is then redone on every rank).
 qvq_status resolve_deferred(qvq_ctx *ctx, uint32_t bits, const std::vector<uint32_t *> &alev, bool &failed) {
-    const uint32_t D = ctx->D;
+    const uint32_t D = ctx->ts.D;
     // [0] failures | per level L: its parent cells (2^(L-1)), four 16-bit counts per word
     std::vector<uint64_t> off(bits + 2, 1);
     for (uint32_t L = 1; L <= bits; L++) off[L + 1] = off[L] + ((1ull << (L - 1)) + 3) / 4;
     std::vector<uint64_t> v(off[bits + 1], 0);
     v[0] = failed ? 1 : 0;
-    for (const auto &d : ctx->deferred)
+    for (const auto &d : ctx->kh.deferred)
         for (uint32_t c = 0; c < d.K / 2; c++)
             if (d.cs.sel[c]) v[off[d.level] + c / 4] |= 1ull << (16 * (c % 4));
     qvq_status st;
@@ -2271,7 +2181,7 @@ qvq_status resolve_deferred(qvq_ctx *ctx, uint32_t bits, const std::vector<uint3
         for (uint32_t c = 0; c < Kc; c++)
             if ((v[off[L] + c / 4] >> (16 * (c % 4))) & 0xFFFF) cell_of.push_back(c);
         if (cell_of.empty()) {   // no rank wants a cell here: rows still open stay open (a redo)
-            for (const auto &d : ctx->deferred)
+            for (const auto &d : ctx->kh.deferred)
                 if (d.level == L && !d.cs.pend.empty()) local_fail = true;
             continue;
         }
@@ -2279,18 +2189,18 @@ qvq_status resolve_deferred(qvq_ctx *ctx, uint32_t bits, const std::vector<uint3
         const uint32_t S = (uint32_t)cell_of.size();
         if ((st = ensure_kahan(ctx, Kc)) != QVQ_OK) return st;
         if (L >= 2) {
-            for (uint32_t c = 0; c < Kc; c++) ctx->h_kc_sel[c] = 0;
-            for (uint32_t t = 0; t < S; t++) ctx->h_kc_sel[cell_of[t]] = t + 1;
-            HIPCHK(hipMemcpyAsync(ctx->d_kc_sel, ctx->h_kc_sel, (size_t)Kc * 4, hipMemcpyHostToDevice, ctx->stream));
-            st = kahan_chained(ctx, alev[L - 1], Kc, ctx->d_kc_sel, S, true);
+            for (uint32_t c = 0; c < Kc; c++) ctx->kh.cells.h_kc_sel[c] = 0;
+            for (uint32_t t = 0; t < S; t++) ctx->kh.cells.h_kc_sel[cell_of[t]] = t + 1;
+            HIPCHK(hipMemcpyAsync(ctx->kh.cells.d_kc_sel, ctx->kh.cells.h_kc_sel, (size_t)Kc * 4, hipMemcpyHostToDevice, ctx->stream));
+            st = kahan_chained(ctx, alev[L - 1], Kc, ctx->kh.cells.d_kc_sel, S, true);
         } else {
             st = kahan_chained(ctx, nullptr, 1, nullptr, 1, true);
         }
         if (st != QVQ_OK) return st;
         split.resize(2ull * S * D);
-        HIPCHK(hipMemcpyAsync(split.data(), ctx->d_kc_split, split.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(split.data(), ctx->kh.cells.d_kc_split, split.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
         if ((st = wait_stream(ctx)) != QVQ_OK) return st;
-        for (auto &d : ctx->deferred) {
+        for (auto &d : ctx->kh.deferred) {
             if (d.level != L) continue;
             const uint32_t open = cert_finish(*d.tree, d.cs, d.K, D, cell_of, split.data());
             const bool bad = open || cert_mismatch(d.cs, d.K);
@@ -2309,7 +2219,7 @@ qvq_status resolve_deferred(qvq_ctx *ctx, uint32_t bits, const std::vector<uint3
 // The byte histogram of the resident rows (kept on the device: qvq_lbg derives sum ||x||^2 and
 // the row count from it, after summing it over the ranks).
 qvq_status compute_xsq(qvq_ctx *ctx) {
-    HIPCHK(launch_byte_hist(ctx->stream, ctx->d_codes, ctx->N, ctx->D, ctx->Dp, ctx->d_hist));
+    HIPCHK(launch_byte_hist(ctx->stream, ctx->ts.d_codes, ctx->ts.N, ctx->ts.D, ctx->ts.Dp, ctx->d_hist));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return QVQ_OK;
 }
@@ -2327,8 +2237,8 @@ qvq_status check_image_args(qvq_ctx *ctx, uint32_t n_images, uint32_t xSize, uin
 qvq_status tile_into(qvq_ctx *ctx, const uint8_t *d_rgb, uint32_t n_images, uint32_t xSize, uint32_t ySize,
                      uint32_t bw, uint32_t bh) {
     ctx->col_blocks = (ySize + bh - 1) / bh;   // the pruned wide search stacks its chunks across columns
-    HIPCHK(launch_tile(ctx->stream, d_rgb, ctx->d_codes, n_images, xSize, ySize, bw, bh, ctx->D, ctx->Dp,
-                       ctx->terms.pad_code));
+    HIPCHK(launch_tile(ctx->stream, d_rgb, ctx->ts.d_codes, n_images, xSize, ySize, bw, bh, ctx->ts.D, ctx->ts.Dp,
+                       ctx->ts.terms.pad_code));
     return QVQ_OK;
 }
 
@@ -2362,51 +2272,43 @@ QVQ_API qvq_status qvq_create(int hip_device, qvq_ctx **out) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n == 0) return fail(nullptr, QVQ_EDEVICE, "no HIP device");
     if (hip_device < 0 || hip_device >= n) return fail(nullptr, QVQ_EINVAL, "bad device index");
-    qvq_ctx *ctx = new qvq_ctx();
+    std::unique_ptr<qvq_ctx> owner(new qvq_ctx());   // an early return destroys what was made
+    qvq_ctx *ctx = owner.get();
     ctx->dev = hip_device;
     if (const char *t = std::getenv("QVQ_TIMING")) ctx->timing_level = std::atoi(t);   // A/B: the default per-level events
     std::memset(&ctx->tm, 0, sizeof(ctx->tm));
-    auto bail = [&](hipError_t e, const char *what) {
-        g_static_err = std::string(what) + ": " + hipGetErrorString(e);
-        qvq_destroy(ctx);
-        return QVQ_EDEVICE;
-    };
-    hipError_t e;
-    if ((e = hipSetDevice(hip_device)) != hipSuccess) return bail(e, "hipSetDevice");
+    // (errors go to the thread's static string: the caller gets no context to ask)
+#define CREATECHK(expr, what)                                                                          \
+    do {                                                                                               \
+        const hipError_t e_ = (expr);                                                                  \
+        if (e_ != hipSuccess) return fail(nullptr, QVQ_EDEVICE, std::string(what) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+    CREATECHK(hipSetDevice(hip_device), "hipSetDevice");
     hipDeviceProp_t prop;
-    if ((e = hipGetDeviceProperties(&prop, hip_device)) != hipSuccess) return bail(e, "hipGetDeviceProperties");
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-        g_static_err = std::string("libqvq is built for gfx950, device is ") + prop.gcnArchName;
-        qvq_destroy(ctx);
-        return QVQ_EDEVICE;
-    }
+    CREATECHK(hipGetDeviceProperties(&prop, hip_device), "hipGetDeviceProperties");
+    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        return fail(nullptr, QVQ_EDEVICE, std::string("libqvq is built for gfx950, device is ") + prop.gcnArchName);
     ctx->num_cu = prop.multiProcessorCount;
     ctx->G = (uint32_t)ctx->num_cu;   // one search/update workgroup (and slab) per CU
-    if ((e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking)) != hipSuccess) return bail(e, "stream");
-    if ((e = hipMalloc(&ctx->d_lut32, 256 * 4)) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = hipMalloc(&ctx->d_w, 256 * 4)) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = hipMalloc(&ctx->d_lut64, 256 * 8)) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = hipMalloc(&ctx->d_plut, 256 * 8)) != hipSuccess) return bail(e, "hipMalloc");
-    // mapped: [0, 64) the codebook ready number, [64, 1024) a quantize's small results
-    if ((e = hipHostMalloc(&ctx->h_ready, 1024, hipHostMallocMapped | hipHostMallocCoherent)) != hipSuccess)
-        return bail(e, "hipHostMalloc");
+    CREATECHK(hipStreamCreateWithFlags(ctx->stream.put(), hipStreamNonBlocking), "stream");
+    CREATECHK(ctx->d_lut32.alloc(256), "hipMalloc");
+    CREATECHK(ctx->d_w.alloc(256), "hipMalloc");
+    CREATECHK(ctx->d_lut64.alloc(256), "hipMalloc");
+    CREATECHK(ctx->d_plut.alloc(256), "hipMalloc");
+    CREATECHK(ctx->h_ready.alloc(1024 / 8), "hipHostMalloc");
     *ctx->h_ready = 0;
-    if ((e = hipHostGetDevicePointer((void **)&ctx->dh_ready, ctx->h_ready, 0)) != hipSuccess)
-        return bail(e, "hipHostGetDevicePointer");
-    if ((e = hipMalloc(&ctx->d_counters, N_COUNTERS_ALLOC * sizeof(unsigned))) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = hipMemset(ctx->d_counters, 0, N_COUNTERS_ALLOC * sizeof(unsigned))) != hipSuccess) return bail(e, "hipMemset");
-    if ((e = hipMalloc(&ctx->d_hist, 512 * 8)) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = hipMalloc(&ctx->d_decode_stat, 16)) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = hipHostMalloc(&ctx->h_decode_stat, 16, hipHostMallocDefault)) != hipSuccess) return bail(e, "hipHostMalloc");
-    if ((e = hipMalloc(&ctx->d_dist_part, 8192 * 8)) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = hipMalloc(&ctx->d_mean, MEAN_COPIES * (2 * 64 + 1) * 8)) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = hipMemset(ctx->d_mean, 0, MEAN_COPIES * (2 * 64 + 1) * 8)) != hipSuccess) return bail(e, "hipMemset");
-    for (int l = 0; l < 32; l++)
-        for (int j = 0; j < 4; j++)
-            if ((e = hipEventCreate(&ctx->ev[l][j])) != hipSuccess) return bail(e, "hipEventCreate");
-    if ((e = hipEventCreate(&ctx->ev_end)) != hipSuccess) return bail(e, "hipEventCreate");
-    if ((e = hipEventCreateWithFlags(&ctx->ev_sync, hipEventDisableTiming)) != hipSuccess)
-        return bail(e, "hipEventCreate");
+    CREATECHK(ctx->d_counters.alloc(N_COUNTERS_ALLOC), "hipMalloc");
+    CREATECHK(hipMemset(ctx->d_counters, 0, ctx->d_counters.bytes()), "hipMemset");
+    CREATECHK(ctx->d_hist.alloc(512), "hipMalloc");
+    CREATECHK(ctx->d_decode_stat.alloc(2), "hipMalloc");
+    CREATECHK(ctx->h_decode_stat.alloc(2), "hipHostMalloc");
+    CREATECHK(ctx->d_dist_part.alloc(8192), "hipMalloc");
+    CREATECHK(ctx->d_mean.alloc(MEAN_COPIES * (2 * 64 + 1)), "hipMalloc");
+    CREATECHK(hipMemset(ctx->d_mean, 0, ctx->d_mean.bytes()), "hipMemset");
+    for (auto &level : ctx->ev)
+        for (Event &ev : level) CREATECHK(hipEventCreate(ev.put()), "hipEventCreate");
+    CREATECHK(hipEventCreate(ctx->ev_end.put()), "hipEventCreate");
+    CREATECHK(hipEventCreateWithFlags(ctx->ev_sync.put(), hipEventDisableTiming), "hipEventCreate");
     {
         std::vector<double> tab(512);
         for (int cs : {QVQ_CS_NORMAL, QVQ_CS_SCALED}) {
@@ -2414,21 +2316,20 @@ QVQ_API qvq_status qvq_create(int hip_device, qvq_ctx **out) {
             make_terms(cs, t);
             std::memcpy(&tab[256 * cs], t.v64, sizeof(t.v64));
         }
-        if ((e = hipMalloc(&ctx->d_ing_tab, 512 * 8)) != hipSuccess) return bail(e, "hipMalloc");
-        if ((e = hipMemcpy(ctx->d_ing_tab, tab.data(), 512 * 8, hipMemcpyHostToDevice)) != hipSuccess)
-            return bail(e, "hipMemcpy");
-        if ((e = hipMalloc(&ctx->d_ing_verdict, sizeof(unsigned))) != hipSuccess) return bail(e, "hipMalloc");
-        if ((e = hipHostMalloc(&ctx->h_ing_verdict, sizeof(unsigned), hipHostMallocDefault)) != hipSuccess)
-            return bail(e, "hipHostMalloc");
-        for (hipEvent_t &ev : ctx->ev_ing)
-            if ((e = hipEventCreate(&ev)) != hipSuccess) return bail(e, "hipEventCreate");
+        CREATECHK(ctx->d_ing_tab.alloc(512), "hipMalloc");
+        CREATECHK(hipMemcpy(ctx->d_ing_tab, tab.data(), 512 * 8, hipMemcpyHostToDevice), "hipMemcpy");
+        CREATECHK(ctx->d_ing_verdict.alloc(1), "hipMalloc");
+        CREATECHK(ctx->h_ing_verdict.alloc(1), "hipHostMalloc");
+        for (Event &ev : ctx->ev_ing) CREATECHK(hipEventCreate(ev.put()), "hipEventCreate");
     }
+#undef CREATECHK
     if (const char *t = std::getenv("QVQ_TIMEOUT_S")) ctx->timeout_s = std::max(0.001, std::atof(t));
-    ctx->ev_ready = true;
-    *out = ctx;
+    *out = owner.release();
     return QVQ_OK;
 }
 
+// The ordered part of the teardown: no thread or queued work may outlive the buffers, which the
+// context's members then release (streams last: they are declared first).
 QVQ_API void qvq_destroy(qvq_ctx *ctx) {
     if (!ctx) return;
     join_tree_job(ctx, true);
@@ -2453,56 +2354,14 @@ QVQ_API void qvq_destroy(qvq_ctx *ctx) {
     }
     (void)hipSetDevice(ctx->dev);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->kstream) {
-        (void)hipStreamSynchronize(ctx->kstream);
-        (void)hipStreamDestroy(ctx->kstream);
-    }
-    if (ctx->ev_kcb) (void)hipEventDestroy(ctx->ev_kcb);
-    if (ctx->ev_kdb) (void)hipEventDestroy(ctx->ev_kdb);
+    if (ctx->kstream) (void)hipStreamSynchronize(ctx->kstream);
     if (ctx->comm) ncclCommDestroy(ctx->comm);
-    free_training(ctx);
-    free_levels(ctx);
-    dfree(ctx->d_lut32);
-    dfree(ctx->d_w);
-    dfree(ctx->d_lut64);
-    dfree(ctx->d_plut);
-    dfree(ctx->d_counters);
-    dfree(ctx->d_hist);
-    if (ctx->h_ready) (void)hipHostFree(ctx->h_ready);
-    dfree(ctx->d_dist_part);
-    dfree(ctx->d_mean);
-    dfree(ctx->d_scatter);
-    dfree(ctx->d_decode);
-    dfree(ctx->d_reseed);
-    dfree(ctx->d_raster);
-    dfree(ctx->d_decode_stat);
-    if (ctx->h_decode_stat) (void)hipHostFree(ctx->h_decode_stat);
-    if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
-    if (ctx->h_ar_stage) (void)hipHostFree(ctx->h_ar_stage);
-    dfree(ctx->d_vote);
-    if (ctx->h_vote) (void)hipHostFree(ctx->h_vote);
-    if (ctx->ev_ready)
-        for (int l = 0; l < 32; l++)
-            for (int j = 0; j < 4; j++) (void)hipEventDestroy(ctx->ev[l][j]);
-    if (ctx->ev_end) (void)hipEventDestroy(ctx->ev_end);
-    if (ctx->ev_sync) (void)hipEventDestroy(ctx->ev_sync);
-    dfree(ctx->d_ing_tab);
-    dfree(ctx->d_ing_verdict);
-    if (ctx->h_ing_verdict) (void)hipHostFree(ctx->h_ing_verdict);
-    for (hipEvent_t ev : ctx->ev_ing)
-        if (ev) (void)hipEventDestroy(ev);
-    for (auto &v : ctx->ver)
-        if (v.ev) (void)hipEventDestroy(v.ev);
-    for (uint8_t *h : ctx->h_tx)
-        if (h) (void)hipHostFree(h);
-    if (ctx->vstream) (void)hipStreamDestroy(ctx->vstream);
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
 
-QVQ_API uint64_t qvq_num_vectors(const qvq_ctx *ctx) { return ctx ? ctx->N : 0; }
-QVQ_API uint32_t qvq_dim(const qvq_ctx *ctx) { return ctx ? ctx->D : 0; }
-QVQ_API const uint32_t *qvq_assign_device(const qvq_ctx *ctx) { return ctx ? ctx->d_A : nullptr; }
+QVQ_API uint64_t qvq_num_vectors(const qvq_ctx *ctx) { return ctx ? ctx->ts.N : 0; }
+QVQ_API uint32_t qvq_dim(const qvq_ctx *ctx) { return ctx ? ctx->ts.D : 0; }
+QVQ_API const uint32_t *qvq_assign_device(const qvq_ctx *ctx) { return ctx ? ctx->ts.d_A : nullptr; }
 
 QVQ_API qvq_status qvq_set_images_device(qvq_ctx *ctx, const void *d_rgb, uint32_t n_images, uint32_t xSize,
                                          uint32_t ySize, uint32_t bw, uint32_t bh, int colorspace) {
@@ -2532,12 +2391,7 @@ QVQ_API qvq_status qvq_set_images(qvq_ctx *ctx, const uint8_t *rgb, uint32_t n_i
     if (colorspace == QVQ_CS_CIE1931 && (st = check_cie_raster(ctx, N, bw, bh)) != QVQ_OK) return st;
     HIPCHK(hipSetDevice(ctx->dev));
     const uint64_t bytes = (uint64_t)xSize * ySize * 3 * n_images;
-    if (ctx->raster_bytes < bytes) {   // kept across calls (repeated compresses)
-        dfree(ctx->d_raster);
-        ctx->raster_bytes = 0;
-        HIPCHK(hipMalloc(&ctx->d_raster, bytes));
-        ctx->raster_bytes = bytes;
-    }
+    HIPCHK(ctx->d_raster.ensure(bytes));   // kept across calls (repeated compresses)
     const hipError_t e = host_copy(ctx, ctx->d_raster, rgb, bytes, hipMemcpyHostToDevice);
     if (e != hipSuccess) return fail(ctx, QVQ_EDEVICE, std::string("raster upload: ") + hipGetErrorString(e));
     if (colorspace == QVQ_CS_CIE1931)
@@ -2560,8 +2414,8 @@ QVQ_API qvq_status qvq_set_synthetic(qvq_ctx *ctx, uint32_t S, uint64_t seed0, u
     if (cie && (st = check_cie_raster(ctx, N, bw, bh)) != QVQ_OK) return st;
     HIPCHK(hipSetDevice(ctx->dev));
     const uint64_t npix = (uint64_t)S * S * n_images;
-    uint8_t *d_rgb = nullptr;
-    HIPCHK(hipMalloc(&d_rgb, npix * 3));
+    DevBuf<uint8_t> d_rgb;   // (freed after the synchronize below)
+    HIPCHK(d_rgb.alloc(npix * 3));
     st = QVQ_OK;
     const hipError_t e = launch_gen(ctx->stream, d_rgb, S, seed0, npix);
     if (e != hipSuccess) st = fail(ctx, QVQ_EDEVICE, std::string("gen_kernel: ") + hipGetErrorString(e));
@@ -2570,7 +2424,6 @@ QVQ_API qvq_status qvq_set_synthetic(qvq_ctx *ctx, uint32_t S, uint64_t seed0, u
     if (st == QVQ_OK && !cie) st = tile_into(ctx, d_rgb, n_images, S, S, bw, bh);
     if (st == QVQ_OK && !cie) st = compute_xsq(ctx);
     (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_rgb);
     return st;
 }
 
@@ -2634,49 +2487,38 @@ static qvq_status check_exact_set(qvq_ctx *ctx, uint64_t n, bool forced, bool fi
     return QVQ_OK;
 }
 
-// A transient device buffer, freed on every way out unless it was handed on.
-struct DevRows {
-    double *p = nullptr;
-    ~DevRows() {
-        if (p) (void)hipFree(p);
-    }
-};
-
-// The exact-mode set of n rows of dim components: *adopt (an upload of the engine's own) taken over
+// The exact-mode set of n rows of dim components: adopt (an upload of the engine's own) taken over
 // as d_X64 as it is, or a fresh d_X64 that fill writes with work on the context's stream (a copy of
 // the caller's rows, or the launch that produces them).  raster_cs: the colour space of the raster
 // the rows come from, -1 for fp64 rows (qvq_get_training_info).  Returns with the stream drained.
-static qvq_status install_exact(qvq_ctx *ctx, uint64_t n, uint32_t dim, int raster_cs, double **adopt,
+static qvq_status install_exact(qvq_ctx *ctx, uint64_t n, uint32_t dim, int raster_cs, DevBuf<double> *adopt,
                                 const std::function<hipError_t(double *)> &fill) {
     ctx->rf = qvq_ctx::RefineState();
-    free_training(ctx);
-    free_levels(ctx);
-    ctx->N = n;
-    ctx->D = dim;
-    ctx->Dp = (dim + 3) & ~3u;
-    ctx->cs = -1;
-    ctx->exact = true;
-    ctx->exact_cs = raster_cs;
-    if (adopt) {
-        ctx->d_X64 = *adopt;
-        *adopt = nullptr;
-    } else {
-        HIPCHK(hipMalloc(&ctx->d_X64, n * dim * 8));
-    }
-    HIPCHK(hipMalloc(&ctx->d_A, n * 4));
-    HIPCHK(hipMalloc(&ctx->d_ties, n * 4));
-    HIPCHK(hipMalloc(&ctx->d_ex_keys, n * 4));
-    HIPCHK(hipMalloc(&ctx->d_ex_iota, n * 4));
-    HIPCHK(hipMalloc(&ctx->d_ex_order, n * 4));
-    ctx->ex_temp_bytes = exact_sort_temp_bytes(n);
-    HIPCHK(hipMalloc(&ctx->d_ex_temp, std::max<size_t>(ctx->ex_temp_bytes, 16)));
-    if (!adopt) HIPCHK(fill(ctx->d_X64));
-    HIPCHK(launch_exact_iota(ctx->stream, ctx->d_ex_iota, n));
+    drop_training(ctx);   // before the new set's allocations: peak memory is one set
+    qvq_ctx::Training ts;   // moved into the context when it is complete
+    ts.N = n;
+    ts.D = dim;
+    ts.Dp = (dim + 3) & ~3u;
+    ts.exact = true;
+    ts.exact_cs = raster_cs;
+    if (adopt) ts.ex.d_X64 = std::move(*adopt);
+    else HIPCHK(ts.ex.d_X64.alloc(n * dim));
+    qvq_status st = ensure_apool(ctx, ts, 1);
+    if (st != QVQ_OK) return st;
+    HIPCHK(ts.d_ties.alloc(n));
+    HIPCHK(ts.ex.d_keys.alloc(n));
+    HIPCHK(ts.ex.d_iota.alloc(n));
+    HIPCHK(ts.ex.d_order.alloc(n));
+    ts.ex.temp_bytes = exact_sort_temp_bytes(n);
+    HIPCHK(ts.ex.d_temp.alloc(std::max<size_t>(ts.ex.temp_bytes, 16)));
+    if (!adopt) HIPCHK(fill(ts.ex.d_X64));
+    HIPCHK(launch_exact_iota(ctx->stream, ts.ex.d_iota, n));
     HIPCHK(hipStreamSynchronize(ctx->stream));
+    ctx->ts = std::move(ts);
     return QVQ_OK;
 }
 // ... from src's rows: on the host, or on the device where the context's stream may read them
-static qvq_status install_exact_copy(qvq_ctx *ctx, const double *src, hipMemcpyKind kind, double **adopt, uint64_t n,
+static qvq_status install_exact_copy(qvq_ctx *ctx, const double *src, hipMemcpyKind kind, DevBuf<double> *adopt, uint64_t n,
                                      uint32_t dim) {
     return install_exact(ctx, n, dim, -1, adopt, [&](double *dst) {
         return hipMemcpyAsync(dst, src, n * dim * 8, kind, ctx->stream);
@@ -2705,7 +2547,7 @@ static qvq_status install_cie_raster(qvq_ctx *ctx, const uint8_t *d_rgb, uint32_
 // pack under the space found or install the rows as the exact-mode set.  adopt: dX is *adopt, the
 // engine's own upload, which exact mode keeps.  Returns with the stream drained.
 static qvq_status ingest_rows(qvq_ctx *ctx, const double *dX, uint64_t n, uint32_t dim, bool force_exact,
-                              double **adopt) {
+                              DevBuf<double> *adopt) {
     const bool timed = ctx->timing_level == -3;   // events around the two passes (qvq_get_ingest_ms)
     ctx->ingest_ms[0] = ctx->ingest_ms[1] = 0;
     if (timed) HIPCHK(hipEventRecord(ctx->ev_ing[0], ctx->stream));
@@ -2726,7 +2568,7 @@ static qvq_status ingest_rows(qvq_ctx *ctx, const double *dX, uint64_t n, uint32
     // (the same shape again keeps every buffer; the pack below refills d_codes either way)
     if ((st = alloc_training(ctx, n, dim, cs)) != QVQ_OK) return st;
     if (timed) HIPCHK(hipEventRecord(ctx->ev_ing[1], ctx->stream));
-    HIPCHK(launch_ingest_pack(ctx->stream, dX, n, dim, (uint32_t)cs, ctx->d_ing_tab, ctx->d_codes));
+    HIPCHK(launch_ingest_pack(ctx->stream, dX, n, dim, (uint32_t)cs, ctx->d_ing_tab, ctx->ts.d_codes));
     if (timed) HIPCHK(hipEventRecord(ctx->ev_ing[2], ctx->stream));
     if ((st = compute_xsq(ctx)) != QVQ_OK) return st;
     if (timed && hipEventElapsedTime(&ms, ctx->ev_ing[1], ctx->ev_ing[2]) == hipSuccess) ctx->ingest_ms[1] = ms;
@@ -2753,7 +2595,7 @@ static qvq_status ingest_host_rule(qvq_ctx *ctx, const double *X, uint64_t n, ui
     }
     ctx->col_blocks = 0;
     if ((st = alloc_training(ctx, n, dim, cs)) != QVQ_OK) return st;
-    HIPCHK(hipMemcpy(ctx->d_codes, codes.data(), codes.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(ctx->ts.d_codes, codes.data(), codes.size(), hipMemcpyHostToDevice));
     return compute_xsq(ctx);
 }
 
@@ -2764,14 +2606,13 @@ static qvq_status set_vectors_host(qvq_ctx *ctx, const double *X, uint64_t n, ui
     if (st != QVQ_OK) return st;
     HIPCHK(hipSetDevice(ctx->dev));
     // one upload into a transient buffer: the pass reads it, exact mode keeps it as d_X64
-    DevRows rows;
-    if (hipMalloc(&rows.p, n * dim * 8) != hipSuccess) {
+    DevBuf<double> rows;
+    if (rows.alloc(n * dim) != hipSuccess) {
         (void)hipGetLastError();
-        rows.p = nullptr;
         return ingest_host_rule(ctx, X, n, dim, force_exact);
     }
-    HIPCHK(hipMemcpyAsync(rows.p, X, n * dim * 8, hipMemcpyHostToDevice, ctx->stream));
-    return ingest_rows(ctx, rows.p, n, dim, force_exact, &rows.p);
+    HIPCHK(hipMemcpyAsync(rows, X, n * dim * 8, hipMemcpyHostToDevice, ctx->stream));
+    return ingest_rows(ctx, rows, n, dim, force_exact, &rows);
 }
 
 QVQ_API qvq_status qvq_set_vectors(qvq_ctx *ctx, const double *X, uint64_t n, uint32_t dim) {
@@ -2806,10 +2647,10 @@ QVQ_API qvq_status qvq_set_vectors_device(qvq_ctx *ctx, const void *d_X, uint64_
 
 QVQ_API qvq_status qvq_get_training_info(const qvq_ctx *ctx, qvq_training_info *out) {
     if (!ctx || !out) return QVQ_EINVAL;
-    out->mode = ctx->exact ? 2u : ctx->d_codes ? 1u : 0u;
-    out->colorspace = out->mode == 1 ? ctx->cs : out->mode == 2 ? ctx->exact_cs : -1;
-    out->n = ctx->N;
-    out->dim = ctx->D;
+    out->mode = ctx->ts.exact ? 2u : ctx->ts.d_codes ? 1u : 0u;
+    out->colorspace = out->mode == 1 ? ctx->ts.cs : out->mode == 2 ? ctx->ts.exact_cs : -1;
+    out->n = ctx->ts.N;
+    out->dim = ctx->ts.D;
     return QVQ_OK;
 }
 
@@ -2820,32 +2661,27 @@ QVQ_API qvq_status qvq_get_training_info(const qvq_ctx *ctx, qvq_training_info *
 QVQ_API qvq_status qvq_get_vectors(qvq_ctx *ctx, uint64_t row0, uint64_t nrows, double *out) {
     if (!ctx) return QVQ_EINVAL;
     GUARD(ctx);
-    if (ctx->N == 0) return fail(ctx, QVQ_ESTATE, "no training set");
+    if (ctx->ts.N == 0) return fail(ctx, QVQ_ESTATE, "no training set");
     if (!out || nrows == 0) return fail(ctx, QVQ_EINVAL, "empty read-back");
-    if (row0 >= ctx->N || nrows > ctx->N - row0) return fail(ctx, QVQ_EINVAL, "rows outside the training set");
+    if (row0 >= ctx->ts.N || nrows > ctx->ts.N - row0) return fail(ctx, QVQ_EINVAL, "rows outside the training set");
     HIPCHK(hipSetDevice(ctx->dev));
     constexpr uint64_t GET_PIECE = 64ull << 20;
-    const uint64_t row_bytes = (uint64_t)ctx->D * 8;
+    const uint64_t row_bytes = (uint64_t)ctx->ts.D * 8;
     const uint64_t piece_rows = std::min<uint64_t>(nrows, std::max<uint64_t>(1, GET_PIECE / row_bytes));
-    qvq_status st = ensure_pinned(ctx, ctx->h_stage, ctx->stage_bytes, piece_rows * row_bytes);
-    if (st != QVQ_OK) return st;
-    if (!ctx->exact && ctx->decode_bytes < piece_rows * row_bytes) {
-        dfree(ctx->d_decode);
-        ctx->decode_bytes = 0;
-        HIPCHK(hipMalloc(&ctx->d_decode, piece_rows * row_bytes));
-        ctx->decode_bytes = piece_rows * row_bytes;
-    }
+    HIPCHK(ctx->h_stage.ensure(piece_rows * row_bytes));
+    qvq_status st;
+    if (!ctx->ts.exact) HIPCHK(ctx->d_decode.ensure(piece_rows * row_bytes));
     for (uint64_t r = 0; r < nrows; r += piece_rows) {
         const uint64_t nr = std::min(piece_rows, nrows - r);
-        const double *src = ctx->d_X64 + (row0 + r) * ctx->D;
-        if (!ctx->exact) {
-            double *d = reinterpret_cast<double *>(ctx->d_decode);
-            HIPCHK(launch_rows_f64(ctx->stream, ctx->d_codes, ctx->Dp, ctx->D, row0 + r, nr, ctx->d_lut64, d));
+        const double *src = ctx->ts.ex.d_X64 + (row0 + r) * ctx->ts.D;
+        if (!ctx->ts.exact) {
+            double *d = reinterpret_cast<double *>(ctx->d_decode.get());
+            HIPCHK(launch_rows_f64(ctx->stream, ctx->ts.d_codes, ctx->ts.Dp, ctx->ts.D, row0 + r, nr, ctx->d_lut64, d));
             src = d;
         }
         HIPCHK(hipMemcpyAsync(ctx->h_stage, src, nr * row_bytes, hipMemcpyDeviceToHost, ctx->stream));
         if ((st = wait_stream(ctx)) != QVQ_OK) return st;
-        std::memcpy(out + r * ctx->D, ctx->h_stage, nr * row_bytes);
+        std::memcpy(out + r * ctx->ts.D, ctx->h_stage, nr * row_bytes);
     }
     return QVQ_OK;
 }
@@ -2867,43 +2703,36 @@ qvq_status exact_single_rank(qvq_ctx *ctx) {
 }
 
 qvq_status exact_koff(qvq_ctx *ctx, uint32_t K) {
-    if (ctx->ex_kcap >= K + 1) return QVQ_OK;
-    dfree(ctx->d_ex_koff);
-    HIPCHK(hipMalloc(&ctx->d_ex_koff, ((size_t)K + 1) * 4));
-    ctx->ex_kcap = K + 1;
+    HIPCHK(ctx->ts.ex.d_koff.ensure((size_t)K + 1));
     return QVQ_OK;
 }
 
 // Assignment of every row against the K code vectors at d_C64_split (host copy hC): the
 // fp64 argmin, exact ties answered by the host kd-tree over hC.  Returns the tie count.
 qvq_status exact_assign(qvq_ctx *ctx, const double *hC, uint32_t K, unsigned &nties) {
-    const uint32_t D = ctx->D;
+    const uint32_t D = ctx->ts.D;
     qvq_status st;
     unsigned *cnt = ctx->d_counters + 1;
     HIPCHK(hipMemsetAsync(cnt, 0, sizeof(unsigned), ctx->stream));
-    HIPCHK(launch_exact_assign(ctx->stream, ctx->d_X64, ctx->N, D, ctx->d_C64_split, K, 1e-12, ctx->d_A, ctx->d_ties,
+    HIPCHK(launch_exact_assign(ctx->stream, ctx->ts.ex.d_X64, ctx->ts.N, D, ctx->lv.d_C64_split, K, 1e-12, ctx->ts.d_A, ctx->ts.d_ties,
                                cnt));
     HIPCHK(hipMemcpyAsync(&nties, cnt, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
     if ((st = wait_stream(ctx)) != QVQ_OK) return st;
     if (nties == 0) return QVQ_OK;
     const uint64_t need = (uint64_t)nties * (8 + 8ull * D);
-    if (ctx->scatter_bytes < need) {
-        dfree(ctx->d_scatter);
-        HIPCHK(hipMalloc(&ctx->d_scatter, need));
-        ctx->scatter_bytes = need;
-    }
+    HIPCHK(ctx->d_scatter.ensure(need / 4));
     uint32_t *d_vals = ctx->d_scatter;
     double *d_rows = reinterpret_cast<double *>(ctx->d_scatter + 2 * (uint64_t)nties);
     std::vector<uint32_t> rows(nties), vals(nties);
     std::vector<double> q((size_t)nties * D);
-    HIPCHK(launch_exact_gather(ctx->stream, ctx->d_X64, D, ctx->d_ties, nties, d_rows));
-    HIPCHK(hipMemcpyAsync(rows.data(), ctx->d_ties, nties * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(launch_exact_gather(ctx->stream, ctx->ts.ex.d_X64, D, ctx->ts.d_ties, nties, d_rows));
+    HIPCHK(hipMemcpyAsync(rows.data(), ctx->ts.d_ties, nties * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(q.data(), d_rows, q.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
     if ((st = wait_stream(ctx)) != QVQ_OK) return st;
     RefKDTree tree(hC, K, (int)D);
     for (unsigned i = 0; i < nties; i++) vals[i] = tree.nearest(q.data() + (size_t)i * D);
     HIPCHK(hipMemcpyAsync(d_vals, vals.data(), nties * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(launch_exact_fix(ctx->stream, ctx->d_A, ctx->d_ties, d_vals, nties));
+    HIPCHK(launch_exact_fix(ctx->stream, ctx->ts.d_A, ctx->ts.d_ties, d_vals, nties));
     if ((st = wait_stream(ctx)) != QVQ_OK) return st;   // the host vectors must outlive the copies
     return QVQ_OK;
 }
@@ -2912,9 +2741,9 @@ qvq_status exact_assign(qvq_ctx *ctx, const double *hC, uint32_t K, unsigned &nt
 qvq_status exact_centroids(qvq_ctx *ctx, bool mean, uint32_t K, uint64_t *cnt) {
     qvq_status st = exact_koff(ctx, K);
     if (st != QVQ_OK) return st;
-    HIPCHK(launch_exact_centroids(ctx->stream, ctx->d_X64, ctx->N, ctx->D, mean ? nullptr : ctx->d_A, K,
-                                  ctx->d_ex_keys, ctx->d_ex_iota, ctx->d_ex_order, ctx->d_ex_koff, ctx->d_ex_temp,
-                                  ctx->ex_temp_bytes, ctx->d_C64_cent, cnt));
+    HIPCHK(launch_exact_centroids(ctx->stream, ctx->ts.ex.d_X64, ctx->ts.N, ctx->ts.D, mean ? nullptr : ctx->ts.d_A, K,
+                                  ctx->ts.ex.d_keys, ctx->ts.ex.d_iota, ctx->ts.ex.d_order, ctx->ts.ex.d_koff, ctx->ts.ex.d_temp,
+                                  ctx->ts.ex.temp_bytes, ctx->lv.d_C64_cent, cnt));
     return QVQ_OK;
 }
 
@@ -2922,16 +2751,16 @@ qvq_status lbg_exact(qvq_ctx *ctx, uint32_t bits, double *codebook, uint32_t *as
     qvq_status st = exact_single_rank(ctx);
     if (st != QVQ_OK) return st;
     const auto t0 = std::chrono::steady_clock::now();
-    const uint32_t Kmax = 1u << bits, D = ctx->D;
+    const uint32_t Kmax = 1u << bits, D = ctx->ts.D;
     if ((st = ensure_levels(ctx, std::max<uint32_t>(Kmax, 2))) != QVQ_OK) return st;
     std::memset(&ctx->tm, 0, sizeof(ctx->tm));
     ctx->tm.levels = (int)bits;
     // codeVectors[0] = trainingSetSum() / N (src/Quantizer.cpp:129-130)
     std::vector<double> hC((size_t)Kmax * D), hS((size_t)Kmax * D);
     if ((st = exact_centroids(ctx, true, 1, nullptr)) != QVQ_OK) return st;
-    HIPCHK(hipMemcpyAsync(hC.data(), ctx->d_C64_cent, (size_t)D * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(hC.data(), ctx->lv.d_C64_cent, (size_t)D * 8, hipMemcpyDeviceToHost, ctx->stream));
     if ((st = wait_stream(ctx)) != QVQ_OK) return st;
-    if (bits == 0) HIPCHK(hipMemsetAsync(ctx->d_A, 0, ctx->N * 4, ctx->stream));
+    if (bits == 0) HIPCHK(hipMemsetAsync(ctx->ts.d_A, 0, ctx->ts.N * 4, ctx->stream));
     for (uint32_t lvl = 1; lvl <= bits; lvl++) {
         const uint32_t K = 1u << lvl, H = K / 2;
         // concat(C, C), then the halves scaled by (1 + 0.2) and (1 - 0.2) (src/Quantizer.cpp:134-138)
@@ -2939,14 +2768,14 @@ qvq_status lbg_exact(qvq_ctx *ctx, uint32_t bits, double *codebook, uint32_t *as
             hS[i] = hC[i] * (double)(1 + 0.2);
             hS[(size_t)H * D + i] = hC[i] * (double)(1 - 0.2);
         }
-        HIPCHK(hipMemcpyAsync(ctx->d_C64_split, hS.data(), (size_t)K * D * 8, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(ctx->lv.d_C64_split, hS.data(), (size_t)K * D * 8, hipMemcpyHostToDevice, ctx->stream));
         unsigned nt = 0;
         const auto ta = std::chrono::steady_clock::now();
         if ((st = exact_assign(ctx, hS.data(), K, nt)) != QVQ_OK) return st;   // synchronous
         const auto tb = std::chrono::steady_clock::now();
         ctx->tm.host_ties[lvl - 1] = nt;
         if ((st = exact_centroids(ctx, false, K, nullptr)) != QVQ_OK) return st;
-        HIPCHK(hipMemcpyAsync(hC.data(), ctx->d_C64_cent, (size_t)K * D * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(hC.data(), ctx->lv.d_C64_cent, (size_t)K * D * 8, hipMemcpyDeviceToHost, ctx->stream));
         if ((st = wait_stream(ctx)) != QVQ_OK) return st;
         // wall times: assign (search + ties) and update (sort + Kahan chains + codebook copy)
         ctx->tm.assign_ms[lvl - 1] = std::chrono::duration<float, std::milli>(tb - ta).count();
@@ -2955,16 +2784,16 @@ qvq_status lbg_exact(qvq_ctx *ctx, uint32_t bits, double *codebook, uint32_t *as
     }
     // updateDistortion after the last fix (src/Quantizer.cpp:9-22)
     double dist = 0;
-    HIPCHK(launch_exact_distortion(ctx->stream, ctx->d_X64, ctx->N, D, ctx->d_C64_cent, ctx->d_A, ctx->d_dist_part,
+    HIPCHK(launch_exact_distortion(ctx->stream, ctx->ts.ex.d_X64, ctx->ts.N, D, ctx->lv.d_C64_cent, ctx->ts.d_A, ctx->d_dist_part,
                                    ctx->d_dist_part + 4096));
     // results reach the caller only after the bounded wait succeeds (staged in pinned memory)
-    if ((st = ensure_pinned(ctx, ctx->h_stage, ctx->stage_bytes, 8 + (assign ? ctx->N * 4 : 0))) != QVQ_OK) return st;
+    HIPCHK(ctx->h_stage.ensure(8 + (assign ? ctx->ts.N * 4 : 0)));
     uint8_t *stage = static_cast<uint8_t *>(ctx->h_stage);
     HIPCHK(hipMemcpyAsync(stage, ctx->d_dist_part + 4096, 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (assign) HIPCHK(hipMemcpyAsync(stage + 8, ctx->d_A, ctx->N * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (assign) HIPCHK(hipMemcpyAsync(stage + 8, ctx->ts.d_A, ctx->ts.N * 4, hipMemcpyDeviceToHost, ctx->stream));
     if ((st = wait_stream(ctx)) != QVQ_OK) return st;
     std::memcpy(&dist, stage, 8);
-    if (assign) std::memcpy(assign, stage + 8, ctx->N * 4);
+    if (assign) std::memcpy(assign, stage + 8, ctx->ts.N * 4);
     if (codebook) std::memcpy(codebook, hC.data(), (size_t)Kmax * D * 8);
     if (distortion) *distortion = dist;
     ctx->tm.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -3044,11 +2873,11 @@ QVQ_API qvq_status qvq_lbg(qvq_ctx *ctx, uint32_t bits, double eps, double *code
     (void)eps;   // cannot change the outputs: one Lloyd step per level
     if (!ctx) return QVQ_EINVAL;
     GUARD(ctx);
-    if (ctx->N == 0) return fail(ctx, QVQ_ESTATE, "no training set");
+    if (ctx->ts.N == 0) return fail(ctx, QVQ_ESTATE, "no training set");
     if (bits > 20) return fail(ctx, QVQ_EINVAL, "bits must be <= 20");
     ctx->rf.valid = false;
     HIPCHK(hipSetDevice(ctx->dev));
-    if (ctx->exact) return lbg_exact(ctx, bits, codebook, assign, distortion);
+    if (ctx->ts.exact) return lbg_exact(ctx, bits, codebook, assign, distortion);
     const HostPlaceGuard place(ctx);
     const auto t0 = std::chrono::steady_clock::now();
     static const bool htrace = env_is("QVQ_HOST_TRACE", "1");
@@ -3082,21 +2911,17 @@ QVQ_API qvq_status qvq_lbg(qvq_ctx *ctx, uint32_t bits, double eps, double *code
     // rows wait for the end of the call, where the ranks vote, sum the cells wanted together
     // (kahan_chained) and vote again, so that every rank redoes the quantize or none does.
     // QVQ_SPECULATE=0: synchronous from the start.
-    const bool kahan = kahan_mode(ctx) && ctx->cs == QVQ_CS_SCALED;
+    const bool kahan = kahan_mode(ctx) && ctx->ts.cs == QVQ_CS_SCALED;
     const bool multi = ctx->nranks > 1 && (ctx->comm || ctx->host_ar);
     static const bool spec_off = env_is("QVQ_SPECULATE", "0");
     bool spec = kahan && !spec_off;
     if (spec && (st = ensure_speculation(ctx, Kmax)) != QVQ_OK) return st;
-    if (kahan && !ctx->d_A_alt) HIPCHK(hipMalloc(&ctx->d_A_alt, ctx->N * 4));
+    if (kahan && (st = ensure_apool(ctx, ctx->ts, 2)) != QVQ_OK) return st;
     // several ranks, speculative: one assignment buffer per level, so that every level's parent
     // assignment is still there when the deferred checks finish at the end of the call
     const uint32_t npool = spec && multi ? std::max<uint32_t>(4, bits + 1) : 4;
-    while (spec && 4 + ctx->d_Aext.size() < npool) {
-        uint32_t *p = nullptr;
-        HIPCHK(hipMalloc(&p, ctx->N * 4));
-        ctx->d_Aext.push_back(p);
-    }
-    ctx->deferred.clear();
+    if (spec && (st = ensure_apool(ctx, ctx->ts, npool)) != QVQ_OK) return st;
+    ctx->kh.deferred.clear();
     struct JobGuard {   // no tree build or check outlives the call (an error return included)
         qvq_ctx *c;
         ~JobGuard() {
@@ -3116,13 +2941,13 @@ QVQ_API qvq_status qvq_lbg(qvq_ctx *ctx, uint32_t bits, double eps, double *code
     uint64_t out_seq = 0;
     auto enqueue_out = [&]() -> qvq_status {
         if (ctx->timing_level == -1) HIPCHK(hipEventRecord(ctx->ev_end, ctx->stream));   // each record idles the GPU ~6 us
-        uint8_t *dh_small = reinterpret_cast<uint8_t *>(ctx->dh_ready) + 64;
+        uint8_t *dh_small = reinterpret_cast<uint8_t *>(ctx->h_ready.dev()) + 64;
         static_assert(3 * sizeof(double) + LEVEL_COUNTERS * sizeof(unsigned) <= 1024 - 64, "small results exceed the mapped area");
-        const uint64_t cb_bytes = codebook ? (uint64_t)Kmax * ctx->D * 8 : 0;
+        const uint64_t cb_bytes = codebook ? (uint64_t)Kmax * ctx->ts.D * 8 : 0;
         uint64_t *done = reinterpret_cast<uint64_t *>(dh_small + (1024 - 64 - 8));
         out_seq = ++ctx->out_seq;
         HIPCHK(launch_copy_out(ctx->stream, ctx->d_dist_part, dh_small, 3 * sizeof(double), ctx->d_counters,
-                               dh_small + 3 * sizeof(double), LEVEL_COUNTERS * sizeof(unsigned), ctx->d_C64_cent, ctx->dh_cb,
+                               dh_small + 3 * sizeof(double), LEVEL_COUNTERS * sizeof(unsigned), ctx->lv.d_C64_cent, ctx->lv.h_cb.dev(),
                                cb_bytes, done, out_seq, ctx->d_counters + COPY_DONE_COUNTER));
         out_enqueued = true;
         return QVQ_OK;
@@ -3134,13 +2959,13 @@ QVQ_API qvq_status qvq_lbg(qvq_ctx *ctx, uint32_t bits, double eps, double *code
     bool results_copied = false;
     bool upd[32] = {};   // per level: a separate sums pass was timed (LevelSums::upd)
     auto copy_results = [&]() -> qvq_status {
-        uint8_t *h_small = reinterpret_cast<uint8_t *>(ctx->h_ready) + 64;
-        const uint64_t cb_bytes = codebook ? (uint64_t)Kmax * ctx->D * 8 : 0;
+        uint8_t *h_small = reinterpret_cast<uint8_t *>(ctx->h_ready.get()) + 64;
+        const uint64_t cb_bytes = codebook ? (uint64_t)Kmax * ctx->ts.D * 8 : 0;
         qvq_status ws = wait_flag(ctx, reinterpret_cast<volatile uint64_t *>(h_small + (1024 - 64 - 8)), out_seq);
         if (ws != QVQ_OK) return ws;
         std::memcpy(dres, h_small, sizeof(dres));
         std::memcpy(stats, h_small + sizeof(dres), sizeof(stats));
-        if (codebook) std::memcpy(codebook, ctx->h_cb, cb_bytes);
+        if (codebook) std::memcpy(codebook, ctx->lv.h_cb, cb_bytes);
         results_copied = true;
         ctx->htrace.mark("results copied");
         return QVQ_OK;
@@ -3150,7 +2975,7 @@ QVQ_API qvq_status qvq_lbg(qvq_ctx *ctx, uint32_t bits, double eps, double *code
     results_copied = false;
     const bool tmean = ctx->timing_level == -3;   // events around the mean kernel (qvq_set_timing)
     if (tmean) HIPCHK(hipEventRecord(ctx->ev[31][0], ctx->stream));
-    HIPCHK(launch_mean_sums(ctx->stream, ctx->Dp, ctx->d_codes, ctx->N, ctx->D, ctx->d_plut, ctx->d_mean,
+    HIPCHK(launch_mean_sums(ctx->stream, ctx->ts.Dp, ctx->ts.d_codes, ctx->ts.N, ctx->ts.D, ctx->d_plut, ctx->d_mean,
                             ctx->d_counters, N_COUNTERS, d_dist, hist, ctx->d_lut64));
     if (tmean) HIPCHK(hipEventRecord(ctx->ev[31][1], ctx->stream));
     if ((st = all_reduce_sums(ctx, 1, ctx->d_mean, MEAN_COPIES)) != QVQ_OK) {
@@ -3162,7 +2987,7 @@ QVQ_API qvq_status qvq_lbg(qvq_ctx *ctx, uint32_t bits, double eps, double *code
     if ((st = clear_dirty_sums(ctx)) != QVQ_OK) return st;
     // the split a finalize writes: with deferred ties the level's own split must survive its
     // (speculative) finalize, so the next one goes to the other buffer and the two swap
-    double *split_out = ctx->d_C64_split;
+    double *split_out = ctx->lv.d_C64_split;
     // The finalize of the K cells whose sums rs describes (K = 1: the mean sums), with the split
     // and the tables of the next level (its plan: next) or, at the last level (next null), the
     // distortion term.  clear1: the finalize also clears sums copy 1 after adding it (no fused
@@ -3183,15 +3008,14 @@ QVQ_API qvq_status qvq_lbg(qvq_ctx *ctx, uint32_t bits, double eps, double *code
     LevelPlan plan = plan_level(ctx, 2);
     if ((st = finalize(1, bits > 0 ? &plan : nullptr)) != QVQ_OK) return st;
     // with bits >= 1 the first search writes every row's index
-    if (bits == 0) HIPCHK(hipMemsetAsync(ctx->d_A, 0, ctx->N * 4, ctx->stream));
+    if (bits == 0) HIPCHK(hipMemsetAsync(ctx->ts.d_A, 0, ctx->ts.N * 4, ctx->stream));
 
     const bool sync_kahan = kahan && !spec;
-    if (sync_kahan) split_out = ctx->d_C64_split_alt;
-    // the assignment buffers (d_A, d_A_alt, d_A3, d_A4 and d_Aext own them together): level L
-    // writes abuf[L % P]; a check of level L reads A_{L-1} until level L + 3 starts (one rank) or
+    if (sync_kahan) split_out = ctx->lv.d_C64_split_alt;
+    // the assignment buffers (apool owns them; d_A, d_A_alt, d_A3 and d_A4 are views): level L
+    // writes apool[L % P]; a check of level L reads A_{L-1} until level L + 3 starts (one rank) or
     // to the end of the call (several ranks, P > bits)
-    std::vector<uint32_t *> abuf = {ctx->d_A, ctx->d_A_alt, ctx->d_A3, ctx->d_A4};
-    abuf.insert(abuf.end(), ctx->d_Aext.begin(), ctx->d_Aext.end());
+    const std::vector<DevBuf<uint32_t>> &abuf = ctx->ts.apool;
     const uint32_t P = spec ? (uint32_t)std::min<size_t>(abuf.size(), npool) : 4;
     std::vector<uint32_t *> alev(bits + 1, nullptr);   // A_L of this call
     bool spec_failed = false, local_fail = false;
@@ -3210,17 +3034,14 @@ QVQ_API qvq_status qvq_lbg(qvq_ctx *ctx, uint32_t bits, double eps, double *code
                 }
                 local_fail = local_fail || !ok;   // several ranks: every rank runs on to the vote
             }
-            ctx->d_A = abuf[lvl % P];
-            ctx->d_A_alt = abuf[(lvl + P - 1) % P];
-            ctx->d_A3 = abuf[(lvl + 1) % P];   // the buffers stay distinct, and owned, across calls
-            ctx->d_A4 = abuf[(lvl + 2) % P];
-            ctx->d_Aext.clear();   // the rest of the pool
-            for (uint32_t *q : abuf)
-                if (q != ctx->d_A && q != ctx->d_A_alt && q != ctx->d_A3 && q != ctx->d_A4) ctx->d_Aext.push_back(q);
+            ctx->ts.d_A = abuf[lvl % P];
+            ctx->ts.d_A_alt = abuf[(lvl + P - 1) % P];
+            ctx->ts.d_A3 = abuf[(lvl + 1) % P];   // (P >= 4: the four views stay distinct across calls)
+            ctx->ts.d_A4 = abuf[(lvl + 2) % P];
         } else if (kahan) {
-            std::swap(ctx->d_A, ctx->d_A_alt);   // d_A_alt: the previous level's assignment
+            std::swap(ctx->ts.d_A, ctx->ts.d_A_alt);   // d_A_alt: the previous level's assignment
         }
-        alev[lvl] = ctx->d_A;
+        alev[lvl] = ctx->ts.d_A;
         const LevelPlan p = plan;
         const bool split = lvl < bits;
         if (split) plan = plan_level(ctx, 2 * K);
@@ -3247,13 +3068,13 @@ QVQ_API qvq_status qvq_lbg(qvq_ctx *ctx, uint32_t bits, double eps, double *code
             if ((st = all_reduce_sums(ctx, K)) != QVQ_OK) return st;
             TieExport tx;
             if (spec) {   // the level's tie rows and their indices go out with its codebook
-                tx.rows = ctx->d_ties;
+                tx.rows = ctx->ts.d_ties;
                 tx.cnt = ctx->d_counters + 2 * slot + 1;   // the level's ties
-                tx.A = ctx->d_A;
-                tx.codes = ctx->d_codes;
+                tx.A = ctx->ts.d_A;
+                tx.codes = ctx->ts.d_codes;
                 tx.cap = ctx->tx_cap;
-                tx.n_rows = ctx->N;
-                tx.out = ctx->dh_tx[lvl % 3];
+                tx.n_rows = ctx->ts.N;
+                tx.out = ctx->h_tx[lvl % 3].dev();
             }
             if ((st = finalize(K, next, rs, tx)) != QVQ_OK) return st;
             if (spec) {   // the check of this level, on the worker
@@ -3264,7 +3085,7 @@ QVQ_API qvq_status qvq_lbg(qvq_ctx *ctx, uint32_t bits, double eps, double *code
                 v.status = 1;
                 v.seq = ctx->seq;
                 v.par = (int)(lvl % 3);
-                v.A_prev = lvl >= 2 ? ctx->d_A_alt : nullptr;
+                v.A_prev = lvl >= 2 ? ctx->ts.d_A_alt : nullptr;
                 qvq_ctx::Verify *vp = &v;
                 post_job(ctx, [ctx, vp] {
                     verify_level(ctx, *vp);
@@ -3286,8 +3107,8 @@ QVQ_API qvq_status qvq_lbg(qvq_ctx *ctx, uint32_t bits, double eps, double *code
                     if ((st = finalize(K, next, rs, TieExport(), !kd_merge(ctx))) != QVQ_OK) return st;
                 }
                 if (split) {
-                    std::swap(ctx->d_C64_split, ctx->d_C64_split_alt);
-                    split_out = ctx->d_C64_split_alt;
+                    std::swap(ctx->lv.d_C64_split, ctx->lv.d_C64_split_alt);
+                    split_out = ctx->lv.d_C64_split_alt;
                 }
             }
         }
@@ -3307,7 +3128,7 @@ QVQ_API qvq_status qvq_lbg(qvq_ctx *ctx, uint32_t bits, double eps, double *code
         spec_failed = local_fail;
         if (multi && (st = resolve_deferred(ctx, bits, alev, spec_failed)) != QVQ_OK) return st;
     }
-    ctx->deferred.clear();
+    ctx->kh.deferred.clear();
     if (!spec_failed) break;
     // a check failed: every check joined, the stream drained, then the quantize again with
     // synchronous Kahan levels
@@ -3315,7 +3136,7 @@ QVQ_API qvq_status qvq_lbg(qvq_ctx *ctx, uint32_t bits, double eps, double *code
         v.cancel.store(true);
         join_verify(ctx, v);
     }
-    ctx->deferred.clear();
+    ctx->kh.deferred.clear();
     if ((st = wait_stream(ctx)) != QVQ_OK) return st;
     if ((st = clear_dirty_sums(ctx)) != QVQ_OK) return st;
     ctx->tm.kahan_redo++;
@@ -3327,10 +3148,10 @@ QVQ_API qvq_status qvq_lbg(qvq_ctx *ctx, uint32_t bits, double eps, double *code
     if (!out_enqueued && (st = enqueue_out()) != QVQ_OK) return st;
     if (!results_copied && (st = copy_results()) != QVQ_OK) return st;
     if (assign)   // every collective of this call is complete: a plain copy
-        HIPCHK(host_copy(ctx, assign, ctx->d_A, ctx->N * 4, hipMemcpyDeviceToHost));
+        HIPCHK(host_copy(ctx, assign, ctx->ts.d_A, ctx->ts.N * 4, hipMemcpyDeviceToHost));
     // closed form: sum ||x||^2 - sum_k (2 c_k.S_k - n_k ||c_k||^2) cancels to a few ulps of
     // sum ||x||^2 when the cells are (nearly) exact; a distortion is never negative
-    const double dist_final = std::max(0.0, (dres[0] - dres[2]) / (dres[1] * (double)ctx->D));
+    const double dist_final = std::max(0.0, (dres[0] - dres[2]) / (dres[1] * (double)ctx->ts.D));
     if (distortion) *distortion = dist_final;
     for (uint32_t lvl = 1; lvl <= bits; lvl++) {
         // assign: the search kernel; update: the non-fused update; other: the rest of the
@@ -3375,14 +3196,14 @@ QVQ_API qvq_status qvq_lbg(qvq_ctx *ctx, uint32_t bits, double eps, double *code
 QVQ_API qvq_status qvq_assign(qvq_ctx *ctx, const double *C, uint32_t K, uint32_t *assign) {
     if (!ctx) return QVQ_EINVAL;
     GUARD(ctx);
-    if (ctx->N == 0) return fail(ctx, QVQ_ESTATE, "no training set");
+    if (ctx->ts.N == 0) return fail(ctx, QVQ_ESTATE, "no training set");
     if (!C || K == 0) return fail(ctx, QVQ_EINVAL, "empty codebook");
-    if (!ctx->exact) {
+    if (!ctx->ts.exact) {
         // the searches' near-tie thresholds (mfma_setup, valu_coeffs) and the f16 / fp32 score scale
         // 2^t hold for components in [cmin, cmax] only; NaN fails the comparison too
         double vmin, vmax, cmin, cmax;
-        codebook_range(ctx->terms, vmin, vmax, cmin, cmax);
-        for (uint64_t i = 0; i < (uint64_t)K * ctx->D; i++)
+        codebook_range(ctx->ts.terms, vmin, vmax, cmin, cmax);
+        for (uint64_t i = 0; i < (uint64_t)K * ctx->ts.D; i++)
             if (!(C[i] >= cmin && C[i] <= cmax))
                 return fail(ctx, QVQ_EINVAL, "codebook outside 1.2 times the colour space's value range");
     }
@@ -3391,13 +3212,13 @@ QVQ_API qvq_status qvq_assign(qvq_ctx *ctx, const double *C, uint32_t K, uint32_
     qvq_status st = ensure_levels(ctx, K);
     if (st != QVQ_OK) return st;
     std::memset(&ctx->tm, 0, sizeof(ctx->tm));
-    HIPCHK(hipMemcpy(ctx->d_C64_split, C, (uint64_t)K * ctx->D * 8, hipMemcpyHostToDevice));
-    if (ctx->exact) {
+    HIPCHK(hipMemcpy(ctx->lv.d_C64_split, C, (uint64_t)K * ctx->ts.D * 8, hipMemcpyHostToDevice));
+    if (ctx->ts.exact) {
         unsigned nt = 0;
         if ((st = exact_assign(ctx, C, K, nt)) != QVQ_OK) return st;
         ctx->tm.levels = 1;
         ctx->tm.host_ties[0] = nt;
-        if (assign) HIPCHK(hipMemcpy(assign, ctx->d_A, ctx->N * 4, hipMemcpyDeviceToHost));
+        if (assign) HIPCHK(hipMemcpy(assign, ctx->ts.d_A, ctx->ts.N * 4, hipMemcpyDeviceToHost));
         return QVQ_OK;
     }
     HIPCHK(hipMemsetAsync(ctx->d_counters, 0, 2 * sizeof(unsigned), ctx->stream));
@@ -3406,7 +3227,7 @@ QVQ_API qvq_status qvq_assign(qvq_ctx *ctx, const double *C, uint32_t K, uint32_
     if ((st = run_level(ctx, plan_level(ctx, K), K, 0, false, C, 0, false, ls)) != QVQ_OK) return st;
     unsigned stats[2];
     HIPCHK(hipMemcpyAsync(stats, ctx->d_counters, sizeof(stats), hipMemcpyDeviceToHost, ctx->stream));
-    if (assign) HIPCHK(hipMemcpyAsync(assign, ctx->d_A, ctx->N * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (assign) HIPCHK(hipMemcpyAsync(assign, ctx->ts.d_A, ctx->ts.N * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     ctx->tm.levels = 1;
     ctx->tm.flagged[0] = stats[0];
@@ -3417,24 +3238,24 @@ QVQ_API qvq_status qvq_assign(qvq_ctx *ctx, const double *C, uint32_t K, uint32_
 QVQ_API qvq_status qvq_update(qvq_ctx *ctx, const uint32_t *assign, uint32_t K, double *C_out, uint64_t *counts) {
     if (!ctx) return QVQ_EINVAL;
     GUARD(ctx);
-    if (ctx->N == 0) return fail(ctx, QVQ_ESTATE, "no training set");
+    if (ctx->ts.N == 0) return fail(ctx, QVQ_ESTATE, "no training set");
     if (!assign || K == 0) return fail(ctx, QVQ_EINVAL, "empty assignment");
     ctx->rf.valid = false;
-    for (uint64_t i = 0; i < ctx->N; i++)
+    for (uint64_t i = 0; i < ctx->ts.N; i++)
         if (assign[i] >= K) return fail(ctx, QVQ_EINVAL, "assignment index out of range");
     HIPCHK(hipSetDevice(ctx->dev));
     qvq_status st = ensure_levels(ctx, K);
     if (st != QVQ_OK) return st;
-    HIPCHK(hipMemcpy(ctx->d_A, assign, ctx->N * 4, hipMemcpyHostToDevice));
-    if (ctx->exact) {
+    HIPCHK(hipMemcpy(ctx->ts.d_A, assign, ctx->ts.N * 4, hipMemcpyHostToDevice));
+    if (ctx->ts.exact) {
         if ((st = exact_single_rank(ctx)) != QVQ_OK) return st;
-        uint64_t *d_cnt = ctx->d_sums;   // K u64 of scratch (2KD + K)
+        uint64_t *d_cnt = ctx->lv.d_sums;   // K u64 of scratch (2KD + K)
         if ((st = exact_centroids(ctx, false, K, d_cnt)) != QVQ_OK) return st;
-        if (C_out) HIPCHK(hipMemcpyAsync(C_out, ctx->d_C64_cent, (uint64_t)K * ctx->D * 8, hipMemcpyDeviceToHost, ctx->stream));
+        if (C_out) HIPCHK(hipMemcpyAsync(C_out, ctx->lv.d_C64_cent, (uint64_t)K * ctx->ts.D * 8, hipMemcpyDeviceToHost, ctx->stream));
         if (counts) HIPCHK(hipMemcpyAsync(counts, d_cnt, (uint64_t)K * 8, hipMemcpyDeviceToHost, ctx->stream));
         return wait_stream(ctx);
     }
-    if ((st = run_update(ctx, plan_level(ctx, K), ctx->d_A, K)) != QVQ_OK) return st;
+    if ((st = run_update(ctx, plan_level(ctx, K), ctx->ts.d_A, K)) != QVQ_OK) return st;
     if ((st = all_reduce_sums(ctx, K)) != QVQ_OK) return st;
     FinArgs f = finalize_args(ctx, K, false);   // the centroids only
     const ReducedSums rs;
@@ -3442,11 +3263,11 @@ QVQ_API qvq_status qvq_update(qvq_ctx *ctx, const uint32_t *assign, uint32_t K, 
     if ((st = run_finalize(ctx, f)) != QVQ_OK) return st;
     // results land in context-owned pinned memory and reach the caller only after the bounded
     // wait succeeds (a failed wait can leave these copies queued: wait_failed)
-    const uint64_t cB = (uint64_t)K * ctx->D * 8, nB = (uint64_t)K * 8;
-    if ((st = ensure_pinned(ctx, ctx->h_stage, ctx->stage_bytes, cB + nB)) != QVQ_OK) return st;
+    const uint64_t cB = (uint64_t)K * ctx->ts.D * 8, nB = (uint64_t)K * 8;
+    HIPCHK(ctx->h_stage.ensure(cB + nB));
     uint8_t *stage = static_cast<uint8_t *>(ctx->h_stage);
-    HIPCHK(hipMemcpyAsync(stage, ctx->d_C64_cent, cB, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(stage + cB, ctx->d_sums + 2 * (uint64_t)K * ctx->D, nB, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(stage, ctx->lv.d_C64_cent, cB, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(stage + cB, ctx->lv.d_sums + 2 * (uint64_t)K * ctx->ts.D, nB, hipMemcpyDeviceToHost, ctx->stream));
     if ((st = wait_stream(ctx)) != QVQ_OK) return st;   // bounded: the all-reduce may wait on peer ranks
     if (C_out) std::memcpy(C_out, stage, cB);
     if (counts) std::memcpy(counts, stage + cB, nB);
@@ -3458,40 +3279,40 @@ QVQ_API qvq_status qvq_update(qvq_ctx *ctx, const uint32_t *assign, uint32_t K, 
 QVQ_API qvq_status qvq_update_kahan(qvq_ctx *ctx, const uint32_t *assign, uint32_t K, double *C_out) {
     if (!ctx) return QVQ_EINVAL;
     GUARD(ctx);
-    if (ctx->N == 0) return fail(ctx, QVQ_ESTATE, "no training set");
+    if (ctx->ts.N == 0) return fail(ctx, QVQ_ESTATE, "no training set");
     if (!assign || K == 0) return fail(ctx, QVQ_EINVAL, "empty assignment");
     ctx->rf.valid = false;
-    if (ctx->exact) return qvq_update(ctx, assign, K, C_out, nullptr);   // exact mode: the Kahan chain already
-    if (ctx->cs != QVQ_CS_SCALED) return qvq_update(ctx, assign, K, C_out, nullptr);   // integers: exact = Kahan
-    for (uint64_t i = 0; i < ctx->N; i++)
+    if (ctx->ts.exact) return qvq_update(ctx, assign, K, C_out, nullptr);   // exact mode: the Kahan chain already
+    if (ctx->ts.cs != QVQ_CS_SCALED) return qvq_update(ctx, assign, K, C_out, nullptr);   // integers: exact = Kahan
+    for (uint64_t i = 0; i < ctx->ts.N; i++)
         if (assign[i] >= K) return fail(ctx, QVQ_EINVAL, "assignment index out of range");
     HIPCHK(hipSetDevice(ctx->dev));
     qvq_status st = ensure_levels(ctx, K);
     if (st != QVQ_OK) return st;
     if ((st = ensure_kahan(ctx, K)) != QVQ_OK) return st;
-    HIPCHK(hipMemcpy(ctx->d_A, assign, ctx->N * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(ctx->ts.d_A, assign, ctx->ts.N * 4, hipMemcpyHostToDevice));
     if (ctx->nranks > 1) {   // every rank's rows: the chains pass from rank to rank (kahan_chained)
-        if ((st = kahan_chained(ctx, K == 1 ? nullptr : ctx->d_A, K, nullptr, K, false)) != QVQ_OK)
+        if ((st = kahan_chained(ctx, K == 1 ? nullptr : ctx->ts.d_A, K, nullptr, K, false)) != QVQ_OK)
             return st;
     } else {
-        uint64_t max_rows = ctx->N;   // the longest chain (short ones run step by step)
+        uint64_t max_rows = ctx->ts.N;   // the longest chain (short ones run step by step)
         if (K > 1) {
             std::vector<uint64_t> n(K, 0);
-            for (uint64_t i = 0; i < ctx->N; i++) n[assign[i]]++;   // (checked < K above)
+            for (uint64_t i = 0; i < ctx->ts.N; i++) n[assign[i]]++;   // (checked < K above)
             max_rows = std::max<uint64_t>(1, *std::max_element(n.begin(), n.end()));
         }
-        HIPCHK(launch_kahan_centroids(ctx->stream, ctx->kw, ctx->d_codes, ctx->Dp, ctx->D, ctx->N,
-                                      K == 1 ? nullptr : ctx->d_A, K, ctx->d_kc_cent, nullptr, nullptr, 0, max_rows));
+        HIPCHK(launch_kahan_centroids(ctx->stream, ctx->kh.kw, ctx->ts.d_codes, ctx->ts.Dp, ctx->ts.D, ctx->ts.N,
+                                      K == 1 ? nullptr : ctx->ts.d_A, K, ctx->kh.cells.d_kc_cent, nullptr, nullptr, 0, max_rows));
     }
-    const uint64_t cB = (uint64_t)K * ctx->D * 8;
-    if ((st = ensure_pinned(ctx, ctx->h_stage, ctx->stage_bytes, cB)) != QVQ_OK) return st;
-    HIPCHK(hipMemcpyAsync(ctx->h_stage, ctx->d_kc_cent, cB, hipMemcpyDeviceToHost, ctx->stream));
+    const uint64_t cB = (uint64_t)K * ctx->ts.D * 8;
+    HIPCHK(ctx->h_stage.ensure(cB));
+    HIPCHK(hipMemcpyAsync(ctx->h_stage, ctx->kh.cells.d_kc_cent, cB, hipMemcpyDeviceToHost, ctx->stream));
     if ((st = wait_stream(ctx)) != QVQ_OK) return st;
     if (C_out) std::memcpy(C_out, ctx->h_stage, cB);
     if (env_is("QVQ_KAHAN_DEBUG", "1")) {
         unsigned ms[4];
-        HIPCHK(hipMemcpy(ms, ctx->kw.stats, sizeof(ms), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemset(ctx->kw.stats, 0, sizeof(ms)));
+        HIPCHK(hipMemcpy(ms, ctx->kh.kw.stats, sizeof(ms), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemset(ctx->kh.kw.stats, 0, sizeof(ms)));
         std::fprintf(stderr, "qvq kahan: K %u blocks not composable %u block misses %u replays %u\n", K, ms[0], ms[1],
                      ms[2]);
     }
@@ -3505,25 +3326,25 @@ QVQ_API qvq_status qvq_update_kahan_split(qvq_ctx *ctx, const uint32_t *assign, 
                                           uint32_t nsplits, double *C_out) {
     if (!ctx) return QVQ_EINVAL;
     GUARD(ctx);
-    if (ctx->N == 0) return fail(ctx, QVQ_ESTATE, "no training set");
-    if (ctx->exact || ctx->cs != QVQ_CS_SCALED) return fail(ctx, QVQ_EUNSUPPORTED, "SCALED byte rows only");
+    if (ctx->ts.N == 0) return fail(ctx, QVQ_ESTATE, "no training set");
+    if (ctx->ts.exact || ctx->ts.cs != QVQ_CS_SCALED) return fail(ctx, QVQ_EUNSUPPORTED, "SCALED byte rows only");
     if (!assign || K == 0 || !splits || nsplits == 0) return fail(ctx, QVQ_EINVAL, "empty assignment or splits");
     ctx->rf.valid = false;
-    if (splits[0] != 0 || splits[nsplits] != ctx->N) return fail(ctx, QVQ_EINVAL, "splits must run from 0 to N");
+    if (splits[0] != 0 || splits[nsplits] != ctx->ts.N) return fail(ctx, QVQ_EINVAL, "splits must run from 0 to N");
     for (uint32_t i = 0; i < nsplits; i++)
         if (splits[i] > splits[i + 1]) return fail(ctx, QVQ_EINVAL, "splits must not decrease");
-    for (uint64_t i = 0; i < ctx->N; i++)
+    for (uint64_t i = 0; i < ctx->ts.N; i++)
         if (assign[i] >= K) return fail(ctx, QVQ_EINVAL, "assignment index out of range");
     HIPCHK(hipSetDevice(ctx->dev));
     qvq_status st = ensure_levels(ctx, K);
     if (st != QVQ_OK) return st;
-    HIPCHK(hipMemcpy(ctx->d_A, assign, ctx->N * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(ctx->ts.d_A, assign, ctx->ts.N * 4, hipMemcpyHostToDevice));
     const std::vector<uint64_t> cuts(splits, splits + nsplits + 1);
-    if ((st = kahan_chained(ctx, K == 1 ? nullptr : ctx->d_A, K, nullptr, K, false, &cuts)) != QVQ_OK)
+    if ((st = kahan_chained(ctx, K == 1 ? nullptr : ctx->ts.d_A, K, nullptr, K, false, &cuts)) != QVQ_OK)
         return st;
-    const uint64_t cB = (uint64_t)K * ctx->D * 8;
-    if ((st = ensure_pinned(ctx, ctx->h_stage, ctx->stage_bytes, cB)) != QVQ_OK) return st;
-    HIPCHK(hipMemcpyAsync(ctx->h_stage, ctx->d_kc_cent, cB, hipMemcpyDeviceToHost, ctx->stream));
+    const uint64_t cB = (uint64_t)K * ctx->ts.D * 8;
+    HIPCHK(ctx->h_stage.ensure(cB));
+    HIPCHK(hipMemcpyAsync(ctx->h_stage, ctx->kh.cells.d_kc_cent, cB, hipMemcpyDeviceToHost, ctx->stream));
     if ((st = wait_stream(ctx)) != QVQ_OK) return st;
     if (C_out) std::memcpy(C_out, ctx->h_stage, cB);
     return QVQ_OK;
@@ -3558,22 +3379,22 @@ QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start, u
         lst = s;
         lmsg = m;
     };
-    if (ctx->N == 0) reject(QVQ_ESTATE, "no training set");
+    if (ctx->ts.N == 0) reject(QVQ_ESTATE, "no training set");
     else if (flags & ~(uint32_t)(QVQ_REFINE_FRESH | QVQ_REFINE_RESEED)) reject(QVQ_EINVAL, "unknown refine flags");
     else if (max_iters == 0 && !fresh) reject(QVQ_EINVAL, "max_iters = 0 needs QVQ_REFINE_FRESH");
     else if (K == 0 || K > (1u << 20)) reject(QVQ_EINVAL, "K must be in 1 .. 2^20");
     else if (!(eps >= 0)) reject(QVQ_EINVAL, "eps must be >= 0");
-    else if (ctx->exact) reject(QVQ_EUNSUPPORTED, "refinement of an exact-mode training set is not supported");
+    else if (ctx->ts.exact) reject(QVQ_EUNSUPPORTED, "refinement of an exact-mode training set is not supported");
     else if (reseed && sharded) reject(QVQ_EUNSUPPORTED, "QVQ_REFINE_RESEED is not supported on a communicator");
-    else if (reseed && ctx->N >= 0xFFFFFFFFull) reject(QVQ_EUNSUPPORTED, "QVQ_REFINE_RESEED takes fewer than 2^32 - 1 rows");
+    else if (reseed && ctx->ts.N >= 0xFFFFFFFFull) reject(QVQ_EUNSUPPORTED, "QVQ_REFINE_RESEED takes fewer than 2^32 - 1 rows");
     else if (cont) {
         if (!ctx->rf.valid) reject(QVQ_ESTATE, "no qvq_lbg or qvq_refine result to continue from");
         else if (ctx->rf.K != K) reject(QVQ_EINVAL, "K differs from the result to continue from");
     } else {
         double vmin, vmax, cmin, cmax;
-        codebook_range(ctx->terms, vmin, vmax, cmin, cmax);
+        codebook_range(ctx->ts.terms, vmin, vmax, cmin, cmax);
         // (the searches' error bands assume |c| <= 1.2 vmax: valu_coeffs, mf_th)
-        for (uint64_t i = 0; i < (uint64_t)K * ctx->D; i++)
+        for (uint64_t i = 0; i < (uint64_t)K * ctx->ts.D; i++)
             if (!(C_start[i] >= vmin && C_start[i] <= vmax)) {
                 reject(QVQ_EINVAL, "starting codebook outside the colour space's value range");
                 break;
@@ -3592,7 +3413,7 @@ QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start, u
         std::memcpy(&ebits, &eps, 8);
         const uint64_t head[5] = {K, max_iters, ebits, flags, cont ? 1u : 0u};
         mix(head, sizeof(head));
-        if (!cont && K >= 1 && K <= (1u << 20)) mix(C_start, (uint64_t)K * ctx->D * 8);
+        if (!cont && K >= 1 && K <= (1u << 20)) mix(C_start, (uint64_t)K * ctx->ts.D * 8);
         const uint32_t R = (uint32_t)ctx->nranks;
         std::vector<uint64_t> v(2ull * R, 0);
         v[2 * ctx->rank] = lst == QVQ_OK ? 1 : 2;   // (0: the rank wrote nothing)
@@ -3615,28 +3436,23 @@ QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start, u
     HIPCHK(hipSetDevice(ctx->dev));
     qvq_status st = ensure_levels(ctx, std::max<uint32_t>(K, 2));
     if (st != QVQ_OK) return st;
-    if (!ctx->d_A_alt) HIPCHK(hipMalloc(&ctx->d_A_alt, ctx->N * 4));
+    if ((st = ensure_apool(ctx, ctx->ts, 2)) != QVQ_OK) return st;
     ReseedWork rw;
     if (reseed) {
         const uint64_t need = reseed_layout(K).total;
-        if (ctx->reseed_bytes < need) {
-            dfree(ctx->d_reseed);
-            ctx->reseed_bytes = 0;
-            HIPCHK(hipMalloc(&ctx->d_reseed, need));
-            ctx->reseed_bytes = need;
-        }
+        HIPCHK(ctx->d_reseed.ensure(need));
         rw = reseed_work(ctx->d_reseed, K);
         HIPCHK(hipMemsetAsync(rw.state, 0, 16, ctx->stream));   // (an abandoned call may have left a count)
     }
     std::memset(&ctx->tm, 0, sizeof(ctx->tm));
-    const uint32_t D = ctx->D;
+    const uint32_t D = ctx->ts.D;
     const uint64_t KD = (uint64_t)K * D;
     // sum ||x||^2 and the rows, from the byte histogram
     auto hist_totals = [&](const uint64_t *hist, double &sq_out, uint64_t &rows_out) {
         long double sq = 0;
         uint64_t n = 0;
         for (int b = 0; b < 256; b++) {
-            sq += (long double)hist[b] * (long double)ctx->terms.v64[b] * (long double)ctx->terms.v64[b];
+            sq += (long double)hist[b] * (long double)ctx->ts.terms.v64[b] * (long double)ctx->ts.terms.v64[b];
             n += hist[b];
         }
         sq_out = (double)sq;
@@ -3647,10 +3463,10 @@ QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start, u
     if (sharded) {   // of every rank's rows: the histogram all-reduced as integers, as qvq_lbg does (once per call)
         HIPCHK(hipMemcpyAsync(ctx->d_hist + 256, ctx->d_hist, 256 * 8, hipMemcpyDeviceToDevice, ctx->stream));
         if ((st = all_reduce(ctx, ctx->d_hist + 256, 256, false)) != QVQ_OK) return st;
-        if ((st = ensure_pinned(ctx, ctx->h_stage, ctx->stage_bytes, 256 * 8)) != QVQ_OK) return st;
+        HIPCHK(ctx->h_stage.ensure(256 * 8));
         HIPCHK(hipMemcpyAsync(ctx->h_stage, ctx->d_hist + 256, 256 * 8, hipMemcpyDeviceToHost, ctx->stream));
         if ((st = wait_stream(ctx)) != QVQ_OK) return st;   // bounded: the all-reduce may wait on peer ranks
-        hist_totals(static_cast<const uint64_t *>(ctx->h_stage), xsq, rows_all);
+        hist_totals(reinterpret_cast<const uint64_t *>(ctx->h_stage.get()), xsq, rows_all);
     } else {
         if (!ctx->rf.have_xsq) {   // once per training set
             uint64_t hist[256], n;
@@ -3660,14 +3476,14 @@ QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start, u
             ctx->rf.have_xsq = true;
         }
         xsq = ctx->rf.xsq;
-        rows_all = ctx->N;
+        rows_all = ctx->ts.N;
     }
     const double norm = (sharded ? (double)rows_all : ctx->rf.rows) * (double)D;
     // a communicator: the rows changed are counted into the u64 behind the level's sums and
     // all-reduced with them (one collective per iteration)
     const uint64_t cell_u64 = 2 * KD + K;
-    uint64_t *const changed64 = sharded ? ctx->d_sums + cell_u64 : nullptr;
-    if (!cont) HIPCHK(hipMemcpy(ctx->d_C64_cent, C_start, KD * 8, hipMemcpyHostToDevice));
+    uint64_t *const changed64 = sharded ? ctx->lv.d_sums + cell_u64 : nullptr;
+    if (!cont) HIPCHK(hipMemcpy(ctx->lv.d_C64_cent, C_start, KD * 8, hipMemcpyHostToDevice));
     // both iterations' counters, the changed total; copy 1 of the sums if a quantize left it dirty
     HIPCHK(hipMemsetAsync(ctx->d_counters, 0, 4 * sizeof(unsigned), ctx->stream));
     HIPCHK(hipMemsetAsync(ctx->d_counters + CHANGED_COUNTER, 0, 2 * sizeof(unsigned), ctx->stream));
@@ -3681,13 +3497,13 @@ QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start, u
     auto publish = [&](uint32_t t, bool tables, const ReducedSums *rs, unsigned *cnts, bool count) -> qvq_status {
         FinArgs f = finalize_args(ctx, K, true);
         if (rs) sums_args(ctx, f, rs, true);
-        f.C_src = ctx->d_C64_cent;
-        if (tables) tables_args(ctx, f, 1, ctx->d_C64_split, dev_cb_of(ctx, t), plan.prunable);
+        f.C_src = ctx->lv.d_C64_cent;
+        if (tables) tables_args(ctx, f, 1, ctx->lv.d_C64_split, dev_cb_of(ctx, t), plan.prunable);
         else f.measure = true;
         if (count && changed64) f.changed64 = changed64;
         else if (count) f.changed = ctx->d_counters + CHANGED_COUNTER;
         f.clear_cnt = cnts;
-        f.pub = ctx->dh_ready + 4;
+        f.pub = ctx->h_ready.dev() + 4;
         f.seq = ++ctx->seq;
         return run_finalize(ctx, f);
     };
@@ -3699,23 +3515,23 @@ QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start, u
     // publish the seeds placed; the tables, tile order and host copy from the seeded codebook, the
     // form iteration 0 uses, which carries the ready number the host waits for.
     auto publish_reseeded = [&](uint32_t t, const ReducedSums &rs, unsigned *cnts, bool count) -> qvq_status {
-        HIPCHK(launch_reseed_count(ctx->stream, ctx->d_sums, K, D, rs.copies,
+        HIPCHK(launch_reseed_count(ctx->stream, ctx->lv.d_sums, K, D, rs.copies,
                                    rs.copies > 1 ? sums_cap_stride(ctx) : 0, rs.gate, rw));
         FinArgs f = finalize_args(ctx, K, true);
         sums_args(ctx, f, &rs, true);
         if (count) f.changed = ctx->d_counters + CHANGED_COUNTER;
         f.clear_cnt = cnts;
-        f.pub = ctx->dh_ready + 4;
+        f.pub = ctx->h_ready.dev() + 4;
         f.seq = ++ctx->seq;
         qvq_status s = run_finalize(ctx, f);
         if (s != QVQ_OK) return s;
-        HIPCHK(launch_reseed_rows(ctx->stream, ctx->d_codes, ctx->Dp, D, ctx->N, ctx->d_A, ctx->d_C64_cent, K,
-                                  ctx->d_lut64, ctx->cs == QVQ_CS_SCALED, rw));
-        HIPCHK(launch_reseed_select(ctx->stream, ctx->d_codes, ctx->Dp, D, ctx->N, ctx->d_lut64, ctx->d_C64_cent, K, rw,
-                                    ctx->dh_ready + 6));
+        HIPCHK(launch_reseed_rows(ctx->stream, ctx->ts.d_codes, ctx->ts.Dp, D, ctx->ts.N, ctx->ts.d_A, ctx->lv.d_C64_cent, K,
+                                  ctx->d_lut64, ctx->ts.cs == QVQ_CS_SCALED, rw));
+        HIPCHK(launch_reseed_select(ctx->stream, ctx->ts.d_codes, ctx->ts.Dp, D, ctx->ts.N, ctx->d_lut64, ctx->lv.d_C64_cent, K, rw,
+                                    ctx->h_ready.dev() + 6));
         FinArgs g = finalize_args(ctx, K, true);
-        g.C_src = ctx->d_C64_cent;
-        tables_args(ctx, g, 1, ctx->d_C64_split, dev_cb_of(ctx, t), plan.prunable);
+        g.C_src = ctx->lv.d_C64_cent;
+        tables_args(ctx, g, 1, ctx->lv.d_C64_split, dev_cb_of(ctx, t), plan.prunable);
         g.seq = ++ctx->seq;
         return run_finalize(ctx, g);
     };
@@ -3749,7 +3565,7 @@ QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start, u
             break;
         }
         const int slot = (int)(t & 1);
-        if (have_A) std::swap(ctx->d_A, ctx->d_A_alt);   // d_A_alt: A_t; d_A takes the search against C_t
+        if (have_A) std::swap(ctx->ts.d_A, ctx->ts.d_A_alt);   // d_A_alt: A_t; d_A takes the search against C_t
         LevelSums ls;   // (dropped with the search where the call stops without fresh)
         if ((st = run_level(ctx, plan, K, slot, true, host_cb_of(ctx, t), ctx->seq, false, ls)) != QVQ_OK) return st;
         if (t >= 1) absorb();   // (run_level waited for C_t)
@@ -3769,7 +3585,7 @@ QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start, u
                 std::memcpy(&term, &bits, 8);
                 d_last = std::max(0.0, (xsq - term) / norm);
             } else {   // dropped: A_t stays the assignment
-                if (have_A) std::swap(ctx->d_A, ctx->d_A_alt);
+                if (have_A) std::swap(ctx->ts.d_A, ctx->ts.d_A_alt);
                 if ((st = wait_stream(ctx)) != QVQ_OK) return st;
             }
             break;
@@ -3777,10 +3593,10 @@ QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start, u
         if ((st = reduce_level(ctx, K, slot, ls, rs)) != QVQ_OK) return st;
         if (changed64) {   // the level's sums and the rows changed over every rank: one collective
             mark_sums1(ctx);   // (the slot lies in copy 1's range: cleared if the call ends before the finalize)
-            if (have_A) HIPCHK(launch_count_changed64(ctx->stream, ctx->num_cu, ctx->d_A, ctx->d_A_alt, ctx->N, changed64));
-            if ((st = all_reduce(ctx, ctx->d_sums, cell_u64 + 1, false)) != QVQ_OK) return st;
+            if (have_A) HIPCHK(launch_count_changed64(ctx->stream, ctx->num_cu, ctx->ts.d_A, ctx->ts.d_A_alt, ctx->ts.N, changed64));
+            if ((st = all_reduce(ctx, ctx->lv.d_sums, cell_u64 + 1, false)) != QVQ_OK) return st;
         } else if (have_A) {
-            HIPCHK(launch_count_changed(ctx->stream, ctx->num_cu, ctx->d_A, ctx->d_A_alt, ctx->N,
+            HIPCHK(launch_count_changed(ctx->stream, ctx->num_cu, ctx->ts.d_A, ctx->ts.d_A_alt, ctx->ts.N,
                                         ctx->d_counters + CHANGED_COUNTER));
         }
         if (reseed) st = publish_reseeded(t + 1, rs, ctx->d_counters + 2 * slot, have_A);
@@ -3791,7 +3607,7 @@ QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start, u
     }
     // C_t as the finalize published it (t = 0: the starting codebook's copy)
     if (codebook) std::memcpy(codebook, host_cb_of(ctx, t), KD * 8);
-    if (assign) HIPCHK(host_copy(ctx, assign, ctx->d_A, ctx->N * 4, hipMemcpyDeviceToHost));
+    if (assign) HIPCHK(host_copy(ctx, assign, ctx->ts.d_A, ctx->ts.N * 4, hipMemcpyDeviceToHost));
     if (distortion) *distortion = d_last;
     if (info) {
         info->iters = t;
@@ -3887,11 +3703,7 @@ QVQ_API qvq_status qvq_decode_mse(qvq_ctx *ctx, const uint8_t *codebook, uint32_
     const uint64_t cbB = (uint64_t)K * bw * bh * 3, aB = nblocks * 4, rB = (uint64_t)xSize * ySize * 3;
     const uint64_t oA = (cbB + 15) & ~15ull, oR = (oA + aB + 15) & ~15ull, oO = (oR + rB + 15) & ~15ull;
     const uint64_t need = oO + (orig ? rB : 0);
-    if (ctx->decode_bytes < need) {
-        dfree(ctx->d_decode);
-        HIPCHK(hipMalloc(&ctx->d_decode, need));
-        ctx->decode_bytes = need;
-    }
+    HIPCHK(ctx->d_decode.ensure(need));
     uint8_t *d = ctx->d_decode;
     HIPCHK(hipMemcpyAsync(d, codebook, cbB, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(d + oA, assign, aB, hipMemcpyHostToDevice, ctx->stream));
@@ -4004,40 +3816,30 @@ QVQ_API qvq_status qvq_kdtree_device_check(qvq_ctx *ctx, const double *C, uint32
     if (!kd_build_fits(K, dim)) return fail(ctx, QVQ_EUNSUPPORTED, "device kd build: K or dim too large");
     HIPCHK(hipSetDevice(ctx->dev));
     const KdbHostLayout L = kdb_host_layout(K, dim);
-    double *dP = nullptr, *nbox = nullptr, *cbox = nullptr;
-    uint32_t *vind = nullptr;
-    KdbNode *nodes = nullptr;
-    uint8_t *flat = nullptr, *himg = nullptr, *dhimg = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    struct Free {
-        std::function<void()> f;
-        ~Free() { f(); }
-    } fr{[&] {
-        for (void *p : {(void *)dP, (void *)nbox, (void *)cbox, (void *)vind, (void *)nodes, (void *)flat})
-            if (p) (void)hipFree(p);
-        if (himg) (void)hipHostFree(himg);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    }};
-    HIPCHK(hipMalloc(&dP, (uint64_t)K * dim * 8));
-    HIPCHK(hipMalloc(&nbox, 2ull * K * 2 * dim * 8));
-    HIPCHK(hipMalloc(&cbox, 2ull * K * 2 * dim * 8));
-    HIPCHK(hipMalloc(&vind, (uint64_t)K * 4));
-    HIPCHK(hipMalloc(&nodes, 2ull * K * sizeof(KdbNode)));
-    HIPCHK(hipMalloc(&flat, tree_bytes(K, dim)));
-    HIPCHK(hipHostMalloc(&himg, L.total, hipHostMallocMapped | hipHostMallocCoherent));
-    HIPCHK(hipHostGetDevicePointer((void **)&dhimg, himg, 0));
+    DevBuf<double> dP, nbox, cbox;
+    DevBuf<uint32_t> vind;
+    DevBuf<KdbNode> nodes;
+    DevBuf<uint8_t> flat;
+    CoherentBuf<uint8_t> himg;
+    Event e0, e1;
+    HIPCHK(dP.alloc((uint64_t)K * dim));
+    HIPCHK(nbox.alloc(2ull * K * 2 * dim));
+    HIPCHK(cbox.alloc(2ull * K * 2 * dim));
+    HIPCHK(vind.alloc(K));
+    HIPCHK(nodes.alloc(2ull * K));
+    HIPCHK(flat.alloc(tree_bytes(K, dim)));
+    HIPCHK(himg.alloc(L.total));
     std::memset(himg, 0, sizeof(KdbHeader));
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
+    HIPCHK(hipEventCreate(e0.put()));
+    HIPCHK(hipEventCreate(e1.put()));
     HIPCHK(hipMemcpy(dP, C, (uint64_t)K * dim * 8, hipMemcpyHostToDevice));
     HIPCHK(hipEventRecord(e0, ctx->stream));
-    HIPCHK(launch_kd_build(ctx->stream, dP, K, dim, vind, nodes, nbox, cbox, flat, dhimg, 1));
+    HIPCHK(launch_kd_build(ctx->stream, dP, K, dim, vind, nodes, nbox, cbox, flat, himg.dev(), 1));
     HIPCHK(hipEventRecord(e1, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     float ms = 0;
     (void)hipEventElapsedTime(&ms, e0, e1);
-    const KdbHeader &h = *reinterpret_cast<const KdbHeader *>(himg);
+    const KdbHeader &h = *reinterpret_cast<const KdbHeader *>(himg.get());
     if (build_ms) {   // the launch; phase 1, phase 2, the images (the kernel's 100 MHz stamps)
         build_ms[0] = ms;
         for (int i = 0; i < 3; i++) build_ms[1 + i] = (double)h.pad2[i] * 1e-5;

@@ -2,7 +2,8 @@
 // Built by tests/cpp/Makefile (target `sanitize`) with -fsanitize=address,undefined over the
 // product's host C++ -- the reference kd-tree (quant_amd/csrc/kdtree.cpp), the bounded-wait
 // policy (wait.hpp), the codec's host code (quant_amd/cpp/*.cpp: .quant writer/reader, PPM IO,
-// colour spaces, tiling) -- and run on the CPU by tests/test_host_sanitize.py.  No GPU: the
+// colour spaces, tiling), the owning handles (owned.hpp, over a counting fake allocator) -- and
+// run on the CPU by tests/test_host_sanitize.py.  No GPU: the
 // engine calls in quant_amd/cpp are linked (libqvq.so) but never reached.  The kd-tree is
 // checked against the oracle's restatement (oracle/lbg_oracle.c, test infrastructure).
 #include <cstdio>
@@ -15,6 +16,7 @@
 #include <vector>
 
 #include "kdtree.hpp"
+#include "owned.hpp"
 #include "quant_amd/ColorSpace.hpp"
 #include "quant_amd/Compressor.hpp"
 #include "quant_amd/RGBImage.hpp"
@@ -126,6 +128,100 @@ static void test_certificate() {
     }
 }
 
+// The owning buffer handle (owned.hpp) over a fake policy that logs every call, counts the live
+// blocks and fails the allocation it is told to: moves, ensure's three cases, a group built in a
+// local and committed on success, release.  The blocks are real (malloc), so a double free or a
+// leak is the sanitizers' to report as well.
+struct FakeMem {
+    using error = bool;
+    static constexpr bool ok = true;
+    static int live, allocs, frees, fail_at;   // fail_at: the allocation (counted from 1) that fails; 0: none
+    static std::string log;                    // 'a' per allocation asked for, 'f' per free
+    static bool alloc(void **p, void **dev, size_t bytes) {
+        log += 'a';
+        if (++allocs == fail_at) return false;
+        *p = *dev = std::malloc(bytes ? bytes : 1);
+        live++;
+        return true;
+    }
+    static void free(void *p) {
+        log += 'f';
+        frees++;
+        live--;
+        std::free(p);
+    }
+    static void reset(int fail = 0) { live = allocs = frees = 0, fail_at = fail, log.clear(); }
+};
+int FakeMem::live, FakeMem::allocs, FakeMem::frees, FakeMem::fail_at;
+std::string FakeMem::log;
+
+static void test_owned() {
+    using Buf = qvq::Owned<uint32_t, FakeMem>;
+    {   // move construction and assignment
+        FakeMem::reset();
+        Buf a;
+        CHECK(a.alloc(10) && a.get() && a.size() == 10 && a.bytes() == 40 && a.dev() == a.get());
+        uint32_t *pa = a.get();
+        Buf b(std::move(a));
+        CHECK(!a.get() && a.size() == 0 && b.get() == pa && b.size() == 10 && FakeMem::live == 1);
+        Buf c;
+        CHECK(c.alloc(3) && FakeMem::live == 2);
+        c = std::move(b);   // onto a full buffer: its block freed once
+        CHECK(c.get() == pa && c.size() == 10 && !b.get() && b.size() == 0);
+        CHECK(FakeMem::live == 1 && FakeMem::frees == 1);
+    }
+    CHECK(FakeMem::live == 0 && FakeMem::frees == 2);
+    {   // ensure
+        FakeMem::reset();
+        Buf a;
+        CHECK(a.ensure(8) && FakeMem::log == "a");
+        uint32_t *pa = a.get();
+        CHECK(a.ensure(8) && a.ensure(5) && a.get() == pa && a.size() == 8 && FakeMem::log == "a");   // fits: untouched
+        CHECK(a.ensure(9) && a.size() == 9 && FakeMem::log == "afa");   // short: freed, then asked for
+        FakeMem::fail_at = FakeMem::allocs + 1;
+        CHECK(!a.ensure(100));   // fails: empty, not dangling
+        CHECK(!a.get() && !a.dev() && a.size() == 0 && a.bytes() == 0 && FakeMem::live == 0 && FakeMem::log == "afafa");
+        CHECK(a.ensure(4) && a.get() && a.size() == 4 && FakeMem::live == 1);
+        CHECK(FakeMem::frees == 2);   // nothing freed twice
+    }
+    CHECK(FakeMem::live == 0);
+    {   // a group built in a local and committed on success
+        struct Group {
+            Buf x, y, z;
+            uint32_t cap = 0;
+        };
+        auto build = [](Group &target, uint32_t n) {
+            target = {};   // released first
+            Group g;
+            if (!g.x.alloc(n) || !g.y.alloc(n) || !g.z.alloc(n)) return false;
+            g.cap = n;
+            target = std::move(g);
+            return true;
+        };
+        FakeMem::reset();
+        Group target;
+        CHECK(build(target, 4) && target.cap == 4 && target.x.get() && target.z.get() && FakeMem::live == 3);
+        FakeMem::fail_at = FakeMem::allocs + 2;   // the second allocation of the rebuild
+        CHECK(!build(target, 16));
+        CHECK(!target.x.get() && !target.y.get() && !target.z.get() && target.cap == 0 && FakeMem::live == 0);
+        CHECK(build(target, 16) && target.cap == 16 && FakeMem::live == 3);
+    }
+    CHECK(FakeMem::live == 0);
+    {   // release: the block handed over, the destructor frees nothing
+        FakeMem::reset();
+        uint32_t *p;
+        {
+            Buf a;
+            CHECK(a.alloc(2));
+            p = a.release();
+            CHECK(p && !a.get() && a.size() == 0);
+        }
+        CHECK(FakeMem::live == 1 && FakeMem::frees == 0);
+        FakeMem::free(p);
+    }
+    CHECK(FakeMem::live == 0);
+}
+
 // wait_until (wait.hpp) under scripted probes: publish, timeout, peer failure, stream failure,
 // drained stream.
 static void test_wait() {
@@ -218,6 +314,7 @@ int main(int argc, char **argv) {
     test_kdtree();
     test_certificate();
     test_wait();
+    test_owned();
     test_codec(tmp);
     std::printf("host sanitize test: %s (%d failures)\n", failures ? "FAILED" : "ok", failures);
     return failures ? 1 : 0;
