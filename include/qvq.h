@@ -327,8 +327,12 @@ QVQ_API qvq_status qvq_update_kahan_split(qvq_ctx *ctx, const uint32_t *assign, 
  * device pointers and a hipStream_t on which it launches (NULL = the legacy null stream, so
  * work the caller queued on blocking streams is ordered before it; the engine's own queued work
  * is ordered before it on any stream) and synchronises that stream before returning.  d_assign
- * must be 4-byte aligned (QVQ_EINVAL otherwise); an unaligned raster takes a per-pixel kernel,
- * as does the host qvq_decode path for any alignment of its staging. */
+ * must be 4-byte aligned (QVQ_EINVAL otherwise).  The fast row kernels (ySize % 8 == 0) want
+ * d_rgb 8-byte and d_assign 16-byte aligned: a pointer without that takes the per-pixel kernel.
+ * d_codebook may have any alignment: the 16-bit codebook reads of the block-height 2, 4 and 8 row
+ * kernel need an even pointer only when the codebook stays in global memory (K*bw*bh*3 > 48 KB),
+ * and an odd one then takes the byte-reading row kernel.  Every route decodes the same bytes
+ * (qvq_host_decode_plan names the one taken). */
 QVQ_API qvq_status qvq_decode(qvq_ctx *ctx, const uint8_t *codebook, uint32_t K, const uint32_t *assign,
                               uint64_t nblocks, uint32_t xSize, uint32_t ySize, uint32_t bw, uint32_t bh, uint8_t *rgb);
 QVQ_API qvq_status qvq_decode_mse(qvq_ctx *ctx, const uint8_t *codebook, uint32_t K, const uint32_t *assign,
@@ -434,6 +438,27 @@ QVQ_API qvq_status qvq_host_exact_plan(uint32_t dim, uint32_t K, qvq_exact_plan 
  * the distortion). */
 typedef struct { uint32_t block, assign_blocks, iota_blocks, dist_blocks; } qvq_exact_grids;
 QVQ_API qvq_status qvq_host_exact_grids(qvq_exact_grids *out);
+/* The kernel a decode dispatches to (qvq_decode, qvq_decode_mse, qvq_decode_device): the plan
+ * launch_decode switches on (quant_amd/csrc/decode_plan.hpp), from the shape, K and what the
+ * device pointers lack in alignment (align_flags: 0 for the host entry points, whose staging is
+ * aligned).  For tests that want a given instantiation to run (tests/helpers/decode_cases.py). */
+enum { QVQ_DECODE_PIXELS = 0, QVQ_DECODE_ROWS = 1, QVQ_DECODE_ROWS_H = 2 };
+enum { QVQ_DECODE_RASTER_UNALIGNED = 1,   /* raster % 8 != 0 */
+       QVQ_DECODE_ORIG_UNALIGNED = 2,     /* an original is given and original % 8 != 0 */
+       QVQ_DECODE_INDEX_UNALIGNED = 4,    /* indices % 16 != 0 */
+       QVQ_DECODE_CODEBOOK_ODD = 8 };     /* codebook % 2 != 0 */
+typedef struct {
+    uint32_t kernel;        /* QVQ_DECODE_PIXELS: one thread per pixel; _ROWS: 8 pixels per thread, any block
+                               height; _ROWS_H: 8 pixels per thread, block height H and no overhang */
+    uint32_t H;             /* ROWS_H: 1, 2, 4 or 8; else 0 */
+    uint32_t lds;           /* ROWS, ROWS_H: the codebook is staged in LDS (K * bw * bh * 3 <= 48 KB) */
+    uint32_t coal;          /* ROWS_H: wave-contiguous stores (ySize % 512 == 0) */
+    uint32_t grid;          /* blocks of 256 threads */
+    uint32_t lds_bytes;     /* dynamic LDS of the launch */
+    uint64_t rounds;        /* trips of the grid-stride loop in the busiest block; >= 2 past the grid cap */
+} qvq_decode_plan;
+QVQ_API qvq_status qvq_host_decode_plan(uint32_t K, uint32_t xSize, uint32_t ySize, uint32_t bw, uint32_t bh,
+                                        uint32_t align_flags, qvq_decode_plan *out);
 /* The colour space's byte -> value table (Terms::v64, the values the reference computes):
  * out[b] = the value of byte b.  QVQ_EUNSUPPORTED for CIE1931. */
 QVQ_API qvq_status qvq_host_colorspace_values(int colorspace, double out[256]);

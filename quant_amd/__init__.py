@@ -46,6 +46,11 @@ class _ExactPlan(ctypes.Structure):
     _fields_ = [(f, ctypes.c_uint32) for f in ("kc", "chunks", "last_chunk", "templated", "tile_rows")]
 
 
+class _DecodePlan(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_uint32) for f in ("kernel", "H", "lds", "coal", "grid", "lds_bytes")] + \
+               [("rounds", ctypes.c_uint64)]
+
+
 class _ExactGrids(ctypes.Structure):
     _fields_ = [(f, ctypes.c_uint32) for f in ("block", "assign_blocks", "iota_blocks", "dist_blocks")]
 
@@ -63,6 +68,9 @@ class _IngestGrid(ctypes.Structure):
 PLAN_SEARCH_SMALL, PLAN_SEARCH_MF32, PLAN_SEARCH_WIDE, PLAN_SEARCH_VALU = 0, 1, 2, 3
 PLAN_RECHECK_MF32, PLAN_RECHECK_STAGED, PLAN_RECHECK_CHUNKED, PLAN_RECHECK_GLOBAL = 0, 1, 2, 3
 PLAN_UPDATE_RUNS, PLAN_UPDATE_SORTED, PLAN_UPDATE_LDS = 0, 1, 2
+# qvq_decode_plan enumerators and qvq_host_decode_plan's align_flags (qvq.h)
+DECODE_PIXELS, DECODE_ROWS, DECODE_ROWS_H = 0, 1, 2
+DECODE_RASTER_UNALIGNED, DECODE_ORIG_UNALIGNED, DECODE_INDEX_UNALIGNED, DECODE_CODEBOOK_ODD = 1, 2, 4, 8
 
 _lib = None
 EXPORTED = ["qvq_create", "qvq_destroy", "qvq_last_error", "qvq_version", "qvq_set_images",
@@ -76,7 +84,7 @@ EXPORTED = ["qvq_create", "qvq_destroy", "qvq_last_error", "qvq_version", "qvq_s
             "qvq_host_exact_grids", "qvq_set_vectors_device", "qvq_get_training_info", "qvq_get_ingest_ms",
             "qvq_host_colorspace_values", "qvq_host_classify", "qvq_host_ingest_grid", "qvq_get_vectors",
             "qvq_host_cie1931", "qvq_host_tile64_grid", "qvq_get_refine_reseeds", "qvq_host_row_error",
-            "qvq_host_reseed_far_key", "qvq_host_reseed_select", "qvq_host_reseed_grid"]
+            "qvq_host_reseed_far_key", "qvq_host_reseed_select", "qvq_host_reseed_grid", "qvq_host_decode_plan"]
 
 COMM_NONE, COMM_RCCL, COMM_HOST = 0, 1, 2
 REFINE_FRESH, REFINE_RESEED = 1, 2            # qvq_refine flags
@@ -134,6 +142,7 @@ def lib():
             "qvq_host_plan": ([u32, u32, u64, ctypes.POINTER(_Plan)], i),
             "qvq_host_exact_plan": ([u32, u32, ctypes.POINTER(_ExactPlan)], i),
             "qvq_host_exact_grids": ([ctypes.POINTER(_ExactGrids)], i),
+            "qvq_host_decode_plan": ([u32, u32, u32, u32, u32, u32, ctypes.POINTER(_DecodePlan)], i),
             "qvq_set_vectors_device": ([P, P, u64, u32, u32, P], i),
             "qvq_get_training_info": ([P, ctypes.POINTER(_TrainingInfo)], i),
             "qvq_get_ingest_ms": ([P, P], i),
@@ -511,6 +520,16 @@ def host_exact_plan(dim, K):
     p = _ExactPlan()
     _check(lib().qvq_host_exact_plan(int(dim), int(K), ctypes.byref(p)))
     return {f: int(getattr(p, f)) for f, _ in _ExactPlan._fields_}
+
+
+def host_decode_plan(K, xSize, ySize, bw, bh, align_flags=0):
+    """The kernel a decode of this shape dispatches to (qvq_host_decode_plan): a dict of the
+    qvq_decode_plan fields.  align_flags: the DECODE_*_UNALIGNED / DECODE_CODEBOOK_ODD bits of what
+    qvq_decode_device's pointers lack; 0 for the host entry points."""
+    p = _DecodePlan()
+    _check(lib().qvq_host_decode_plan(int(K), int(xSize), int(ySize), int(bw), int(bh), int(align_flags),
+                                      ctypes.byref(p)))
+    return {f: int(getattr(p, f)) for f, _ in _DecodePlan._fields_}
 
 
 def host_exact_grids():

@@ -36,6 +36,7 @@
 #include "byte_image.hpp"
 #include "cie1931.hpp"
 #include "common.hpp"
+#include "decode_plan.hpp"
 #include "exact_plan.hpp"
 #include "kdtree.hpp"
 #include "owned.hpp"
@@ -3932,6 +3933,31 @@ QVQ_API qvq_status qvq_host_exact_grids(qvq_exact_grids *out) {
     out->assign_blocks = EX_ASSIGN_GRID_CAP;
     out->iota_blocks = EX_IOTA_GRID_CAP;
     out->dist_blocks = EX_DIST_GRID_CAP;
+    return QVQ_OK;
+}
+
+QVQ_API qvq_status qvq_host_decode_plan(uint32_t K, uint32_t xSize, uint32_t ySize, uint32_t bw, uint32_t bh,
+                                        uint32_t align_flags, qvq_decode_plan *out) {
+    // the shapes check_decode_args lets through
+    if (!out || K == 0 || bw == 0 || bh == 0 || xSize == 0 || ySize == 0) return QVQ_EINVAL;
+    if ((uint64_t)ySize + bh - 1 > 0xFFFFFFFFull || (uint64_t)xSize + bw - 1 > 0xFFFFFFFFull) return QVQ_EINVAL;
+    if ((uint64_t)bw * bh * 3 > 0xFFFFFFFFull) return QVQ_EINVAL;
+    static_assert(QVQ_DECODE_RASTER_UNALIGNED == DEC_RASTER_UNALIGNED && QVQ_DECODE_ORIG_UNALIGNED == DEC_ORIG_UNALIGNED &&
+                      QVQ_DECODE_INDEX_UNALIGNED == DEC_INDEX_UNALIGNED && QVQ_DECODE_CODEBOOK_ODD == DEC_CODEBOOK_ODD &&
+                      QVQ_DECODE_PIXELS == DEC_PIXELS && QVQ_DECODE_ROWS == DEC_ROWS && QVQ_DECODE_ROWS_H == DEC_ROWS_H,
+                  "qvq.h's decode plan enumerators are decode_plan.hpp's");
+    if (align_flags & ~15u) return QVQ_EINVAL;
+    const DecodePlan dp = decode_plan(K, xSize, ySize, bw, bh, align_flags);   // the plan launch_decode switches on
+    qvq_decode_plan p;
+    std::memset(&p, 0, sizeof(p));
+    p.kernel = dp.kernel;
+    p.H = dp.H;
+    p.lds = dp.lds;
+    p.coal = dp.coal;
+    p.grid = dp.grid;
+    p.lds_bytes = dp.lds_bytes;
+    p.rounds = dp.rounds;
+    *out = p;
     return QVQ_OK;
 }
 

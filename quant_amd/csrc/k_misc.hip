@@ -5,6 +5,7 @@
 //   hi[d][k] (K*D) | lo[d][k] (K*D) | cnt[k] (K)
 // Workgroup slabs (update kernels): part[g][d][k] packed (hi << 32 | lo), part_cnt[g][k].
 #include "common.hpp"
+#include "decode_plan.hpp"
 #include "mfma_util.hpp"
 
 namespace qvq {
@@ -1161,7 +1162,8 @@ __global__ __launch_bounds__(256) void decode_rows_kernel(DecodeArgs a) {
 // column dx0 = x mod w of 8 / H consecutive blocks of one block column -- 3H contiguous bytes of
 // each block's code vector at byte 3 H dx0 -- so no per-pixel divisions: one vector load of the
 // 8 / H consecutive indices (16-byte aligned: hB = ys / H and 8q / H are multiples of 8 / H),
-// 16-bit codebook reads from LDS (3H is even for H >= 2), three dwordx2 stores.
+// 16-bit codebook reads (3H is even for H >= 2; LDS, or an even pointer in global memory: with an
+// odd one decode_plan.hpp sends the shape to decode_rows_kernel<false>), three dwordx2 stores.
 // COAL (ys % 512 == 0: a wave's 64 threads are 1536 contiguous output bytes of one raster row):
 // the wave stages its three 8-byte pieces per lane in LDS and stores the chunk lane-contiguously,
 // 512 bytes per store instruction (the direct stores have a 24-byte lane stride); the raport's
@@ -1314,45 +1316,34 @@ hipError_t launch_decode(hipStream_t s, const uint8_t *cb, uint32_t K, uint32_t 
     a.yspan = a.hB * h;
     a.overhang = a.yspan - ys;
     a.rgb = rgb, a.orig = orig, a.sqerr = (unsigned long long *)sqerr, a.bad = bad;
-    // the row kernels store (and read the original) in 8-byte pieces and load 8 / H indices per
-    // vector load: caller pointers (qvq_decode_device) without that alignment take the
-    // per-pixel kernel
-    const bool aligned = (uintptr_t)rgb % 8 == 0 && (!orig || (uintptr_t)orig % 8 == 0) && (uintptr_t)A % 16 == 0;
-    if (aligned && ys % 8 == 0 && (uint64_t)xs * ys < (1ull << 40)) {
-        const uint64_t items = (uint64_t)xs * (ys / 8);
-        const size_t cbB = (size_t)K * D;
-        const bool lds = cbB <= 48 * 1024;
-        // with the codebook staged in LDS, a block loops over several 256-item rounds (C3: 8192
-        // one-round blocks staged 100 MB of codebook copies for 67 MB of output)
-        constexpr uint64_t cap = 2048;
-        const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>((items + 255) / 256, lds ? cap : 1u << 16));
-        const size_t ldsB = lds ? (cbB + 15) & ~(size_t)15 : 0;
-        if (a.overhang == 0 && (h == 1 || h == 2 || h == 4 || h == 8)) {
-            // wave-contiguous output chunks need whole waves inside one raster row: 64 | ys / 8
-            const bool coal = (ys / 8) % 64 == 0;
-            const uint32_t soff = (uint32_t)ldsB;
-            const size_t lb = ldsB + (coal ? 4 * 1536 : 0);
-#define QVQ_DEC_H(HV)                                                                                                  \
-    if (h == HV) {                                                                                                     \
-        if (coal) {                                                                                                    \
-            if (lds) hipLaunchKernelGGL((decode_rows_h_kernel<HV, true, true>), dim3(grid), dim3(256), lb, s, a, soff); \
-            else hipLaunchKernelGGL((decode_rows_h_kernel<HV, false, true>), dim3(grid), dim3(256), lb, s, a, soff);    \
-        } else {                                                                                                       \
-            if (lds) hipLaunchKernelGGL((decode_rows_h_kernel<HV, true, false>), dim3(grid), dim3(256), lb, s, a, soff);\
-            else hipLaunchKernelGGL((decode_rows_h_kernel<HV, false, false>), dim3(grid), dim3(256), lb, s, a, soff);   \
-        }                                                                                                              \
+    // which kernel, its grid and LDS: decode_plan.hpp (pointers without the row kernels' alignment
+    // take the per-pixel kernel; an odd codebook outside LDS takes the byte-reading row kernel)
+    const uint32_t unaligned = ((uintptr_t)rgb % 8 ? DEC_RASTER_UNALIGNED : 0u) |
+                               (orig && (uintptr_t)orig % 8 ? DEC_ORIG_UNALIGNED : 0u) |
+                               ((uintptr_t)A % 16 ? DEC_INDEX_UNALIGNED : 0u) |
+                               ((uintptr_t)cb % 2 ? DEC_CODEBOOK_ODD : 0u);
+    const DecodePlan p = decode_plan(K, xs, ys, w, h, unaligned);
+    const dim3 grid(p.grid), block(DEC_THREADS);
+    const size_t lb = p.lds_bytes;
+    const uint32_t soff = p.stage_off;
+    if (p.kernel == DEC_ROWS_H) {
+#define QVQ_DEC_H(HV)                                                                                            \
+    if (p.H == HV) {                                                                                             \
+        if (p.coal) {                                                                                            \
+            if (p.lds) hipLaunchKernelGGL((decode_rows_h_kernel<HV, true, true>), grid, block, lb, s, a, soff);  \
+            else hipLaunchKernelGGL((decode_rows_h_kernel<HV, false, true>), grid, block, lb, s, a, soff);       \
+        } else {                                                                                                 \
+            if (p.lds) hipLaunchKernelGGL((decode_rows_h_kernel<HV, true, false>), grid, block, lb, s, a, soff); \
+            else hipLaunchKernelGGL((decode_rows_h_kernel<HV, false, false>), grid, block, lb, s, a, soff);      \
+        }                                                                                                        \
     }
-            QVQ_DEC_H(1) QVQ_DEC_H(2) QVQ_DEC_H(4) QVQ_DEC_H(8)
+        QVQ_DEC_H(1) QVQ_DEC_H(2) QVQ_DEC_H(4) QVQ_DEC_H(8)
 #undef QVQ_DEC_H
-        } else if (lds) {
-            hipLaunchKernelGGL(decode_rows_kernel<true>, dim3(grid), dim3(256), ldsB, s, a);
-        } else {
-            hipLaunchKernelGGL(decode_rows_kernel<false>, dim3(grid), dim3(256), 0, s, a);
-        }
+    } else if (p.kernel == DEC_ROWS) {
+        if (p.lds) hipLaunchKernelGGL(decode_rows_kernel<true>, grid, block, lb, s, a);
+        else hipLaunchKernelGGL(decode_rows_kernel<false>, grid, block, 0, s, a);
     } else {
-        const uint64_t npix = (uint64_t)xs * ys;
-        const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>((npix + 255) / 256, 1u << 16));
-        hipLaunchKernelGGL(decode_pixels_kernel, dim3(grid), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(decode_pixels_kernel, grid, block, 0, s, a);
     }
     return hipGetLastError();
 }
