@@ -36,6 +36,10 @@ public:
     void loadFromFile(const std::string &path);
     size_t sizeInBits();
 
+    // LBG: the reference's quantizer.  MEDIAN_CUT: the engine's median cut (qvq_median_cut, qvq.h);
+    // LBG_MEDIAN_CUT: the same refined by up to 100 Lloyd iterations stopped by eps.  Both take
+    // NORMAL and SCALED rasters and throw std::runtime_error for CIE1931 (no exact mode); ABC throws
+    // "quantizer not implemented".  The enumerator given is recorded in `quantizer`.
     static std::pair<CompressedImage, CompressionRaport> compress(const RGBImage &image, Quantizers quantizer,
                                                                   ColorSpaces colorSpace, int blockWidth,
                                                                   int blockHeight, VectorType eps, int N);

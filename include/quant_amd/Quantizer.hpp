@@ -30,3 +30,10 @@ QuantizerPtr getQuantizer(Quantizers);
 // iteration's centroid step the empty cells take rows of the worst cells (QVQ_REFINE_RESEED; byte
 // images only, needs maxIters > 0: std::invalid_argument otherwise).  (0, false) is getQuantizer(LBG).
 QuantizerPtr getRefinedLBGQuantizer(size_t maxIters, bool fresh, bool reseed = false);
+// Median cut on the device (qvq_median_cut, include/qvq.h: the rule is written there; the reference
+// names MEDIAN_CUT and LBG_MEDIAN_CUT and implements neither, so getQuantizer keeps giving nullptr
+// for them).  quantize(trainingSet, n, eps) cuts to 2^n boxes; with refineIters > 0 or fresh it then
+// runs qvq_refine as a warm start from the median-cut codebook (eps the stop rule, the flags as
+// given).  reseed needs refineIters > 0 (std::invalid_argument otherwise).  Byte images only: any
+// other training set throws std::runtime_error with the engine's message.
+QuantizerPtr getMedianCutQuantizer(size_t refineIters = 0, bool fresh = false, bool reseed = false);

@@ -285,6 +285,43 @@ QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start /*
  * NULL / 0).  QVQ_ESTATE before any qvq_refine on the context. */
 QVQ_API qvq_status qvq_get_refine_reseeds(qvq_ctx *ctx, uint64_t *out, uint32_t cap, uint32_t *iters);
 
+/*
+ * Median cut on the device: a codebook of K = 2^bits code vectors by cutting boxes of rows at the
+ * median of their widest component; with qvq_refine (C_start = this call's codebook) behind it, the
+ * textbook alternative to split-LBG.  The reference names the quantizer (MEDIAN_CUT) and has none
+ * to match: this text is the rule.  One rank's byte path: N rows of dim real components; pad
+ * components take no part.  u[row][d] = (int8)code + 128 is the ordinal of a row's code byte; both
+ * byte colour spaces order their values by it.
+ *
+ * A[row] = 0.  For level l = 1 .. bits, half = 2^(l-1), for every box b < half:
+ *   1. n_b = the rows with A = b; lo_d, hi_d = the minimum and maximum of u[.][d] over them;
+ *   2. axis = the d with the largest hi_d - lo_d, on equal ranges the lowest d;
+ *   3. n_b = 0 or hi_axis = lo_axis (range 0): the box is not cut, its rows keep b and box
+ *      b + half stays empty;
+ *   4. else h[v] = the box's rows with u[.][axis] = v, cum(v) = sum of h[w] over w <= v; t = the v in
+ *      [lo_axis, hi_axis - 1] that minimises |2 cum(v) - n_b|, on ties the lowest.  Rows with
+ *      u[.][axis] > t take A = b + half, the others (a row at t included) keep b.  Both children
+ *      are non-empty by construction.
+ * cuts[l-1] = the boxes cut at level l (bits entries; may be NULL).
+ * After the last level: assign = A; codebook[k] = the centroid of box k by qvq_update's exact-sum
+ * rule (an empty box: the zero vector); distortion = the mean squared error of (codebook, A), as
+ * updateDistortion (closed form from the boxes' sums); qvq_assign_device points at A.  bits = 0 is
+ * legal: one box, its centroid the mean.  Everything before the centroids is integer minima,
+ * maxima and counts: exact, whatever order the device takes the rows in.
+ * (qvq_host_median_cut_axis and qvq_host_median_cut_select are steps 2 and 4 on the host.)
+ *
+ * Errors, in this order: QVQ_ESTATE without a training set; QVQ_EINVAL for bits > 20;
+ * QVQ_EUNSUPPORTED for an exact-mode set; QVQ_EUNSUPPORTED with any communicator joined (a
+ * sharded median cut needs the boxes' minima and maxima over every rank's rows, a min/max reduce
+ * the host communicator does not have).  An error leaves the context as it was.  Like qvq_assign, a
+ * successful call ends qvq_refine's C_start == NULL continuation (QVQ_ESTATE); a later qvq_lbg on
+ * the context returns what it returned before.  Outputs (caller-owned host memory, any may be
+ * NULL) are written only after the bounded wait has succeeded.  Under qvq_set_timing(-1)
+ * qvq_get_timings reports per level the two row passes in assign_ms and the rest in other_ms.
+ */
+QVQ_API qvq_status qvq_median_cut(qvq_ctx *ctx, uint32_t bits, double *codebook, uint32_t *assign,
+                                  double *distortion, uint32_t *cuts);
+
 /* Single steps over the current training set, for tests and benchmarks.
  * qvq_assign: nearest code vector of every row for codebook C (K x dim fp64, host),
  *   with the same MFMA/VALU search + fp64 recheck + kd-tree tie resolution as qvq_lbg.
@@ -496,6 +533,33 @@ QVQ_API qvq_status qvq_host_reseed_select(const uint64_t *E, const uint64_t *n, 
  * than block * blocks rows take the kernel's grid-stride loop a second time. */
 typedef struct { uint32_t block, blocks; } qvq_reseed_grid;
 QVQ_API qvq_status qvq_host_reseed_grid(qvq_reseed_grid *out);
+/* qvq_median_cut's rule on the host (quant_amd/csrc/median_cut_rule.hpp, the text the kernels run).
+ * qvq_host_median_cut_axis: the cut axis of a box from its per-component minima lo and maxima hi
+ * (dim entries each).  qvq_host_median_cut_select: the cut t of a box of n rows from its 256-bin
+ * histogram on the axis, whose ordinals span [lo, hi], lo < hi <= 255 (QVQ_EINVAL otherwise). */
+QVQ_API qvq_status qvq_host_median_cut_axis(const uint32_t *lo, const uint32_t *hi, uint32_t dim, uint32_t *axis);
+QVQ_API qvq_status qvq_host_median_cut_select(const uint32_t *hist, uint32_t lo, uint32_t hi, uint64_t n, uint32_t *t);
+/* One median-cut level of `boxes` boxes (a power of two: level l has 2^(l-1)) over n rows of dim
+ * components: the variant each of its two row passes takes and their launch shape
+ * (quant_amd/csrc/median_cut_plan.hpp, the function the launchers switch on).  A pass privatises its
+ * per-box state in a block's LDS; boxes that do not fit are cut into *_groups groups of
+ * *_group_boxes boxes, each group with blocks of its own that read every row's label and take their
+ * boxes' rows; past 16 groups the pass goes straight to global memory (*_lds = 0, *_groups = 0).  A
+ * lane per row, `block` lanes per block, at most *_cap blocks per group: more than block * cap rows
+ * take a pass's grid-stride loop a second time.  The ranges pass also applies the previous level's
+ * cuts; the pass after the last level runs the same loop without ranges (one group, cap 768). */
+typedef struct {
+    uint32_t range_lds;    /* ranges pass: 1 the boxes' minima and maxima (2 * dim words a box) are privatised in LDS */
+    uint32_t hist_lds;     /* histogram pass: 1 the boxes' bins (256 words a box) are privatised in LDS */
+    uint32_t full_hist;    /* 1: the per-(box, dim) histograms in one pass replace both (never: 0) */
+    uint32_t block;
+    uint32_t range_cap, hist_cap;     /* blocks per group at most */
+    uint32_t range_grid, hist_grid;   /* blocks per group launched for n rows */
+    uint32_t lds_words;    /* 32-bit words of LDS a block privatises in */
+    uint32_t range_groups, hist_groups;
+    uint32_t range_group_boxes, hist_group_boxes;
+} qvq_median_cut_plan;
+QVQ_API qvq_status qvq_host_median_cut_plan(uint32_t dim, uint32_t boxes, uint64_t n, qvq_median_cut_plan *out);
 /* The engine's bounded-wait policy (quant_amd/csrc/wait.hpp) driven by scripted probes, for
  * tests: scenario 0 the work publishes after ~5 ms; 1 it never does, no communicator; 2 it
  * never does, a healthy communicator; 3 the communicator reports an error after ~5 ms; 4 the

@@ -64,6 +64,12 @@ class _IngestGrid(ctypes.Structure):
     _fields_ = [(f, ctypes.c_uint32) for f in ("block", "blocks")]
 
 
+class _MedianCutPlan(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_uint32) for f in ("range_lds", "hist_lds", "full_hist", "block", "range_cap",
+                                                "hist_cap", "range_grid", "hist_grid", "lds_words", "range_groups",
+                                                "hist_groups", "range_group_boxes", "hist_group_boxes")]
+
+
 # qvq_plan enumerators (qvq.h)
 PLAN_SEARCH_SMALL, PLAN_SEARCH_MF32, PLAN_SEARCH_WIDE, PLAN_SEARCH_VALU = 0, 1, 2, 3
 PLAN_RECHECK_MF32, PLAN_RECHECK_STAGED, PLAN_RECHECK_CHUNKED, PLAN_RECHECK_GLOBAL = 0, 1, 2, 3
@@ -84,7 +90,9 @@ EXPORTED = ["qvq_create", "qvq_destroy", "qvq_last_error", "qvq_version", "qvq_s
             "qvq_host_exact_grids", "qvq_set_vectors_device", "qvq_get_training_info", "qvq_get_ingest_ms",
             "qvq_host_colorspace_values", "qvq_host_classify", "qvq_host_ingest_grid", "qvq_get_vectors",
             "qvq_host_cie1931", "qvq_host_tile64_grid", "qvq_get_refine_reseeds", "qvq_host_row_error",
-            "qvq_host_reseed_far_key", "qvq_host_reseed_select", "qvq_host_reseed_grid", "qvq_host_decode_plan"]
+            "qvq_host_reseed_far_key", "qvq_host_reseed_select", "qvq_host_reseed_grid", "qvq_host_decode_plan",
+            "qvq_median_cut", "qvq_host_median_cut_plan", "qvq_host_median_cut_axis",
+            "qvq_host_median_cut_select"]
 
 COMM_NONE, COMM_RCCL, COMM_HOST = 0, 1, 2
 REFINE_FRESH, REFINE_RESEED = 1, 2            # qvq_refine flags
@@ -157,6 +165,10 @@ def lib():
             "qvq_host_reseed_far_key": ([u32, u32, ctypes.POINTER(u64)], i),
             "qvq_host_reseed_select": ([P, P, P, u32, P, P, ctypes.POINTER(u32)], i),
             "qvq_host_reseed_grid": ([ctypes.POINTER(_IngestGrid)], i),   # qvq_reseed_grid: the same two fields
+            "qvq_median_cut": ([P, u32, P, P, P, P], i),
+            "qvq_host_median_cut_plan": ([u32, u32, u64, ctypes.POINTER(_MedianCutPlan)], i),
+            "qvq_host_median_cut_axis": ([P, P, u32, ctypes.POINTER(u32)], i),
+            "qvq_host_median_cut_select": ([P, u32, u32, u64, ctypes.POINTER(u32)], i),
         }
         for name, (args, res) in sig.items():
             if os.environ.get("QVQ_LIB") and not hasattr(L, name):
@@ -352,6 +364,17 @@ class Engine:
         return out, A, float(d[0]), {"iters": it, "stop": int(inf[1]), "changed": [int(x) for x in chg[:it]],
                                      "distortion": [float(x) for x in trace[:it]],
                                      "reseeded": [int(x) for x in seeds[:it]]}
+
+    def median_cut(self, bits, want_assign=True):
+        """Median cut to 2**bits boxes on the device (qvq_median_cut, the rule in qvq.h): (codebook,
+        labels or None, distortion, cuts), cuts[l] the boxes cut at level l + 1.  One rank's byte
+        path.  The codebook is a warm start for refine(C=...); refine(C=None) cannot continue from it."""
+        K = 1 << bits
+        C, d = np.empty((K, self.dim), np.float64), np.zeros(1, np.float64)
+        A = np.empty(self.n, np.uint32) if want_assign else None
+        cuts = np.zeros(max(bits, 1), np.uint32)
+        _check(lib().qvq_median_cut(self._h, bits, _p(C), _p(A) if want_assign else None, _p(d), _p(cuts)), self._h)
+        return C, A, float(d[0]), [int(x) for x in cuts[:bits]]
 
     def refine_reseeds(self):
         """The seeds the last refine() placed in each iteration (qvq_get_refine_reseeds)."""
@@ -571,6 +594,35 @@ def host_reseed_grid():
     return {f: int(getattr(g, f)) for f, _ in _IngestGrid._fields_}
 
 
+def host_median_cut_plan(dim, boxes, n):
+    """One median-cut level of `boxes` boxes over n rows of dim components (qvq_host_median_cut_plan):
+    a dict of the qvq_median_cut_plan fields."""
+    p = _MedianCutPlan()
+    _check(lib().qvq_host_median_cut_plan(int(dim), int(boxes), int(n), ctypes.byref(p)))
+    return {f: int(getattr(p, f)) for f, _ in _MedianCutPlan._fields_}
+
+
+def host_median_cut_axis(lo, hi):
+    """The cut axis of a box from its per-component minima and maxima (qvq_host_median_cut_axis)."""
+    lo = np.ascontiguousarray(lo, np.uint32).ravel()
+    hi = np.ascontiguousarray(hi, np.uint32).ravel()
+    assert lo.size == hi.size
+    axis = ctypes.c_uint32()
+    _check(lib().qvq_host_median_cut_axis(_p(lo), _p(hi), lo.size, ctypes.byref(axis)))
+    return axis.value
+
+
+def host_median_cut_select(hist, lo, hi, n=None):
+    """The cut t of a box from its 256-bin histogram on the axis (qvq_host_median_cut_select); n
+    defaults to the histogram's total."""
+    hist = np.ascontiguousarray(hist, np.uint32).ravel()
+    assert hist.size == 256
+    t = ctypes.c_uint32()
+    _check(lib().qvq_host_median_cut_select(_p(hist), int(lo), int(hi), int(hist.sum()) if n is None else int(n),
+                                            ctypes.byref(t)))
+    return t.value
+
+
 def host_row_error(x, c, colorspace=SCALED):
     """The quantised per-row error of QVQ_REFINE_RESEED (qvq_host_row_error): values x against code vector c."""
     x = np.ascontiguousarray(x, np.float64).ravel()
@@ -717,6 +769,34 @@ class LBGQuantizer(AbstractQuantizer):
         res = self._engine.lbg(int(n), eps)
         if self._refine_iters > 0 or self._fresh:
             res = self._engine.refine(max_iters=self._refine_iters, eps=eps, fresh=self._fresh,
+                                      reseed=self._reseed)[:3]
+        return res
+
+
+class MedianCutQuantizer(AbstractQuantizer):
+    """Median cut on the MI355X engine (Engine.median_cut), optionally refined: the reference's
+    MEDIAN_CUT (refine_iters = 0) and LBG_MEDIAN_CUT (refine_iters > 0) names.  getQuantizer keeps
+    returning None for both, as the reference does."""
+
+    def __init__(self, device=0, refine_iters=0, fresh=False, reseed=False):
+        """refine_iters > 0 or fresh: Lloyd iterations warm-started from the median-cut codebook,
+        stopped by eps (Engine.refine with C); reseed needs refine_iters > 0."""
+        if reseed and int(refine_iters) <= 0:
+            raise QVQError(1, "reseed needs refine_iters > 0")
+        self._device = device
+        self._engine = None
+        self._refine_iters = int(refine_iters)
+        self._fresh = bool(fresh)
+        self._reseed = bool(reseed)
+
+    def quantize(self, trainingSet, n, eps):
+        if self._engine is None:
+            self._engine = Engine(self._device)
+        dev = getattr(trainingSet, "is_cuda", False)
+        self._engine.set_vectors(trainingSet if dev else np.asarray(trainingSet, np.float64))
+        res = self._engine.median_cut(int(n))[:3]
+        if self._refine_iters > 0 or self._fresh:
+            res = self._engine.refine(C=res[0], max_iters=self._refine_iters, eps=eps, fresh=self._fresh,
                                       reseed=self._reseed)[:3]
         return res
 

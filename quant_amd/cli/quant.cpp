@@ -2,7 +2,8 @@
 // (src/main.cpp:42-113, no Boost):
 //
 //   quant FILE -o OUT [-n bits=8] [-e eps=1e-6] [-w width=2] [-h height=2] [-r raport=0]
-//                     [-q quantizer=0 (LBG)] [-c colorspace=1 (SCALED)] [--device N]
+//                     [-q quantizer=0 (LBG; 1 median cut, 2 median cut + Lloyd)] [-c colorspace=1 (SCALED)]
+//                     [--device N]
 //                     [--refine N=0] [--fresh] [--reseed]
 //
 // FILE.ppm -> OUT.quant compresses, FILE.quant -> OUT.ppm decompresses, FILE.ppm -> OUT.ppm
@@ -61,7 +62,8 @@ const char *kHelp =
     "  --file arg             File to compress/decompress\n"
     "  -o [ --saveto ] arg    Save to\n"
     "  -r arg (=0)            Print raport to std::out\n"
-    "  -q [ --quantizer ] arg (=0) Pick quantizer\n"
+    "  -q [ --quantizer ] arg (=0) Pick quantizer: 0 LBG, 1 median cut, 2 median cut refined by\n"
+    "                         up to 100 Lloyd iterations (stopped by -e); NORMAL and SCALED only\n"
     "  -c [ --colorspace ] arg (=1) Pick ColorSpace\n"
     "  --device arg (=0)      HIP device of the engine (MI355X build)\n"
     "  --refine arg (=0)      Lloyd iterations at the final codebook size (LBG, stopped by -e)\n"

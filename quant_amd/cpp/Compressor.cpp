@@ -122,6 +122,22 @@ std::tuple<std::vector<Vector>, std::vector<size_t>, VectorType> quantize_raster
     std::vector<double> C(K * D);
     std::vector<uint32_t> A(N);
     double distortion = 0;
+    const bool refined = opt.maxIters > 0 || opt.fresh;
+    if (refined && opt.maxIters > 0xFFFFFFFFull) throw std::runtime_error("compress: too many refinement iterations");
+    if (opt.medianCut) {   // median cut, then the refinement as a warm start from its codebook
+        if (n > 20) throw std::runtime_error("compress: bits must be <= 20");
+        EngineHandle::check(qvq_median_cut(ctx, (uint32_t)n, C.data(), A.data(), &distortion, nullptr), "qvq_median_cut");
+        if (refined) {
+            const std::vector<double> start = C;
+            EngineHandle::check(qvq_refine(ctx, (uint32_t)K, start.data(), (uint32_t)opt.maxIters, eps,
+                                           (opt.fresh ? QVQ_REFINE_FRESH : 0u) | (opt.reseed ? QVQ_REFINE_RESEED : 0u),
+                                           C.data(), A.data(), &distortion, nullptr, nullptr, nullptr),
+                                "qvq_refine");
+        }
+        std::vector<Vector> codebook(K, Vector(D));
+        for (size_t k = 0; k < K; k++) std::copy(C.begin() + k * D, C.begin() + (k + 1) * D, codebook[k].begin());
+        return std::make_tuple(std::move(codebook), std::vector<size_t>(A.begin(), A.end()), distortion);
+    }
     EngineHandle::check(qvq_lbg(ctx, (uint32_t)n, eps, C.data(), A.data(), &distortion), "qvq_lbg");
     // qvq_lbg returns exact-sum centroids; the reference's are Kahan sums (src/Quantizer.cpp:59-87),
     // at most a few ulps away.  Only a component within a few ulps of a point where
@@ -130,9 +146,7 @@ std::tuple<std::vector<Vector>, std::vector<size_t>, VectorType> quantize_raster
     // are integers, whose Kahan sums are exact).  This substitution belongs to the unrefined
     // reference path only: a refined codebook has no reference value to match and is converted to
     // bytes as qvq_refine returns it.
-    const bool refined = opt.maxIters > 0 || opt.fresh;
     if (refined) {
-        if (opt.maxIters > 0xFFFFFFFFull) throw std::runtime_error("compress: too many refinement iterations");
         EngineHandle::check(qvq_refine(ctx, (uint32_t)K, nullptr, (uint32_t)opt.maxIters, eps,
                                        (opt.fresh ? QVQ_REFINE_FRESH : 0u) | (opt.reseed ? QVQ_REFINE_RESEED : 0u),
                                        C.data(), A.data(), &distortion, nullptr, nullptr, nullptr),
@@ -187,6 +201,15 @@ std::pair<CompressedImage, CompressionRaport> CompressedImage::compress(const RG
     const auto t0 = std::chrono::system_clock::now();
     if (quantizer == Quantizers::LBG && engine_takes_raster(colorSpace, false)) {
         std::tie(codebook, assigned, distortion) = quantize_raster(image, colorSpace, blockWidth, blockHeight, eps, N);
+    } else if (quantizer == Quantizers::MEDIAN_CUT || quantizer == Quantizers::LBG_MEDIAN_CUT) {
+        // the engine's median cut from the raster; LBG_MEDIAN_CUT refines it with up to 100 Lloyd
+        // iterations stopped by eps (MAX_IT of the reference's LBGIterate, src/Quantizer.cpp)
+        if (colorSpace == ColorSpaces::CIE1931)
+            throw std::runtime_error("compress: median cut has no exact mode (CIE1931 values are not byte images)");
+        quant_amd::RefineOptions opt;
+        opt.medianCut = true;
+        opt.maxIters = quantizer == Quantizers::LBG_MEDIAN_CUT ? 100 : 0;
+        std::tie(codebook, assigned, distortion) = quantize_raster(image, colorSpace, blockWidth, blockHeight, eps, N, opt);
     } else {
         QuantizerPtr q = getQuantizer(quantizer);
         if (!q) throw std::runtime_error("compress: quantizer not implemented");
@@ -198,9 +221,9 @@ std::pair<CompressedImage, CompressionRaport> CompressedImage::compress(const RG
                            elapsed);
 }
 
-// The caller's quantizer over the image's blocks.  The engine's own LBG quantizers (getQuantizer,
-// getRefinedLBGQuantizer) train straight from the raster as the enum overload does, with their
-// refinement; any other quantizer gets the host-built vectors.
+// The caller's quantizer over the image's blocks.  The engine's own quantizers (getQuantizer,
+// getRefinedLBGQuantizer, getMedianCutQuantizer) train straight from the raster as the enum overload
+// does, with their refinement; any other quantizer gets the host-built vectors.
 std::pair<CompressedImage, CompressionRaport> CompressedImage::compress(const RGBImage &image,
                                                                         AbstractQuantizer &quantizer,
                                                                         ColorSpaces colorSpace, int blockWidth,
@@ -212,8 +235,14 @@ std::pair<CompressedImage, CompressionRaport> CompressedImage::compress(const RG
     VectorType distortion = 0;
     const auto t0 = std::chrono::system_clock::now();
     quant_amd::RefineOptions opt;
-    if (quant_amd::engine_lbg_options(quantizer, opt) &&
-        engine_takes_raster(colorSpace, opt.maxIters > 0 || opt.fresh)) {
+    Quantizers recorded = Quantizers::LBG;
+    if (quant_amd::engine_median_cut_options(quantizer, opt) &&
+        (colorSpace == ColorSpaces::NORMAL || colorSpace == ColorSpaces::SCALED)) {
+        recorded = opt.maxIters > 0 || opt.fresh ? Quantizers::LBG_MEDIAN_CUT : Quantizers::MEDIAN_CUT;
+        std::tie(codebook, assigned, distortion) =
+            quantize_raster(image, colorSpace, blockWidth, blockHeight, eps, N, opt);
+    } else if (quant_amd::engine_lbg_options(quantizer, opt) &&
+               engine_takes_raster(colorSpace, opt.maxIters > 0 || opt.fresh)) {
         std::tie(codebook, assigned, distortion) =
             quantize_raster(image, colorSpace, blockWidth, blockHeight, eps, N, opt);
     } else {
@@ -221,8 +250,8 @@ std::pair<CompressedImage, CompressionRaport> CompressedImage::compress(const RG
             quantizer.quantize(getBlocksAsVectorsFromImage(image, blockWidth, blockHeight, cs), (size_t)N, eps);
     }
     const std::chrono::duration<double> elapsed = std::chrono::system_clock::now() - t0;
-    return pack_compressed(image, codebook, std::move(assigned), cs, colorSpace, Quantizers::LBG, blockWidth,
-                           blockHeight, elapsed);
+    return pack_compressed(image, codebook, std::move(assigned), cs, colorSpace, recorded, blockWidth, blockHeight,
+                           elapsed);
 }
 
 // The rest of src/Compressor.cpp:107-154 after the quantizer: the file's fields and the raport.

@@ -84,7 +84,53 @@ public:
     }
 };
 
+// Median cut on the engine (qvq_median_cut), then optionally qvq_refine warm-started from its codebook.
+class HipMedianCutQuantizer : public AbstractQuantizer {
+    size_t maxIters_ = 0;
+    bool fresh_ = false, reseed_ = false;
+
+public:
+    HipMedianCutQuantizer(size_t maxIters, bool fresh, bool reseed) : maxIters_(maxIters), fresh_(fresh), reseed_(reseed) {}
+    quant_amd::RefineOptions options() const { return {maxIters_, fresh_, reseed_, true}; }
+    std::tuple<std::vector<Vector>, std::vector<size_t>, VectorType> quantize(const std::vector<Vector> &trainingSet,
+                                                                              size_t n, VectorType eps) override {
+        using quant_amd::EngineHandle;
+        if (trainingSet.empty()) throw std::runtime_error("median cut quantize: empty training set");
+        if (n > 20) throw std::runtime_error("median cut quantize: bits must be <= 20");
+        const size_t N = trainingSet.size(), D = trainingSet[0].size();
+        std::vector<double> flat(N * D);
+        for (size_t i = 0; i < N; i++) {
+            if (trainingSet[i].size() != D) throw std::runtime_error("median cut quantize: vectors of different sizes");
+            std::copy(trainingSet[i].begin(), trainingSet[i].end(), flat.begin() + i * D);
+        }
+        qvq_ctx *ctx = EngineHandle::get();
+        EngineHandle::check(qvq_set_vectors(ctx, flat.data(), N, (uint32_t)D), "qvq_set_vectors");
+        const size_t K = (size_t)1 << n;
+        std::vector<double> C(K * D);
+        std::vector<uint32_t> A(N);
+        double distortion = 0;
+        EngineHandle::check(qvq_median_cut(ctx, (uint32_t)n, C.data(), A.data(), &distortion, nullptr), "qvq_median_cut");
+        if (maxIters_ > 0 || fresh_) {
+            if (maxIters_ > 0xFFFFFFFFull) throw std::runtime_error("median cut quantize: too many refinement iterations");
+            const std::vector<double> start = C;
+            EngineHandle::check(qvq_refine(ctx, (uint32_t)K, start.data(), (uint32_t)maxIters_, eps,
+                                           (fresh_ ? QVQ_REFINE_FRESH : 0u) | (reseed_ ? QVQ_REFINE_RESEED : 0u),
+                                           C.data(), A.data(), &distortion, nullptr, nullptr, nullptr),
+                                "qvq_refine");
+        }
+        std::vector<Vector> codebook(K, Vector(D));
+        for (size_t k = 0; k < K; k++) std::copy(C.begin() + k * D, C.begin() + (k + 1) * D, codebook[k].begin());
+        return std::make_tuple(std::move(codebook), std::vector<size_t>(A.begin(), A.end()), distortion);
+    }
+};
+
 }  // namespace
+
+bool quant_amd::engine_median_cut_options(const AbstractQuantizer &q, RefineOptions &out) {
+    const HipMedianCutQuantizer *h = dynamic_cast<const HipMedianCutQuantizer *>(&q);
+    if (h) out = h->options();
+    return h != nullptr;
+}
 
 bool quant_amd::engine_lbg_options(const AbstractQuantizer &q, RefineOptions &out) {
     const HipLBGQuantizer *h = dynamic_cast<const HipLBGQuantizer *>(&q);
@@ -100,4 +146,9 @@ QuantizerPtr getQuantizer(Quantizers q) {
 QuantizerPtr getRefinedLBGQuantizer(size_t maxIters, bool fresh, bool reseed) {
     if (reseed && maxIters == 0) throw std::invalid_argument("getRefinedLBGQuantizer: reseed needs maxIters > 0");
     return QuantizerPtr(new HipLBGQuantizer(maxIters, fresh, reseed));
+}
+
+QuantizerPtr getMedianCutQuantizer(size_t refineIters, bool fresh, bool reseed) {
+    if (reseed && refineIters == 0) throw std::invalid_argument("getMedianCutQuantizer: reseed needs refineIters > 0");
+    return QuantizerPtr(new HipMedianCutQuantizer(refineIters, fresh, reseed));
 }

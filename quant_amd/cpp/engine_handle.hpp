@@ -21,7 +21,10 @@ struct RefineOptions {
     size_t maxIters = 0;
     bool fresh = false;
     bool reseed = false;
+    bool medianCut = false;   // the codebook starts from qvq_median_cut, and the refinement is a warm start from it
 };
 bool engine_lbg_options(const AbstractQuantizer &q, RefineOptions &out);
+// The same for the engine's median-cut quantizer (getMedianCutQuantizer): out.medianCut is set.
+bool engine_median_cut_options(const AbstractQuantizer &q, RefineOptions &out);
 
 }  // namespace quant_amd

@@ -459,6 +459,29 @@ hipError_t launch_reseed_select(hipStream_t s, const uint8_t *codes, uint32_t Dp
                                 const double *lut64, double *C, uint32_t K, const ReseedWork &w, uint64_t *pub);
 hipError_t launch_gather_codes(hipStream_t s, const uint8_t *codes, uint32_t Dp, const uint32_t *rows, uint32_t n,
                                uint8_t *out);
+// qvq_median_cut (k_mediancut.hip, median_cut_rule.hpp, median_cut_plan.hpp): scratch for K = 2^bits
+// boxes of D components in one allocation of mc_layout(K, D).total bytes (offsets in bytes).
+struct McWork {
+    uint32_t *cuts = nullptr;   // [32] boxes cut per level
+    uint4 *sel = nullptr;       // [K/2] per box of the level: axis, lo, hi on it, t (or: not cut)
+    uint32_t *lo = nullptr;     // [K][D] the boxes' minima of the row ordinals ...
+    uint32_t *hi = nullptr;     // ... and maxima
+    uint32_t *hist = nullptr;   // [K/2][256] the boxes' counts on their axis
+};
+struct McLayout {
+    uint64_t cuts = 0, sel = 0, lo = 0, hi = 0, hist = 0, total = 0;
+};
+McLayout mc_layout(uint32_t K, uint32_t D);
+McWork mc_work(uint8_t *base, uint32_t K, uint32_t D);
+// A call: init; per level l (half = 2^(l-1) boxes): rows(half_prev = half / 2, ranges), axis(half),
+// hist(half), cut(half, l); then rows(half_prev = K / 2, no ranges).  A holds the labels.
+hipError_t launch_mc_init(hipStream_t s, uint32_t D, const McWork &w);
+hipError_t launch_mc_rows(hipStream_t s, const uint8_t *codes, uint32_t Dp, uint32_t D, uint64_t N, uint32_t *A,
+                          uint32_t half_prev, bool ranges, const McWork &w);
+hipError_t launch_mc_axis(hipStream_t s, uint32_t boxes, uint32_t D, const McWork &w);
+hipError_t launch_mc_hist(hipStream_t s, const uint8_t *codes, uint32_t Dp, uint32_t D, uint64_t N, const uint32_t *A,
+                          uint32_t boxes, const McWork &w);
+hipError_t launch_mc_cut(hipStream_t s, uint32_t boxes, uint32_t D, uint32_t level, const McWork &w);
 // Host-resolved rows: A[rows[i]] = vals[i]; with xslab their terms move from the
 // provisional index (A before) to the new one (move_row_terms).
 hipError_t launch_fix_rows(hipStream_t s, const uint8_t *codes, uint32_t Dp, uint32_t D, uint32_t *A,

@@ -39,6 +39,8 @@
 #include "decode_plan.hpp"
 #include "exact_plan.hpp"
 #include "kdtree.hpp"
+#include "median_cut_plan.hpp"
+#include "median_cut_rule.hpp"
 #include "owned.hpp"
 #include "qvq.h"
 #include "reseed_rule.hpp"
@@ -293,6 +295,12 @@ struct qvq_ctx {
     DevBuf<uint8_t> d_raster;            // qvq_set_images' raster upload buffer
     DevBuf<uint8_t> d_decode;            // qvq_decode's and qvq_get_vectors' scratch
     DevBuf<uint8_t> d_reseed;            // QVQ_REFINE_RESEED's scratch (reseed_layout)
+    // qvq_median_cut's scratch (mc_layout) for K boxes of D components: built in a local of this
+    // type and moved here once every allocation of the call has succeeded
+    struct MedianCut {
+        DevBuf<uint8_t> d_work;
+        uint32_t K = 0, D = 0;
+    } mc;
     DevBuf<uint64_t> d_vote;             // the ranks' small all-reduced decisions (qvq_lbg)
     PinnedBuf<uint64_t> h_vote;
     PinnedBuf<uint8_t> h_ar_stage;       // pinned staging of the host all-reduce
@@ -3632,6 +3640,104 @@ QVQ_API qvq_status qvq_get_refine_reseeds(qvq_ctx *ctx, uint64_t *out, uint32_t 
     return QVQ_OK;
 }
 
+// Median cut on the device (the rule in qvq.h and median_cut_rule.hpp).  Per level
+// two row passes over the code bytes (the ranges with the previous level's relabel, the histogram
+// on the chosen axis) and two per-box launches (axis, cut); one more row pass applies the last
+// level's cuts.  The centroids and the distortion term then come from the engine's exact sums:
+// run_update and the same-K finalize without tables, the form qvq_refine's reseed step uses.  The
+// labels live in d_A; nothing of qvq_lbg's state is touched but the buffers qvq_update uses too.
+QVQ_API qvq_status qvq_median_cut(qvq_ctx *ctx, uint32_t bits, double *codebook, uint32_t *assign, double *distortion,
+                                  uint32_t *cuts) {
+    if (!ctx) return QVQ_EINVAL;
+    GUARD(ctx);
+    if (ctx->ts.N == 0) return fail(ctx, QVQ_ESTATE, "no training set");
+    if (bits > 20) return fail(ctx, QVQ_EINVAL, "bits must be <= 20");
+    if (ctx->ts.exact) return fail(ctx, QVQ_EUNSUPPORTED, "median cut of an exact-mode training set is not supported");
+    if (ctx->comm || ctx->host_ar)
+        return fail(ctx, QVQ_EUNSUPPORTED, "median cut is not supported on a communicator (no min/max reduce)");
+    const auto t0 = std::chrono::steady_clock::now();
+    HIPCHK(hipSetDevice(ctx->dev));
+    const uint32_t K = 1u << bits, D = ctx->ts.D, Dp = ctx->ts.Dp;
+    const uint64_t N = ctx->ts.N, KD = (uint64_t)K * D;
+    qvq_status st = ensure_levels(ctx, std::max<uint32_t>(K, 2));
+    if (st != QVQ_OK) return st;
+    if (ctx->mc.K < K || ctx->mc.D != D) {
+        qvq_ctx::MedianCut mc;
+        HIPCHK(mc.d_work.alloc(mc_layout(K, D).total));
+        mc.K = K;
+        mc.D = D;
+        ctx->mc = std::move(mc);
+    }
+    const uint64_t cB = KD * 8, uB = 32 * sizeof(uint32_t);
+    HIPCHK(ctx->h_stage.ensure(cB + uB));
+    if (!ctx->rf.have_xsq) {   // sum ||x||^2 and the rows from the byte histogram, once per training set
+        uint64_t hist[256], n = 0;
+        HIPCHK(hipMemcpy(hist, ctx->d_hist, sizeof(hist), hipMemcpyDeviceToHost));
+        long double sq = 0;
+        for (int b = 0; b < 256; b++) {
+            sq += (long double)hist[b] * (long double)ctx->ts.terms.v64[b] * (long double)ctx->ts.terms.v64[b];
+            n += hist[b];
+        }
+        ctx->rf.xsq = (double)sq;
+        ctx->rf.rows = (double)(n / D);
+        ctx->rf.have_xsq = true;
+    }
+    ctx->rf.valid = false;
+    std::memset(&ctx->tm, 0, sizeof(ctx->tm));
+    ctx->tm.levels = (int)bits;
+    if ((st = clear_dirty_sums(ctx)) != QVQ_OK) return st;
+    const McWork w = mc_work(ctx->mc.d_work, ctx->mc.K, D);
+    const bool timed = ctx->timing_level == -1;   // each record idles the GPU ~6 us
+    uint32_t *const A = ctx->ts.d_A;
+    HIPCHK(launch_mc_init(ctx->stream, D, w));
+    for (uint32_t l = 1; l <= bits; l++) {
+        const uint32_t half = 1u << (l - 1);
+        if (timed) HIPCHK(hipEventRecord(ctx->ev[l - 1][0], ctx->stream));
+        HIPCHK(launch_mc_rows(ctx->stream, ctx->ts.d_codes, Dp, D, N, A, half / 2, true, w));
+        if (timed) HIPCHK(hipEventRecord(ctx->ev[l - 1][1], ctx->stream));
+        HIPCHK(launch_mc_axis(ctx->stream, half, D, w));
+        if (timed) HIPCHK(hipEventRecord(ctx->ev[l - 1][2], ctx->stream));
+        HIPCHK(launch_mc_hist(ctx->stream, ctx->ts.d_codes, Dp, D, N, A, half, w));
+        if (timed) HIPCHK(hipEventRecord(ctx->ev[l - 1][3], ctx->stream));
+        HIPCHK(launch_mc_cut(ctx->stream, half, D, l, w));
+    }
+    HIPCHK(launch_mc_rows(ctx->stream, ctx->ts.d_codes, Dp, D, N, A, K / 2, false, w));
+    if ((st = run_update(ctx, plan_level(ctx, K), A, K)) != QVQ_OK) return st;
+    FinArgs f = finalize_args(ctx, K, true);   // the centroids and the distortion term, no tables
+    const ReducedSums rs;
+    sums_args(ctx, f, &rs, true);
+    f.pub = ctx->h_ready.dev() + 4;
+    f.seq = ++ctx->seq;
+    if ((st = run_finalize(ctx, f)) != QVQ_OK) return st;
+    if (timed) HIPCHK(hipEventRecord(ctx->ev_end, ctx->stream));
+    // results land in context-owned pinned memory and reach the caller only after the bounded wait
+    uint8_t *stage = static_cast<uint8_t *>(ctx->h_stage);
+    HIPCHK(hipMemcpyAsync(stage, ctx->lv.d_C64_cent, cB, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(stage + cB, w.cuts, uB, hipMemcpyDeviceToHost, ctx->stream));
+    if ((st = wait_stream(ctx)) != QVQ_OK) return st;
+    std::atomic_thread_fence(std::memory_order_acquire);
+    const uint64_t tbits = ctx->h_ready[5];
+    double term;
+    std::memcpy(&term, &tbits, 8);
+    const double dist = std::max(0.0, (ctx->rf.xsq - term) / (ctx->rf.rows * (double)D));
+    if (codebook) std::memcpy(codebook, stage, cB);
+    if (cuts && bits) std::memcpy(cuts, stage + cB, bits * sizeof(uint32_t));
+    if (assign) HIPCHK(host_copy(ctx, assign, A, N * 4, hipMemcpyDeviceToHost));
+    if (distortion) *distortion = dist;
+    for (uint32_t l = 1; timed && l <= bits; l++) {
+        float r = 0, h = 0, whole = 0;
+        (void)hipEventSynchronize(ctx->ev_end);
+        (void)hipEventElapsedTime(&r, ctx->ev[l - 1][0], ctx->ev[l - 1][1]);
+        (void)hipEventElapsedTime(&h, ctx->ev[l - 1][2], ctx->ev[l - 1][3]);
+        (void)hipEventElapsedTime(&whole, ctx->ev[l - 1][0], l < bits ? ctx->ev[l][0] : ctx->ev_end);
+        ctx->tm.assign_ms[l - 1] = r + h;                          // the two row passes
+        ctx->tm.other_ms[l - 1] = std::max(0.f, whole - r - h);    // axis, cut; the last level: relabel, sums, finalize
+    }
+    (void)hipGetLastError();
+    ctx->tm.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return QVQ_OK;
+}
+
 // ---------------------------------------------------------------------------------------
 // Decode: CompressedImage::decompress (src/Compressor.cpp:156-165) as one device gather.
 // ---------------------------------------------------------------------------------------
@@ -4003,6 +4109,38 @@ QVQ_API qvq_status qvq_host_reseed_select(const uint64_t *E, const uint64_t *n, 
         if (rows_out) rows_out[j] = reseed_far_row(far[donors[j]]);
     }
     *m = cnt;
+    return QVQ_OK;
+}
+
+QVQ_API qvq_status qvq_host_median_cut_plan(uint32_t dim, uint32_t boxes, uint64_t n, qvq_median_cut_plan *out) {
+    if (!out || dim == 0 || dim > 64 || boxes == 0 || boxes > (1u << 19) || (boxes & (boxes - 1)) || n == 0) return QVQ_EINVAL;
+    const MedianCutPlan p = median_cut_plan(dim, boxes, n);
+    out->range_lds = p.range_lds;
+    out->hist_lds = p.hist_lds;
+    out->full_hist = p.full_hist;
+    out->block = p.block;
+    out->range_cap = p.range_cap;
+    out->hist_cap = p.hist_cap;
+    out->range_grid = p.range_grid;
+    out->hist_grid = p.hist_grid;
+    out->lds_words = p.lds_words;
+    out->range_groups = p.range_groups;
+    out->hist_groups = p.hist_groups;
+    out->range_group_boxes = p.range_group_boxes;
+    out->hist_group_boxes = p.hist_group_boxes;
+    return QVQ_OK;
+}
+
+QVQ_API qvq_status qvq_host_median_cut_axis(const uint32_t *lo, const uint32_t *hi, uint32_t dim, uint32_t *axis) {
+    if (!lo || !hi || !axis || dim == 0 || dim > 64) return QVQ_EINVAL;
+    uint32_t range;
+    *axis = mc_axis(lo, hi, dim, &range);
+    return QVQ_OK;
+}
+
+QVQ_API qvq_status qvq_host_median_cut_select(const uint32_t *hist, uint32_t lo, uint32_t hi, uint64_t n, uint32_t *t) {
+    if (!hist || !t || lo >= hi || hi > 255) return QVQ_EINVAL;
+    *t = mc_select(hist, lo, hi, n);
     return QVQ_OK;
 }
 
