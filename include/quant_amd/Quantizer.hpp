@@ -30,6 +30,15 @@ QuantizerPtr getQuantizer(Quantizers);
 // iteration's centroid step the empty cells take rows of the worst cells (QVQ_REFINE_RESEED; byte
 // images only, needs maxIters > 0: std::invalid_argument otherwise).  (0, false) is getQuantizer(LBG).
 QuantizerPtr getRefinedLBGQuantizer(size_t maxIters, bool fresh, bool reseed = false);
+// Split-LBG with Lloyd iterations at every level on the device (qvq_lbg_lloyd, include/qvq.h: the
+// textbook schedule, the rule is written there): after every split up to lloydIters iterations,
+// stopped by quantize()'s eps; reseed: the iterations reseed their empty cells (QVQ_LLOYD_RESEED,
+// and QVQ_REFINE_RESEED for the refinement).  With refineIters > 0 or fresh, qvq_refine then
+// continues at the final K as getRefinedLBGQuantizer's does.  lloydIters == 0 is
+// std::invalid_argument.  Byte images only: any other training set (CIE1931 values included) throws
+// std::runtime_error with the engine's message.  The codebook is converted to bytes as the engine
+// returns it: there is no reference value to match.
+QuantizerPtr getLloydLBGQuantizer(size_t lloydIters, bool reseed, size_t refineIters = 0, bool fresh = false);
 // Median cut on the device (qvq_median_cut, include/qvq.h: the rule is written there; the reference
 // names MEDIAN_CUT and LBG_MEDIAN_CUT and implements neither, so getQuantizer keeps giving nullptr
 // for them).  quantize(trainingSet, n, eps) cuts to 2^n boxes; with refineIters > 0 or fresh it then

@@ -54,8 +54,8 @@ enum { QVQ_CS_NORMAL = 0, QVQ_CS_SCALED = 1, QVQ_CS_CIE1931 = 2 };
 /* Per-level / per-call timings filled by qvq_get_timings (device ms from HIP events
  * recorded around each level's search kernel on the context's stream). */
 typedef struct {
-    int levels;                 /* split levels run by the last qvq_lbg */
-    double total_ms;            /* whole qvq_lbg, host wall */
+    int levels;                 /* split levels run by the last qvq_lbg (or qvq_lbg_lloyd, qvq_median_cut) */
+    double total_ms;            /* the whole call, host wall */
     double assign_ms[32];       /* device time of the assignment kernel per level (exact mode: wall time) */
     double update_ms[32];       /* device time of the centroid-sum kernel per level (exact mode: wall time) */
     double other_ms[32];        /* rest of the level: recheck, kd-tree ties, reduce, finalize + tables */
@@ -284,6 +284,51 @@ QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start /*
  * flag): the first min(cap, iterations) entries of out, *iters = the iterations (either may be
  * NULL / 0).  QVQ_ESTATE before any qvq_refine on the context. */
 QVQ_API qvq_status qvq_get_refine_reseeds(qvq_ctx *ctx, uint64_t *out, uint32_t cap, uint32_t *iters);
+
+/*
+ * Split-LBG with Lloyd iterations at every level: the textbook schedule the reference's README
+ * describes (after every split, iterate until the distortion settles) and its code does not run
+ * (qvq_lbg: one assignment per level).  The reference has none to match: this text is the rule.
+ *
+ * C^(0) = the mean of the rows, as qvq_lbg forms it.  For level l = 1 .. bits, K = 2^l, H = K / 2:
+ *   S[k] = C^(l-1)[k] * (double)(1 + 0.2) and S[k + H] = C^(l-1)[k] * (double)(1 - 0.2) for k < H:
+ *   fp64 products, qvq_lbg's split.
+ *   The level then runs qvq_refine's loop exactly as its contract words it, with C_0 = S, no A_0,
+ *   max_iters = iters, this eps, and QVQ_REFINE_RESEED iff QVQ_LLOYD_RESEED.  It is a warm start:
+ *   iteration 1 reports changed = N and takes no eps test; the stop order is qvq_refine's
+ *   (QVQ_STOP_FIXED, _EPS, _MAXIT).  The range check on C_start does not apply to S: the searches are
+ *   specified for |c| <= 1.2 vmax (qvq_assign), which is what qvq_lbg itself searches.
+ *   C^(l), A^(l), d^(l) = that loop's codebook (with its seeds, under the flag), assignment and
+ *   distortion.
+ * levels[l-1] (bits entries, may be NULL): iters and stop of the level's loop; changed, the rows
+ * changed in its last iteration; empty, the cells with no row under A^(l); seeds, the seeds placed
+ * in all of its iterations (0 without the flag); distortion = d^(l).
+ *
+ * Outputs (caller-owned host memory, any may be NULL): codebook 2^bits x dim, assign n u32 and
+ * distortion are C, A and d of the last level, written only after the bounded wait has succeeded;
+ * qvq_assign_device points at that assignment.  bits = 0 gives one cell, the mean, and no levels.
+ * A successful call leaves the state a C_start == NULL qvq_refine continues from (K = 2^bits); a
+ * later qvq_lbg returns what it returned before.  qvq_get_timings reports levels and total_ms, and
+ * 0 for the rest.  With iters = 1 and no flag a level is one assignment and one centroid step of
+ * the split codebook: qvq_lbg's level with exact-sum centroids (qvq_lbg's indices wherever the
+ * reference's Kahan sums and the exact sums give the same ones).
+ *
+ * Errors, in this order, each leaving the context as it was: QVQ_ESTATE without a training set;
+ * QVQ_EINVAL for bits > 20, for iters == 0, for !(eps >= 0), for an unknown flag; QVQ_EUNSUPPORTED
+ * for an exact-mode set, with any communicator joined (a sharded version needs qvq_refine's entry
+ * vote), and for the flag with 2^32 - 1 rows or more.
+ */
+enum { QVQ_LLOYD_RESEED = 1 };   /* flags */
+typedef struct {
+    uint32_t iters, stop;   /* iterations run at this level; QVQ_STOP_* of its last one */
+    uint64_t changed;       /* rows changed in the level's last iteration */
+    uint64_t empty;         /* cells with no row under the level's final assignment */
+    uint64_t seeds;         /* seeds placed at this level (0 without the flag) */
+    double distortion;      /* d of the level's last iteration */
+} qvq_lloyd_level;
+QVQ_API qvq_status qvq_lbg_lloyd(qvq_ctx *ctx, uint32_t bits, uint32_t iters, double eps, uint32_t flags,
+                                 double *codebook, uint32_t *assign, double *distortion,
+                                 qvq_lloyd_level *levels /* bits entries, may be NULL */);
 
 /*
  * Median cut on the device: a codebook of K = 2^bits code vectors by cutting boxes of rows at the

@@ -70,6 +70,11 @@ class _MedianCutPlan(ctypes.Structure):
                                                 "hist_groups", "range_group_boxes", "hist_group_boxes")]
 
 
+class _LloydLevel(ctypes.Structure):   # qvq_lloyd_level
+    _fields_ = [("iters", ctypes.c_uint32), ("stop", ctypes.c_uint32), ("changed", ctypes.c_uint64),
+                ("empty", ctypes.c_uint64), ("seeds", ctypes.c_uint64), ("distortion", ctypes.c_double)]
+
+
 # qvq_plan enumerators (qvq.h)
 PLAN_SEARCH_SMALL, PLAN_SEARCH_MF32, PLAN_SEARCH_WIDE, PLAN_SEARCH_VALU = 0, 1, 2, 3
 PLAN_RECHECK_MF32, PLAN_RECHECK_STAGED, PLAN_RECHECK_CHUNKED, PLAN_RECHECK_GLOBAL = 0, 1, 2, 3
@@ -92,10 +97,11 @@ EXPORTED = ["qvq_create", "qvq_destroy", "qvq_last_error", "qvq_version", "qvq_s
             "qvq_host_cie1931", "qvq_host_tile64_grid", "qvq_get_refine_reseeds", "qvq_host_row_error",
             "qvq_host_reseed_far_key", "qvq_host_reseed_select", "qvq_host_reseed_grid", "qvq_host_decode_plan",
             "qvq_median_cut", "qvq_host_median_cut_plan", "qvq_host_median_cut_axis",
-            "qvq_host_median_cut_select"]
+            "qvq_host_median_cut_select", "qvq_lbg_lloyd"]
 
 COMM_NONE, COMM_RCCL, COMM_HOST = 0, 1, 2
 REFINE_FRESH, REFINE_RESEED = 1, 2            # qvq_refine flags
+LLOYD_RESEED = 1                              # qvq_lbg_lloyd flags
 VECTORS_EXACT = 1                             # qvq_set_vectors_device flags
 MODE_NONE, MODE_BYTE, MODE_EXACT = 0, 1, 2    # qvq_training_info.mode
 STOP_FIXED, STOP_EPS, STOP_MAXIT = 0, 1, 2    # qvq_refine_info.stop
@@ -169,6 +175,7 @@ def lib():
             "qvq_host_median_cut_plan": ([u32, u32, u64, ctypes.POINTER(_MedianCutPlan)], i),
             "qvq_host_median_cut_axis": ([P, P, u32, ctypes.POINTER(u32)], i),
             "qvq_host_median_cut_select": ([P, u32, u32, u64, ctypes.POINTER(u32)], i),
+            "qvq_lbg_lloyd": ([P, u32, u32, ctypes.c_double, u32, P, P, P, P], i),
         }
         for name, (args, res) in sig.items():
             if os.environ.get("QVQ_LIB") and not hasattr(L, name):
@@ -364,6 +371,25 @@ class Engine:
         return out, A, float(d[0]), {"iters": it, "stop": int(inf[1]), "changed": [int(x) for x in chg[:it]],
                                      "distortion": [float(x) for x in trace[:it]],
                                      "reseeded": [int(x) for x in seeds[:it]]}
+
+    def lbg_lloyd(self, bits, iters, eps=1e-6, reseed=False, want_assign=True):
+        """Split-LBG with up to `iters` Lloyd iterations at every level, stopped by eps
+        (qvq_lbg_lloyd, the rule in qvq.h): (C, A or None, distortion, levels), levels[l] a dict of
+        level l + 1's iters, stop (STOP_*), changed (rows changed in its last iteration), empty
+        (cells without a row), seeds (placed at the level: 0 without reseed) and distortion.
+        reseed=True: every level's iterations reseed their empty cells (QVQ_LLOYD_RESEED).  One
+        rank's byte path.  refine(C=None) continues from the result."""
+        bits = int(bits)
+        K = 1 << bits
+        C, d = np.empty((K, self.dim), np.float64), np.zeros(1, np.float64)
+        A = np.empty(self.n, np.uint32) if want_assign else None
+        lv = (_LloydLevel * max(bits, 1))()
+        _check(lib().qvq_lbg_lloyd(self._h, bits, int(iters), float(eps), LLOYD_RESEED if reseed else 0, _p(C),
+                                   _p(A) if want_assign else None, _p(d), ctypes.cast(lv, ctypes.c_void_p)), self._h)
+        self._last_k = K
+        return C, A, float(d[0]), [{"iters": int(v.iters), "stop": int(v.stop), "changed": int(v.changed),
+                                    "empty": int(v.empty), "seeds": int(v.seeds), "distortion": float(v.distortion)}
+                                   for v in lv[:bits]]
 
     def median_cut(self, bits, want_assign=True):
         """Median cut to 2**bits boxes on the device (qvq_median_cut, the rule in qvq.h): (codebook,
@@ -748,17 +774,22 @@ class AbstractQuantizer:
 class LBGQuantizer(AbstractQuantizer):
     """LBGQuantizer (src/Quantizer.cpp:119-144) on the MI355X engine."""
 
-    def __init__(self, device=0, refine_iters=0, fresh=False, reseed=False):
+    def __init__(self, device=0, refine_iters=0, fresh=False, reseed=False, lloyd_iters=0):
         """refine_iters > 0: up to that many Lloyd iterations at the final K after the split
         levels, stopped by eps (Engine.refine); fresh: the indices of the returned codebook;
-        reseed: the iterations reseed their empty cells (needs refine_iters > 0)."""
-        if reseed and int(refine_iters) <= 0:
-            raise QVQError(1, "reseed needs refine_iters > 0")
+        lloyd_iters > 0: up to that many Lloyd iterations after every split, stopped by eps
+        (Engine.lbg_lloyd in place of Engine.lbg); reseed: the iterations reseed their empty cells
+        (needs refine_iters > 0 or lloyd_iters > 0)."""
+        if int(lloyd_iters) < 0:
+            raise QVQError(1, "lloyd_iters must be >= 0")
+        if reseed and int(refine_iters) <= 0 and int(lloyd_iters) <= 0:
+            raise QVQError(1, "reseed needs refine_iters > 0 or lloyd_iters > 0")
         self._device = device
         self._engine = None
         self._refine_iters = int(refine_iters)
         self._fresh = bool(fresh)
         self._reseed = bool(reseed)
+        self._lloyd_iters = int(lloyd_iters)
 
     def quantize(self, trainingSet, n, eps):
         if self._engine is None:
@@ -766,7 +797,10 @@ class LBGQuantizer(AbstractQuantizer):
         # a CUDA tensor goes straight through (no torch import here when handed numpy)
         dev = getattr(trainingSet, "is_cuda", False)
         self._engine.set_vectors(trainingSet if dev else np.asarray(trainingSet, np.float64))
-        res = self._engine.lbg(int(n), eps)
+        if self._lloyd_iters > 0:
+            res = self._engine.lbg_lloyd(int(n), self._lloyd_iters, eps, reseed=self._reseed)[:3]
+        else:
+            res = self._engine.lbg(int(n), eps)
         if self._refine_iters > 0 or self._fresh:
             res = self._engine.refine(max_iters=self._refine_iters, eps=eps, fresh=self._fresh,
                                       reseed=self._reseed)[:3]

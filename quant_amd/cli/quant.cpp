@@ -4,7 +4,7 @@
 //   quant FILE -o OUT [-n bits=8] [-e eps=1e-6] [-w width=2] [-h height=2] [-r raport=0]
 //                     [-q quantizer=0 (LBG; 1 median cut, 2 median cut + Lloyd)] [-c colorspace=1 (SCALED)]
 //                     [--device N]
-//                     [--refine N=0] [--fresh] [--reseed]
+//                     [--refine N=0] [--fresh] [--reseed] [--lloyd N=0]
 //
 // FILE.ppm -> OUT.quant compresses, FILE.quant -> OUT.ppm decompresses, FILE.ppm -> OUT.ppm
 // compresses and writes the decoded image (src/main.cpp:73-111); anything else prints "File
@@ -14,7 +14,10 @@
 // on the GPU through libquant_amd.so / libqvq.so.  --refine N runs up to N Lloyd iterations at the
 // final codebook size after the split levels (stopped by eps) and --fresh writes the indices of
 // the codebook in the file (getRefinedLBGQuantizer); with neither the output is the reference's.
-// --reseed (with --refine N > 0) lets the iterations reseed their empty cells (QVQ_REFINE_RESEED).
+// --lloyd N runs up to N Lloyd iterations after every split (stopped by eps), the textbook schedule
+// (getLloydLBGQuantizer, qvq_lbg_lloyd); --refine then continues from its result.
+// --reseed (with --refine N > 0 or --lloyd N > 0) lets the iterations reseed their empty cells
+// (QVQ_REFINE_RESEED, QVQ_LLOYD_RESEED).
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
@@ -48,7 +51,8 @@ struct Params {   // include/ProgramParameters.hpp:5-19, defaults of src/main.cp
     bool raport = false;
     int refine = 0;       // --refine: Lloyd iterations at the final K (0: none)
     bool fresh = false;   // --fresh: indices of the written codebook
-    bool reseed = false;  // --reseed: the refinement reseeds its empty cells
+    bool reseed = false;  // --reseed: the iterations reseed their empty cells
+    int lloyd = 0;        // --lloyd: Lloyd iterations at every level (0: qvq_lbg's one assignment per level)
     std::string file, saveto;
 };
 
@@ -68,7 +72,8 @@ const char *kHelp =
     "  --device arg (=0)      HIP device of the engine (MI355X build)\n"
     "  --refine arg (=0)      Lloyd iterations at the final codebook size (LBG, stopped by -e)\n"
     "  --fresh                Indices re-assigned to the written codebook\n"
-    "  --reseed               Empty cells reseeded from the worst cells (with --refine)\n";
+    "  --reseed               Empty cells reseeded from the worst cells (with --refine or --lloyd)\n"
+    "  --lloyd arg (=0)       Lloyd iterations after every split (LBG, stopped by -e)\n";
 
 bool parse_bool(const std::string &v) {   // program_options' bool values
     if (v == "1" || v == "true" || v == "yes" || v == "on") return true;
@@ -89,7 +94,7 @@ bool parse(int argc, char **argv, Params &p) {
     const std::map<std::string, std::string> names = {
         {"-n", "n"}, {"-e", "e"}, {"-w", "w"}, {"-h", "h"}, {"-o", "o"}, {"--saveto", "o"}, {"-r", "r"},
         {"-q", "q"}, {"--quantizer", "q"}, {"-c", "c"}, {"--colorspace", "c"}, {"--c", "c"}, {"--file", "file"},
-        {"--device", "device"}, {"--refine", "refine"}};
+        {"--device", "device"}, {"--refine", "refine"}, {"--lloyd", "lloyd"}};
     bool have_file = false, have_out = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
@@ -137,6 +142,10 @@ bool parse(int argc, char **argv, Params &p) {
             p.refine = parse_int(val, "--refine");
             if (p.refine < 0) throw std::invalid_argument("the argument ('" + val + "') for option '--refine' is invalid");
         }
+        else if (key == "lloyd") {
+            p.lloyd = parse_int(val, "--lloyd");
+            if (p.lloyd < 0) throw std::invalid_argument("the argument ('" + val + "') for option '--lloyd' is invalid");
+        }
         else if (key == "o") {
             p.saveto = val;
             have_out = true;
@@ -152,7 +161,10 @@ bool parse(int argc, char **argv, Params &p) {
         throw std::invalid_argument("options '--refine' and '--fresh' need the LBG quantizer");
     if (p.reseed && p.quantizer != (int)Quantizers::LBG)
         throw std::invalid_argument("option '--reseed' needs the LBG quantizer");
-    if (p.reseed && p.refine <= 0) throw std::invalid_argument("option '--reseed' needs '--refine' > 0");
+    if (p.lloyd > 0 && p.quantizer != (int)Quantizers::LBG)
+        throw std::invalid_argument("option '--lloyd' needs the LBG quantizer");
+    if (p.reseed && p.refine <= 0 && p.lloyd <= 0)
+        throw std::invalid_argument("option '--reseed' needs '--refine' > 0 or '--lloyd' > 0");
     return false;
 }
 
@@ -175,7 +187,8 @@ int main(int argc, char **argv) {
         auto run_compression = [&]() {   // src/main.cpp:76-84
             RGBImage img(par.file);
             QuantizerPtr refined;
-            if (par.refine > 0 || par.fresh) refined = getRefinedLBGQuantizer((size_t)par.refine, par.fresh, par.reseed);
+            if (par.lloyd > 0) refined = getLloydLBGQuantizer((size_t)par.lloyd, par.reseed, (size_t)par.refine, par.fresh);
+            else if (par.refine > 0 || par.fresh) refined = getRefinedLBGQuantizer((size_t)par.refine, par.fresh, par.reseed);
             auto result = refined ? CompressedImage::compress(img, *refined, (ColorSpaces)par.colorspace, par.width,
                                                               par.height, par.eps, par.n)
                                   : CompressedImage::compress(img, (Quantizers)par.quantizer,

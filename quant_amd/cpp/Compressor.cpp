@@ -87,7 +87,8 @@ size_t floor_log2(size_t n) {   // smallestPow2, src/Compressor.cpp:167-172
 
 // Colour spaces whose rasters qvq_set_images takes: NORMAL and SCALED on the byte path, CIE1931 as
 // an exact-mode set (tiled and converted on the device; the reference's own centroid bits, so no
-// Kahan substitution).  Exact mode has no qvq_refine: a refined quantizer keeps the host-built vectors.
+// Kahan substitution).  Exact mode has no qvq_refine and no qvq_lbg_lloyd: a refined or Lloyd
+// quantizer keeps the host-built vectors (and the engine then refuses the set).
 bool engine_takes_raster(ColorSpaces cs, bool refined) {
     return cs == ColorSpaces::NORMAL || cs == ColorSpaces::SCALED || (cs == ColorSpaces::CIE1931 && !refined);
 }
@@ -138,20 +139,27 @@ std::tuple<std::vector<Vector>, std::vector<size_t>, VectorType> quantize_raster
         for (size_t k = 0; k < K; k++) std::copy(C.begin() + k * D, C.begin() + (k + 1) * D, codebook[k].begin());
         return std::make_tuple(std::move(codebook), std::vector<size_t>(A.begin(), A.end()), distortion);
     }
-    EngineHandle::check(qvq_lbg(ctx, (uint32_t)n, eps, C.data(), A.data(), &distortion), "qvq_lbg");
+    if (opt.lloydIters > 0 && n > 20) throw std::runtime_error("compress: bits must be <= 20");
+    if (opt.lloydIters > 0xFFFFFFFFull) throw std::runtime_error("compress: too many Lloyd iterations per level");
+    if (opt.lloydIters > 0)   // Lloyd iterations at every level; the refinement, if any, continues from it
+        EngineHandle::check(qvq_lbg_lloyd(ctx, (uint32_t)n, (uint32_t)opt.lloydIters, eps, opt.reseed ? QVQ_LLOYD_RESEED : 0u,
+                                          C.data(), A.data(), &distortion, nullptr),
+                            "qvq_lbg_lloyd");
+    else
+        EngineHandle::check(qvq_lbg(ctx, (uint32_t)n, eps, C.data(), A.data(), &distortion), "qvq_lbg");
     // qvq_lbg returns exact-sum centroids; the reference's are Kahan sums (src/Quantizer.cpp:59-87),
     // at most a few ulps away.  Only a component within a few ulps of a point where
     // round((c - 128) * 255) changes can turn into another byte (src/ColorSpace.cpp:23-28), so the
     // reference's bits are fetched when any component sits that close (SCALED only: NORMAL values
     // are integers, whose Kahan sums are exact).  This substitution belongs to the unrefined
-    // reference path only: a refined codebook has no reference value to match and is converted to
-    // bytes as qvq_refine returns it.
+    // reference path only: a refined codebook, or one of qvq_lbg_lloyd, has no reference value to
+    // match and is converted to bytes as the engine returns it.
     if (refined) {
         EngineHandle::check(qvq_refine(ctx, (uint32_t)K, nullptr, (uint32_t)opt.maxIters, eps,
                                        (opt.fresh ? QVQ_REFINE_FRESH : 0u) | (opt.reseed ? QVQ_REFINE_RESEED : 0u),
                                        C.data(), A.data(), &distortion, nullptr, nullptr, nullptr),
                             "qvq_refine");
-    } else if (cs == ColorSpaces::SCALED && codebook_near_byte_flip(C)) {
+    } else if (opt.lloydIters == 0 && cs == ColorSpaces::SCALED && codebook_near_byte_flip(C)) {
         EngineHandle::check(qvq_update_kahan(ctx, A.data(), (uint32_t)K, C.data()), "qvq_update_kahan");
     }
     std::vector<Vector> codebook(K, Vector(D));
@@ -242,7 +250,7 @@ std::pair<CompressedImage, CompressionRaport> CompressedImage::compress(const RG
         std::tie(codebook, assigned, distortion) =
             quantize_raster(image, colorSpace, blockWidth, blockHeight, eps, N, opt);
     } else if (quant_amd::engine_lbg_options(quantizer, opt) &&
-               engine_takes_raster(colorSpace, opt.maxIters > 0 || opt.fresh)) {
+               engine_takes_raster(colorSpace, opt.maxIters > 0 || opt.fresh || opt.lloydIters > 0)) {
         std::tie(codebook, assigned, distortion) =
             quantize_raster(image, colorSpace, blockWidth, blockHeight, eps, N, opt);
     } else {

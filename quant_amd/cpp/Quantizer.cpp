@@ -45,19 +45,23 @@ namespace {
 // mode, the reference's arithmetic; non-finite values: std::runtime_error.
 // With refinement (getRefinedLBGQuantizer): qvq_refine continues at K = 2^n from the split levels'
 // result, up to maxIters Lloyd iterations stopped by eps, and with fresh returns the indices of the
-// returned codebook.
+// returned codebook.  With Lloyd iterations per level (getLloydLBGQuantizer): qvq_lbg_lloyd in place
+// of qvq_lbg.
 class HipLBGQuantizer : public AbstractQuantizer {
     size_t maxIters_ = 0;
     bool fresh_ = false, reseed_ = false;
+    size_t lloydIters_ = 0;
 
 public:
     HipLBGQuantizer() = default;
-    HipLBGQuantizer(size_t maxIters, bool fresh, bool reseed) : maxIters_(maxIters), fresh_(fresh), reseed_(reseed) {}
-    quant_amd::RefineOptions options() const { return {maxIters_, fresh_, reseed_}; }
+    HipLBGQuantizer(size_t maxIters, bool fresh, bool reseed, size_t lloydIters = 0)
+        : maxIters_(maxIters), fresh_(fresh), reseed_(reseed), lloydIters_(lloydIters) {}
+    quant_amd::RefineOptions options() const { return {maxIters_, fresh_, reseed_, false, lloydIters_}; }
     std::tuple<std::vector<Vector>, std::vector<size_t>, VectorType> quantize(const std::vector<Vector> &trainingSet,
                                                                               size_t n, VectorType eps) override {
         using quant_amd::EngineHandle;
         if (trainingSet.empty()) throw std::runtime_error("LBG quantize: empty training set");
+        if (lloydIters_ > 0 && n > 20) throw std::runtime_error("LBG quantize: bits must be <= 20");
         const size_t N = trainingSet.size(), D = trainingSet[0].size();
         std::vector<double> flat(N * D);
         for (size_t i = 0; i < N; i++) {
@@ -70,7 +74,13 @@ public:
         std::vector<double> C(K * D);
         std::vector<uint32_t> A(N);
         double distortion = 0;
-        EngineHandle::check(qvq_lbg(ctx, (uint32_t)n, eps, C.data(), A.data(), &distortion), "qvq_lbg");
+        if (lloydIters_ > 0xFFFFFFFFull) throw std::runtime_error("LBG quantize: too many Lloyd iterations per level");
+        if (lloydIters_ > 0)
+            EngineHandle::check(qvq_lbg_lloyd(ctx, (uint32_t)n, (uint32_t)lloydIters_, eps,
+                                              reseed_ ? QVQ_LLOYD_RESEED : 0u, C.data(), A.data(), &distortion, nullptr),
+                                "qvq_lbg_lloyd");
+        else
+            EngineHandle::check(qvq_lbg(ctx, (uint32_t)n, eps, C.data(), A.data(), &distortion), "qvq_lbg");
         if (maxIters_ > 0 || fresh_) {
             if (maxIters_ > 0xFFFFFFFFull) throw std::runtime_error("LBG quantize: too many refinement iterations");
             EngineHandle::check(qvq_refine(ctx, (uint32_t)K, nullptr, (uint32_t)maxIters_, eps,
@@ -146,6 +156,11 @@ QuantizerPtr getQuantizer(Quantizers q) {
 QuantizerPtr getRefinedLBGQuantizer(size_t maxIters, bool fresh, bool reseed) {
     if (reseed && maxIters == 0) throw std::invalid_argument("getRefinedLBGQuantizer: reseed needs maxIters > 0");
     return QuantizerPtr(new HipLBGQuantizer(maxIters, fresh, reseed));
+}
+
+QuantizerPtr getLloydLBGQuantizer(size_t lloydIters, bool reseed, size_t refineIters, bool fresh) {
+    if (lloydIters == 0) throw std::invalid_argument("getLloydLBGQuantizer: lloydIters must be > 0");
+    return QuantizerPtr(new HipLBGQuantizer(refineIters, fresh, reseed, lloydIters));
 }
 
 QuantizerPtr getMedianCutQuantizer(size_t refineIters, bool fresh, bool reseed) {

@@ -22,6 +22,8 @@ struct RefineOptions {
     bool fresh = false;
     bool reseed = false;
     bool medianCut = false;   // the codebook starts from qvq_median_cut, and the refinement is a warm start from it
+    size_t lloydIters = 0;    // > 0: qvq_lbg_lloyd with that many iterations per level in place of qvq_lbg (reseed
+                              // then holds for the levels too); the refinement, if any, continues from it
 };
 bool engine_lbg_options(const AbstractQuantizer &q, RefineOptions &out);
 // The same for the engine's median-cut quantizer (getMedianCutQuantizer): out.medianCut is set.

@@ -391,7 +391,8 @@ struct FinArgs {
     // the rows
     uint32_t children = 0;            // table rows per cell: 2 the split, 1 the same K, 0 no tables
     uint32_t Kpad = 0;                // table rows in all: rows children K .. Kpad - 1 are padding that never wins
-    const double *C_src = nullptr;    // sums == null: the codebook to prepare; measure: the codebook measured
+    const double *C_src = nullptr;    // sums == null: the codebook to prepare (children 2: K rows, split into
+                                      // C_next's 2K); measure: the codebook measured
     bool measure = false;
     double *C_cent = nullptr;         // the centroids [K][D]
     double *C_next = nullptr;         // the table rows' code vectors [children K][D]: the next search's codebook
@@ -424,6 +425,10 @@ hipError_t launch_count_changed(hipStream_t s, int num_cu, const uint32_t *A, co
 // a communicator).
 hipError_t launch_count_changed64(hipStream_t s, int num_cu, const uint32_t *A, const uint32_t *B, uint64_t N,
                                   uint64_t *out);
+// *out (mapped host memory) = the cells k < K without a row under the reduced sums, their ncopy copies
+// cstride apart added under the finalize's gate (qvq_lbg_lloyd's per-level count).
+hipError_t launch_count_empty(hipStream_t s, const uint64_t *sums, uint32_t K, uint32_t D, uint32_t ncopy,
+                              uint64_t cstride, const unsigned *gate, uint64_t *out);
 // qvq_refine's empty-cell reseed (k_reseed.hip, reseed_rule.hpp; QVQ_REFINE_RESEED): scratch for K
 // cells in one allocation of reseed_layout(K).total bytes (offsets in bytes; the donors' lists
 // hold K rounded up to a power of two).

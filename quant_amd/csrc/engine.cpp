@@ -3371,6 +3371,176 @@ QVQ_API qvq_status qvq_update_kahan_split(qvq_ctx *ctx, const uint32_t *assign, 
 // sums and one all-reduce per iteration, between the reduce and the finalize, carries both: the
 // codebook, the count and the distortion term -- all the stop rule reads -- are then the same on
 // every rank.  Several ranks first exchange their verdicts on the call (the entry vote).
+// One Lloyd run at K from the codebook in d_C64_cent: qvq_refine's loop as its contract words it
+// (DESIGN.md 3.11), which qvq_refine runs once and qvq_lbg_lloyd once per level (3.15).  The
+// caller has sized the buffers, cleared the iteration counters and the dirty sums, and holds
+// sum ||x||^2 and the norm.
+struct LloydRun {
+    // in
+    uint32_t K = 0, max_iters = 0;
+    double eps = 0;
+    bool fresh = false, reseed = false;
+    bool cont = false;           // A_0 is in d_A and d0 its distortion
+    bool tables_ready = false;   // C_0's tables, tile order and host copy (half 0) are enqueued already,
+                                 // under ctx->seq (qvq_lbg_lloyd's split); else made here from d_C64_cent
+    bool count_empty = false;    // every centroid step publishes its empty cells too (qvq_lbg_lloyd only)
+    double d0 = 0, xsq = 0, norm = 0;
+    uint64_t rows_all = 0;           // the rows of every rank
+    uint64_t *changed64 = nullptr;   // a communicator: the changed total behind the level's sums
+    ReseedWork rw;
+    uint64_t *changed = nullptr;     // the caller's traces (max_iters entries, may be null)
+    double *dist_trace = nullptr;
+    std::vector<uint64_t> *reseeds = nullptr;   // the seeds placed per iteration, appended (may be null)
+    // out
+    uint32_t iters = 0;   // t: C_t is the codebook (host_cb_of(ctx, t)), the assignment is in d_A
+    int stop = -1;
+    double d_last = 0;
+    uint64_t last_changed = 0, last_empty = 0, seeds = 0;   // the last iteration's; the seeds of all
+};
+static qvq_status lloyd_at_k(qvq_ctx *ctx, LloydRun &r) {
+    const uint32_t K = r.K, max_iters = r.max_iters, D = ctx->ts.D;
+    const bool fresh = r.fresh, reseed = r.reseed, cont = r.cont;
+    const double eps = r.eps, d0 = r.d0, xsq = r.xsq, norm = r.norm;
+    const uint64_t rows_all = r.rows_all;
+    uint64_t *const changed64 = r.changed64, *const changed = r.changed;
+    double *const dist_trace = r.dist_trace;
+    const ReseedWork &rw = r.rw;
+    qvq_status st;
+    const LevelPlan plan = plan_level(ctx, K);   // every iteration's
+    volatile uint64_t *h_pub = ctx->h_ready + 4;   // [4] rows changed, [5] the distortion term, [6] seeds placed, [7] empty cells
+    // the empty cells of the sums a centroid step is about to take (before its finalize clears
+    // their further copies and the gate)
+    auto count_empty = [&](const ReducedSums &rs) -> qvq_status {
+        if (r.count_empty)
+            HIPCHK(launch_count_empty(ctx->stream, ctx->lv.d_sums, K, D, rs.copies, rs.copies > 1 ? sums_cap_stride(ctx) : 0,
+                                      rs.gate, ctx->h_ready.dev() + 7));
+        return QVQ_OK;
+    };
+    // C_t's tables, tile order and host copy (t = 0, rs null: from the starting codebook; else the
+    // centroid step over the sums rs describes: copy 1, kd_reduce_kernel's moves, is added and then
+    // cleared under its gate), or without tables the distortion term of C_t under those sums
+    auto publish = [&](uint32_t t, bool tables, const ReducedSums *rs, unsigned *cnts, bool count) -> qvq_status {
+        if (rs && tables && (st = count_empty(*rs)) != QVQ_OK) return st;
+        FinArgs f = finalize_args(ctx, K, true);
+        if (rs) sums_args(ctx, f, rs, true);
+        f.C_src = ctx->lv.d_C64_cent;
+        if (tables) tables_args(ctx, f, 1, ctx->lv.d_C64_split, dev_cb_of(ctx, t), plan.prunable);
+        else f.measure = true;
+        if (count && changed64) f.changed64 = changed64;
+        else if (count) f.changed = ctx->d_counters + CHANGED_COUNTER;
+        f.clear_cnt = cnts;
+        f.pub = ctx->h_ready.dev() + 4;
+        f.seq = ++ctx->seq;
+        return run_finalize(ctx, f);
+    };
+    if (!r.tables_ready && (st = publish(0, true, nullptr, nullptr, false)) != QVQ_OK) return st;
+    // QVQ_REFINE_RESEED: the centroid step in four parts.  The cells' rows and the number of empty
+    // cells (before the finalize clears the sums' further copies and their gate); the centroids
+    // C_{t+1} alone, with the changed count and the distortion term (which the seeds leave as they
+    // are: an empty cell owns no row); the rows pass and the select, which seed C_{t+1} in place and
+    // publish the seeds placed; the tables, tile order and host copy from the seeded codebook, the
+    // form iteration 0 uses, which carries the ready number the host waits for.
+    auto publish_reseeded = [&](uint32_t t, const ReducedSums &rs, unsigned *cnts, bool count) -> qvq_status {
+        if ((st = count_empty(rs)) != QVQ_OK) return st;
+        HIPCHK(launch_reseed_count(ctx->stream, ctx->lv.d_sums, K, D, rs.copies,
+                                   rs.copies > 1 ? sums_cap_stride(ctx) : 0, rs.gate, rw));
+        FinArgs f = finalize_args(ctx, K, true);
+        sums_args(ctx, f, &rs, true);
+        if (count) f.changed = ctx->d_counters + CHANGED_COUNTER;
+        f.clear_cnt = cnts;
+        f.pub = ctx->h_ready.dev() + 4;
+        f.seq = ++ctx->seq;
+        qvq_status s = run_finalize(ctx, f);
+        if (s != QVQ_OK) return s;
+        HIPCHK(launch_reseed_rows(ctx->stream, ctx->ts.d_codes, ctx->ts.Dp, D, ctx->ts.N, ctx->ts.d_A, ctx->lv.d_C64_cent, K,
+                                  ctx->d_lut64, ctx->ts.cs == QVQ_CS_SCALED, rw));
+        HIPCHK(launch_reseed_select(ctx->stream, ctx->ts.d_codes, ctx->ts.Dp, D, ctx->ts.N, ctx->d_lut64, ctx->lv.d_C64_cent, K, rw,
+                                    ctx->h_ready.dev() + 6));
+        FinArgs g = finalize_args(ctx, K, true);
+        g.C_src = ctx->lv.d_C64_cent;
+        tables_args(ctx, g, 1, ctx->lv.d_C64_split, dev_cb_of(ctx, t), plan.prunable);
+        g.seq = ++ctx->seq;
+        return run_finalize(ctx, g);
+    };
+
+    uint32_t t = 0;        // iterations done: C_t is the codebook, A_t (t >= 1, or continuing) in d_A
+    int stop = -1;
+    bool have_A = cont, have_dprev = cont;
+    double d_prev = d0, d_last = d0;
+    // iteration t's published count and distortion, and the stop rule
+    auto absorb = [&]() {
+        std::atomic_thread_fence(std::memory_order_acquire);
+        const uint64_t chg = (t == 1 && !cont) ? rows_all : h_pub[0];
+        const uint64_t bits = h_pub[1];
+        double term;
+        std::memcpy(&term, &bits, 8);
+        const double d = std::max(0.0, (xsq - term) / norm);
+        const uint64_t seeds = reseed ? h_pub[2] : 0;
+        if (r.reseeds) r.reseeds->push_back(seeds);
+        r.seeds += seeds;
+        r.last_changed = chg;
+        if (r.count_empty) r.last_empty = h_pub[3];
+        if (changed) changed[t - 1] = chg;
+        if (dist_trace) dist_trace[t - 1] = d;
+        if (chg == 0 && seeds == 0) stop = QVQ_STOP_FIXED;
+        else if (have_dprev && std::fabs(d_prev - d) / d_prev <= eps) stop = QVQ_STOP_EPS;
+        else if (t == max_iters) stop = QVQ_STOP_MAXIT;
+        d_prev = d_last = d;
+        have_dprev = true;
+    };
+    for (;;) {
+        if (t == max_iters && !fresh) {   // the last iteration's results; nothing else is in flight
+            if ((st = wait_codebook(ctx, ctx->seq)) != QVQ_OK) return st;
+            absorb();
+            break;
+        }
+        const int slot = (int)(t & 1);
+        if (have_A) std::swap(ctx->ts.d_A, ctx->ts.d_A_alt);   // d_A_alt: A_t; d_A takes the search against C_t
+        LevelSums ls;   // (dropped with the search where the call stops without fresh)
+        if ((st = run_level(ctx, plan, K, slot, true, host_cb_of(ctx, t), ctx->seq, false, ls)) != QVQ_OK) return st;
+        if (t >= 1) absorb();   // (run_level waited for C_t)
+        else if (max_iters == 0) stop = QVQ_STOP_MAXIT;
+        // the sums of the assignment run_level just made, reduced into d_sums (a communicator:
+        // run_level has answered the kd-tree ties itself, the sums are one copy and there is no gate)
+        ReducedSums rs;
+        if (stop >= 0) {
+            if (fresh) {   // the search in flight is A* = assign(C_t): its sums, the distortion of (C_t, A*)
+                if ((st = reduce_level(ctx, K, slot, ls, rs)) != QVQ_OK) return st;
+                if ((st = all_reduce_sums(ctx, K)) != QVQ_OK) return st;   // every rank's rows of A*
+                if ((st = publish(t, false, &rs, ctx->d_counters + 2 * slot, false)) != QVQ_OK) return st;
+                if ((st = wait_codebook(ctx, ctx->seq)) != QVQ_OK) return st;
+                std::atomic_thread_fence(std::memory_order_acquire);
+                const uint64_t bits = h_pub[1];
+                double term;
+                std::memcpy(&term, &bits, 8);
+                d_last = std::max(0.0, (xsq - term) / norm);
+            } else {   // dropped: A_t stays the assignment
+                if (have_A) std::swap(ctx->ts.d_A, ctx->ts.d_A_alt);
+                if ((st = wait_stream(ctx)) != QVQ_OK) return st;
+            }
+            break;
+        }
+        if ((st = reduce_level(ctx, K, slot, ls, rs)) != QVQ_OK) return st;
+        if (changed64) {   // the level's sums and the rows changed over every rank: one collective
+            mark_sums1(ctx);   // (the slot lies in copy 1's range: cleared if the call ends before the finalize)
+            if (have_A) HIPCHK(launch_count_changed64(ctx->stream, ctx->num_cu, ctx->ts.d_A, ctx->ts.d_A_alt, ctx->ts.N, changed64));
+            if ((st = all_reduce(ctx, ctx->lv.d_sums, 2 * (uint64_t)K * D + K + 1, false)) != QVQ_OK) return st;
+        } else if (have_A) {
+            HIPCHK(launch_count_changed(ctx->stream, ctx->num_cu, ctx->ts.d_A, ctx->ts.d_A_alt, ctx->ts.N,
+                                        ctx->d_counters + CHANGED_COUNTER));
+        }
+        if (reseed) st = publish_reseeded(t + 1, rs, ctx->d_counters + 2 * slot, have_A);
+        else st = publish(t + 1, true, &rs, ctx->d_counters + 2 * slot, have_A || changed64);
+        if (st != QVQ_OK) return st;
+        have_A = true;
+        t++;
+    }
+    r.iters = t;
+    r.stop = stop;
+    r.d_last = d_last;
+    return QVQ_OK;
+}
+
 QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start, uint32_t max_iters, double eps,
                               uint32_t flags, double *codebook, uint32_t *assign, double *distortion,
                               uint64_t *changed, double *dist_trace, qvq_refine_info *info) {
@@ -3498,122 +3668,26 @@ QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start, u
     HIPCHK(hipMemsetAsync(ctx->d_counters + CHANGED_COUNTER, 0, 2 * sizeof(unsigned), ctx->stream));
     if ((st = clear_dirty_sums(ctx)) != QVQ_OK) return st;
     if (changed64) HIPCHK(hipMemsetAsync(changed64, 0, 8, ctx->stream));
-    const LevelPlan plan = plan_level(ctx, K);   // every iteration's
-    volatile uint64_t *h_pub = ctx->h_ready + 4;   // [4] rows changed, [5] the distortion term, [6] seeds placed
-    // C_t's tables, tile order and host copy (t = 0, rs null: from the starting codebook; else the
-    // centroid step over the sums rs describes: copy 1, kd_reduce_kernel's moves, is added and then
-    // cleared under its gate), or without tables the distortion term of C_t under those sums
-    auto publish = [&](uint32_t t, bool tables, const ReducedSums *rs, unsigned *cnts, bool count) -> qvq_status {
-        FinArgs f = finalize_args(ctx, K, true);
-        if (rs) sums_args(ctx, f, rs, true);
-        f.C_src = ctx->lv.d_C64_cent;
-        if (tables) tables_args(ctx, f, 1, ctx->lv.d_C64_split, dev_cb_of(ctx, t), plan.prunable);
-        else f.measure = true;
-        if (count && changed64) f.changed64 = changed64;
-        else if (count) f.changed = ctx->d_counters + CHANGED_COUNTER;
-        f.clear_cnt = cnts;
-        f.pub = ctx->h_ready.dev() + 4;
-        f.seq = ++ctx->seq;
-        return run_finalize(ctx, f);
-    };
-    if ((st = publish(0, true, nullptr, nullptr, false)) != QVQ_OK) return st;
-    // QVQ_REFINE_RESEED: the centroid step in four parts.  The cells' rows and the number of empty
-    // cells (before the finalize clears the sums' further copies and their gate); the centroids
-    // C_{t+1} alone, with the changed count and the distortion term (which the seeds leave as they
-    // are: an empty cell owns no row); the rows pass and the select, which seed C_{t+1} in place and
-    // publish the seeds placed; the tables, tile order and host copy from the seeded codebook, the
-    // form iteration 0 uses, which carries the ready number the host waits for.
-    auto publish_reseeded = [&](uint32_t t, const ReducedSums &rs, unsigned *cnts, bool count) -> qvq_status {
-        HIPCHK(launch_reseed_count(ctx->stream, ctx->lv.d_sums, K, D, rs.copies,
-                                   rs.copies > 1 ? sums_cap_stride(ctx) : 0, rs.gate, rw));
-        FinArgs f = finalize_args(ctx, K, true);
-        sums_args(ctx, f, &rs, true);
-        if (count) f.changed = ctx->d_counters + CHANGED_COUNTER;
-        f.clear_cnt = cnts;
-        f.pub = ctx->h_ready.dev() + 4;
-        f.seq = ++ctx->seq;
-        qvq_status s = run_finalize(ctx, f);
-        if (s != QVQ_OK) return s;
-        HIPCHK(launch_reseed_rows(ctx->stream, ctx->ts.d_codes, ctx->ts.Dp, D, ctx->ts.N, ctx->ts.d_A, ctx->lv.d_C64_cent, K,
-                                  ctx->d_lut64, ctx->ts.cs == QVQ_CS_SCALED, rw));
-        HIPCHK(launch_reseed_select(ctx->stream, ctx->ts.d_codes, ctx->ts.Dp, D, ctx->ts.N, ctx->d_lut64, ctx->lv.d_C64_cent, K, rw,
-                                    ctx->h_ready.dev() + 6));
-        FinArgs g = finalize_args(ctx, K, true);
-        g.C_src = ctx->lv.d_C64_cent;
-        tables_args(ctx, g, 1, ctx->lv.d_C64_split, dev_cb_of(ctx, t), plan.prunable);
-        g.seq = ++ctx->seq;
-        return run_finalize(ctx, g);
-    };
-
-    uint32_t t = 0;        // iterations done: C_t is the codebook, A_t (t >= 1, or continuing) in d_A
-    int stop = -1;
-    bool have_A = cont, have_dprev = cont;
-    double d_prev = d0, d_last = d0;
-    // iteration t's published count and distortion, and the stop rule
-    auto absorb = [&]() {
-        std::atomic_thread_fence(std::memory_order_acquire);
-        const uint64_t chg = (t == 1 && !cont) ? rows_all : h_pub[0];
-        const uint64_t bits = h_pub[1];
-        double term;
-        std::memcpy(&term, &bits, 8);
-        const double d = std::max(0.0, (xsq - term) / norm);
-        const uint64_t seeds = reseed ? h_pub[2] : 0;
-        ctx->rf.reseeds.push_back(seeds);
-        if (changed) changed[t - 1] = chg;
-        if (dist_trace) dist_trace[t - 1] = d;
-        if (chg == 0 && seeds == 0) stop = QVQ_STOP_FIXED;
-        else if (have_dprev && std::fabs(d_prev - d) / d_prev <= eps) stop = QVQ_STOP_EPS;
-        else if (t == max_iters) stop = QVQ_STOP_MAXIT;
-        d_prev = d_last = d;
-        have_dprev = true;
-    };
-    for (;;) {
-        if (t == max_iters && !fresh) {   // the last iteration's results; nothing else is in flight
-            if ((st = wait_codebook(ctx, ctx->seq)) != QVQ_OK) return st;
-            absorb();
-            break;
-        }
-        const int slot = (int)(t & 1);
-        if (have_A) std::swap(ctx->ts.d_A, ctx->ts.d_A_alt);   // d_A_alt: A_t; d_A takes the search against C_t
-        LevelSums ls;   // (dropped with the search where the call stops without fresh)
-        if ((st = run_level(ctx, plan, K, slot, true, host_cb_of(ctx, t), ctx->seq, false, ls)) != QVQ_OK) return st;
-        if (t >= 1) absorb();   // (run_level waited for C_t)
-        else if (max_iters == 0) stop = QVQ_STOP_MAXIT;
-        // the sums of the assignment run_level just made, reduced into d_sums (a communicator:
-        // run_level has answered the kd-tree ties itself, the sums are one copy and there is no gate)
-        ReducedSums rs;
-        if (stop >= 0) {
-            if (fresh) {   // the search in flight is A* = assign(C_t): its sums, the distortion of (C_t, A*)
-                if ((st = reduce_level(ctx, K, slot, ls, rs)) != QVQ_OK) return st;
-                if ((st = all_reduce_sums(ctx, K)) != QVQ_OK) return st;   // every rank's rows of A*
-                if ((st = publish(t, false, &rs, ctx->d_counters + 2 * slot, false)) != QVQ_OK) return st;
-                if ((st = wait_codebook(ctx, ctx->seq)) != QVQ_OK) return st;
-                std::atomic_thread_fence(std::memory_order_acquire);
-                const uint64_t bits = h_pub[1];
-                double term;
-                std::memcpy(&term, &bits, 8);
-                d_last = std::max(0.0, (xsq - term) / norm);
-            } else {   // dropped: A_t stays the assignment
-                if (have_A) std::swap(ctx->ts.d_A, ctx->ts.d_A_alt);
-                if ((st = wait_stream(ctx)) != QVQ_OK) return st;
-            }
-            break;
-        }
-        if ((st = reduce_level(ctx, K, slot, ls, rs)) != QVQ_OK) return st;
-        if (changed64) {   // the level's sums and the rows changed over every rank: one collective
-            mark_sums1(ctx);   // (the slot lies in copy 1's range: cleared if the call ends before the finalize)
-            if (have_A) HIPCHK(launch_count_changed64(ctx->stream, ctx->num_cu, ctx->ts.d_A, ctx->ts.d_A_alt, ctx->ts.N, changed64));
-            if ((st = all_reduce(ctx, ctx->lv.d_sums, cell_u64 + 1, false)) != QVQ_OK) return st;
-        } else if (have_A) {
-            HIPCHK(launch_count_changed(ctx->stream, ctx->num_cu, ctx->ts.d_A, ctx->ts.d_A_alt, ctx->ts.N,
-                                        ctx->d_counters + CHANGED_COUNTER));
-        }
-        if (reseed) st = publish_reseeded(t + 1, rs, ctx->d_counters + 2 * slot, have_A);
-        else st = publish(t + 1, true, &rs, ctx->d_counters + 2 * slot, have_A || changed64);
-        if (st != QVQ_OK) return st;
-        have_A = true;
-        t++;
-    }
+    LloydRun run;
+    run.K = K;
+    run.max_iters = max_iters;
+    run.eps = eps;
+    run.fresh = fresh;
+    run.reseed = reseed;
+    run.cont = cont;
+    run.d0 = d0;
+    run.xsq = xsq;
+    run.norm = norm;
+    run.rows_all = rows_all;
+    run.changed64 = changed64;
+    run.rw = rw;
+    run.changed = changed;
+    run.dist_trace = dist_trace;
+    run.reseeds = &ctx->rf.reseeds;
+    if ((st = lloyd_at_k(ctx, run)) != QVQ_OK) return st;
+    const uint32_t t = run.iters;
+    const int stop = run.stop;
+    const double d_last = run.d_last;
     // C_t as the finalize published it (t = 0: the starting codebook's copy)
     if (codebook) std::memcpy(codebook, host_cb_of(ctx, t), KD * 8);
     if (assign) HIPCHK(host_copy(ctx, assign, ctx->ts.d_A, ctx->ts.N * 4, hipMemcpyDeviceToHost));
@@ -3637,6 +3711,130 @@ QVQ_API qvq_status qvq_get_refine_reseeds(qvq_ctx *ctx, uint64_t *out, uint32_t 
     const uint32_t n = (uint32_t)ctx->rf.reseeds.size();
     for (uint32_t i = 0; i < std::min(n, cap); i++) out[i] = ctx->rf.reseeds[i];
     if (iters) *iters = n;
+    return QVQ_OK;
+}
+
+// One rank: sum ||x||^2 and the rows from the byte histogram, once per training set (rf.xsq, rf.rows).
+static qvq_status ensure_xsq(qvq_ctx *ctx) {
+    if (ctx->rf.have_xsq) return QVQ_OK;
+    uint64_t hist[256], n = 0;
+    HIPCHK(hipMemcpy(hist, ctx->d_hist, sizeof(hist), hipMemcpyDeviceToHost));
+    long double sq = 0;
+    for (int b = 0; b < 256; b++) {
+        sq += (long double)hist[b] * (long double)ctx->ts.terms.v64[b] * (long double)ctx->ts.terms.v64[b];
+        n += hist[b];
+    }
+    ctx->rf.xsq = (double)sq;
+    ctx->rf.rows = (double)(n / ctx->ts.D);
+    ctx->rf.have_xsq = true;
+    return QVQ_OK;
+}
+
+// Split-LBG with Lloyd iterations at every level (the rule in qvq.h).  The mean as
+// qvq_lbg forms it; then per level one finalize that writes the split of the codebook in
+// d_C64_cent with the level's tables, tile order and host copy (level 1: from the mean's sums, the
+// form qvq_lbg's first finalize has; later levels: from the codebook itself, which may hold
+// seeds), and qvq_refine's loop from those tables (lloyd_at_k).  The buffers are sized once for
+// 2^bits; no codebook crosses to the host and back between the levels.
+QVQ_API qvq_status qvq_lbg_lloyd(qvq_ctx *ctx, uint32_t bits, uint32_t iters, double eps, uint32_t flags,
+                                 double *codebook, uint32_t *assign, double *distortion, qvq_lloyd_level *levels) {
+    if (!ctx) return QVQ_EINVAL;
+    GUARD(ctx);
+    const bool reseed = (flags & QVQ_LLOYD_RESEED) != 0;
+    if (ctx->ts.N == 0) return fail(ctx, QVQ_ESTATE, "no training set");
+    if (bits > 20) return fail(ctx, QVQ_EINVAL, "bits must be <= 20");
+    if (iters == 0) return fail(ctx, QVQ_EINVAL, "iters must be >= 1");
+    if (!(eps >= 0)) return fail(ctx, QVQ_EINVAL, "eps must be >= 0");
+    if (flags & ~(uint32_t)QVQ_LLOYD_RESEED) return fail(ctx, QVQ_EINVAL, "unknown qvq_lbg_lloyd flags");
+    if (ctx->ts.exact) return fail(ctx, QVQ_EUNSUPPORTED, "qvq_lbg_lloyd of an exact-mode training set is not supported");
+    if (ctx->comm || ctx->host_ar) return fail(ctx, QVQ_EUNSUPPORTED, "qvq_lbg_lloyd is not supported on a communicator");
+    if (reseed && ctx->ts.N >= 0xFFFFFFFFull) return fail(ctx, QVQ_EUNSUPPORTED, "QVQ_LLOYD_RESEED takes fewer than 2^32 - 1 rows");
+    const auto t0 = std::chrono::steady_clock::now();
+    HIPCHK(hipSetDevice(ctx->dev));
+    const uint32_t Kmax = 1u << bits, D = ctx->ts.D;
+    qvq_status st = ensure_levels(ctx, std::max<uint32_t>(Kmax, 2));
+    if (st != QVQ_OK) return st;
+    if ((st = ensure_apool(ctx, ctx->ts, 2)) != QVQ_OK) return st;
+    if (reseed) HIPCHK(ctx->d_reseed.ensure(reseed_layout(Kmax).total));
+    if ((st = ensure_xsq(ctx)) != QVQ_OK) return st;
+    const double xsq = ctx->rf.xsq, norm = ctx->rf.rows * (double)D;
+    ctx->rf.valid = false;
+    std::memset(&ctx->tm, 0, sizeof(ctx->tm));
+    if ((st = clear_dirty_sums(ctx)) != QVQ_OK) return st;
+    // the mean's sums (the kernel also clears the level counters); the finalize that takes them
+    // leaves them cleared for the next quantize
+    HIPCHK(launch_mean_sums(ctx->stream, ctx->ts.Dp, ctx->ts.d_codes, ctx->ts.N, D, ctx->d_plut, ctx->d_mean, ctx->d_counters,
+                            N_COUNTERS, ctx->d_dist_part, ctx->d_hist, ctx->d_lut64));
+    std::vector<qvq_lloyd_level> lv(bits);
+    double d_last = 0;
+    uint32_t t_last = 0;   // the last level's iterations: its codebook is host_cb_of(ctx, t_last)
+    if (bits == 0) {   // one cell: the mean and its distortion term, no tables
+        FinArgs f = finalize_args(ctx, 1, true);
+        sums_args(ctx, f, nullptr, false);
+        f.pub = ctx->h_ready.dev() + 4;
+        f.seq = ++ctx->seq;
+        if ((st = run_finalize(ctx, f)) != QVQ_OK) return st;
+        HIPCHK(hipMemsetAsync(ctx->ts.d_A, 0, ctx->ts.N * 4, ctx->stream));
+        HIPCHK(ctx->h_stage.ensure((uint64_t)D * 8));
+        HIPCHK(hipMemcpyAsync(ctx->h_stage, ctx->lv.d_C64_cent, (uint64_t)D * 8, hipMemcpyDeviceToHost, ctx->stream));
+        if ((st = wait_stream(ctx)) != QVQ_OK) return st;
+        std::atomic_thread_fence(std::memory_order_acquire);
+        const uint64_t tbits = ctx->h_ready[5];
+        double term;
+        std::memcpy(&term, &tbits, 8);
+        d_last = std::max(0.0, (xsq - term) / norm);
+    }
+    for (uint32_t l = 1; l <= bits; l++) {
+        const uint32_t K = 1u << l, H = K / 2;
+        // S = the split of C^(l-1), its tables, tile order and host copy
+        FinArgs f = finalize_args(ctx, H, true);
+        if (l == 1) sums_args(ctx, f, nullptr, false);
+        else f.C_src = ctx->lv.d_C64_cent;
+        tables_args(ctx, f, 2, ctx->lv.d_C64_split, dev_cb_of(ctx, 0), plan_level(ctx, K).prunable);
+        f.seq = ++ctx->seq;
+        if ((st = run_finalize(ctx, f)) != QVQ_OK) return st;
+        // both iterations' counters and the changed total (the previous level may have dropped a search)
+        HIPCHK(hipMemsetAsync(ctx->d_counters, 0, 4 * sizeof(unsigned), ctx->stream));
+        HIPCHK(hipMemsetAsync(ctx->d_counters + CHANGED_COUNTER, 0, 2 * sizeof(unsigned), ctx->stream));
+        LloydRun run;
+        run.K = K;
+        run.max_iters = iters;
+        run.eps = eps;
+        run.reseed = reseed;
+        run.tables_ready = true;
+        run.count_empty = true;
+        run.xsq = xsq;
+        run.norm = norm;
+        run.rows_all = ctx->ts.N;
+        if (reseed) {
+            run.rw = reseed_work(ctx->d_reseed, K);
+            HIPCHK(hipMemsetAsync(run.rw.state, 0, 16, ctx->stream));
+        }
+        if ((st = lloyd_at_k(ctx, run)) != QVQ_OK) return st;
+        if ((st = clear_dirty_sums(ctx)) != QVQ_OK) return st;
+        qvq_lloyd_level &o = lv[l - 1];
+        o.iters = run.iters;
+        o.stop = (uint32_t)run.stop;
+        o.changed = run.last_changed;
+        o.empty = run.last_empty;
+        o.seeds = run.seeds;
+        o.distortion = run.d_last;
+        d_last = run.d_last;
+        t_last = run.iters;
+    }
+    // every wait above was bounded and has succeeded: the outputs
+    if (codebook) std::memcpy(codebook, bits ? (const void *)host_cb_of(ctx, t_last) : (const void *)ctx->h_stage.get(), (uint64_t)Kmax * D * 8);
+    if (assign) HIPCHK(host_copy(ctx, assign, ctx->ts.d_A, ctx->ts.N * 4, hipMemcpyDeviceToHost));
+    if (distortion) *distortion = d_last;
+    if (levels)
+        for (uint32_t l = 0; l < bits; l++) levels[l] = lv[l];
+    (void)hipGetLastError();
+    std::memset(&ctx->tm, 0, sizeof(ctx->tm));   // (run_level's per-slot host times are the iterations', not levels')
+    ctx->tm.levels = (int)bits;
+    ctx->tm.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ctx->rf.valid = true;   // qvq_refine may continue from here
+    ctx->rf.K = Kmax;
+    ctx->rf.dist = d_last;
     return QVQ_OK;
 }
 
@@ -3670,18 +3868,7 @@ QVQ_API qvq_status qvq_median_cut(qvq_ctx *ctx, uint32_t bits, double *codebook,
     }
     const uint64_t cB = KD * 8, uB = 32 * sizeof(uint32_t);
     HIPCHK(ctx->h_stage.ensure(cB + uB));
-    if (!ctx->rf.have_xsq) {   // sum ||x||^2 and the rows from the byte histogram, once per training set
-        uint64_t hist[256], n = 0;
-        HIPCHK(hipMemcpy(hist, ctx->d_hist, sizeof(hist), hipMemcpyDeviceToHost));
-        long double sq = 0;
-        for (int b = 0; b < 256; b++) {
-            sq += (long double)hist[b] * (long double)ctx->ts.terms.v64[b] * (long double)ctx->ts.terms.v64[b];
-            n += hist[b];
-        }
-        ctx->rf.xsq = (double)sq;
-        ctx->rf.rows = (double)(n / D);
-        ctx->rf.have_xsq = true;
-    }
+    if ((st = ensure_xsq(ctx)) != QVQ_OK) return st;
     ctx->rf.valid = false;
     std::memset(&ctx->tm, 0, sizeof(ctx->tm));
     ctx->tm.levels = (int)bits;

@@ -1,7 +1,8 @@
 // k_finalize.hip -- the finalize: exact centroids from the reduced sums, the split or (qvq_refine,
 // DESIGN.md 3.11) the same K, the next search's tables, tile order and host copy, the closed-form
-// distortion term; the same tables from a given codebook (qvq_assign); the rows that changed
-// between two assignments.  One kernel in five forms (FinArgs, common.hpp).
+// distortion term; the same tables from a given codebook (qvq_assign) or from its split
+// (qvq_lbg_lloyd); the rows that changed between two assignments; the cells
+// without a row.  One kernel in five forms (FinArgs, common.hpp).
 //
 // Sums layout as k_misc.hip: hi[d][k] (K*D) | lo[d][k] (K*D) | cnt[k] (K), u64; further copies
 // cstride apart (the mean's MEAN_COPIES; kd_reduce_kernel's moves of tie rows), added mod 2^64.
@@ -103,7 +104,8 @@ __device__ __host__ inline uint32_t fin_rows(const FinArgs &a) {
 
 // One (row j, component lane d) item; L lanes per row.  Row j < children K is a code vector:
 // child j / K of cell j mod K (split: factor 1.2, then 0.8; same K: the centroid itself), or
-// without sums row j of C_src; the rows above are padding.  Without tables row j < K is cell j.
+// without sums the same child of row j mod K of C_src (qvq_lbg_lloyd's split of a codebook that
+// holds seeds); the rows above are padding.  Without tables row j < K is cell j.
 // Returns the item's distortion term.
 __device__ inline double finalize_item(const FinDev &a, uint32_t j, uint32_t d, uint32_t L, uint32_t ncopy) {
     const uint32_t K = a.K, D = a.D;
@@ -125,7 +127,8 @@ __device__ inline double finalize_item(const FinDev &a, uint32_t j, uint32_t d, 
                 reinterpret_cast<uint32_t *>(a.host_cb + 2ull * K * D)[k] =
                     s.cnt > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)s.cnt;
         } else {
-            v = a.C_src[(uint64_t)j * D + d];
+            v = a.C_src[(uint64_t)k * D + d];   // (same K: k = j)
+            if (a.children == 2) v *= j < K ? (double)(1 + 0.2) : (double)(1 - 0.2);
         }
     }
     if (a.children && j < fin_rows(a)) write_tables(a, j, d, L, v, j < codes);
@@ -264,6 +267,33 @@ __global__ __launch_bounds__(CHG_THREADS) void count_changed_kernel(const uint32
 
 constexpr uint32_t FIN_ONE_BLOCK_ROWS = 64;   // split rows: K <= 32
 
+// The cells without a row under a level's reduced sums, read as the finalize reads them (its copies
+// under its gate, so before the finalize that clears them): one block, the count to mapped host
+// memory, which the host reads behind the ready number of a later finalize on the stream.
+__global__ __launch_bounds__(CHG_THREADS) void count_empty_kernel(const uint64_t *__restrict__ sums, uint32_t K,
+                                                                  uint32_t D, uint32_t ncopy, uint64_t cstride,
+                                                                  const unsigned *__restrict__ gate,
+                                                                  uint64_t *__restrict__ out) {
+    __shared__ unsigned wsum[CHG_THREADS / 64];
+    const uint64_t cnt0 = 2ull * K * D;
+    const uint32_t nc = (!gate || *gate != 0) ? ncopy : 1;
+    unsigned e = 0;
+    for (uint32_t k = threadIdx.x; k < K; k += CHG_THREADS) {
+        uint64_t n = sums[cnt0 + k];
+        for (uint32_t i = 1; i < nc; i++) n += sums[i * cstride + cnt0 + k];
+        e += n == 0;
+    }
+    for (int off = 32; off >= 1; off >>= 1) e += __shfl_xor(e, off);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = e;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned t = 0;
+        for (int w = 0; w < CHG_THREADS / 64; w++) t += wsum[w];
+        *out = t;
+        __threadfence_system();
+    }
+}
+
 }  // namespace
 
 hipError_t launch_finalize(hipStream_t s, const FinArgs &f) {
@@ -271,8 +301,9 @@ hipError_t launch_finalize(hipStream_t s, const FinArgs &f) {
     if (f.D == 0 || f.D > 64 || f.K == 0 || f.children > 2 || f.ncopy == 0) return hipErrorInvalidValue;
     if (f.sums ? (f.measure ? !f.C_src : !f.C_cent) : !f.C_src) return hipErrorInvalidValue;
     if (f.measure && (!f.sums || f.children)) return hipErrorInvalidValue;
-    if (f.children == 2 && !f.sums) return hipErrorInvalidValue;
-    if (f.children && (f.Kpad < f.K || !f.C32 || !f.rows || (f.sums && !f.C_next))) return hipErrorInvalidValue;
+    if (f.children && (f.Kpad < f.K || !f.C32 || !f.rows || ((f.sums || f.children == 2) && !f.C_next)))
+        return hipErrorInvalidValue;
+    if (f.children == 2 && !f.sums && f.C_next == f.C_src) return hipErrorInvalidValue;   // (row k is read for row k + K)
     if (f.ties.out && (!f.done || !f.ready || !f.ties.rows || !f.ties.cnt || !f.ties.A || !f.ties.codes || (f.Dp & 3) ||
                        !f.ties.n_rows))
         return hipErrorInvalidValue;   // released with the ready flag
@@ -307,6 +338,14 @@ hipError_t launch_finalize(hipStream_t s, const FinArgs &f) {
     const uint32_t grid = n <= FIN_ONE_BLOCK_ROWS ? 1u : std::min<uint32_t>((n + 256 / L - 1) / (256 / L), 512);
     if (a.dist && grid > 1 && !f.dist_part) return hipErrorInvalidValue;
     hipLaunchKernelGGL(finalize_kernel, dim3(grid), dim3(256), 0, s, a, L);
+    return hipGetLastError();
+}
+
+hipError_t launch_count_empty(hipStream_t s, const uint64_t *sums, uint32_t K, uint32_t D, uint32_t ncopy,
+                              uint64_t cstride, const unsigned *gate, uint64_t *out) {
+    if (!sums || !out || K == 0 || D == 0 || ncopy == 0 || (ncopy > 1 && cstride < 2ull * K * D + K))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(count_empty_kernel, dim3(1), dim3(CHG_THREADS), 0, s, sums, K, D, ncopy, cstride, gate, out);
     return hipGetLastError();
 }
 
