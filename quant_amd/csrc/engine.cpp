@@ -2266,10 +2266,64 @@ qvq_status check_cie_raster(qvq_ctx *ctx, uint64_t N, uint32_t bw, uint32_t bh) 
 
 extern "C" {
 
-// The exact-mode set of the rasters d_rgb (device memory the context's stream may read) under
-// CIE1931: tiled and converted in one launch into a fresh d_X64 (k_tile64.hip); defined with install_exact.
+// Exact mode's training set (which sets take it: "way 2" below), ahead of the entry points that
+// install one.
+// The exact-mode set of n rows of dim components: adopt (an upload of the engine's own) taken over
+// as d_X64 as it is, or a fresh d_X64 that fill writes with work on the context's stream (a copy of
+// the caller's rows, or the launch that produces them).  raster_cs: the colour space of the raster
+// the rows come from, -1 for fp64 rows (qvq_get_training_info).  Returns with the stream drained.
+static qvq_status install_exact(qvq_ctx *ctx, uint64_t n, uint32_t dim, int raster_cs, DevBuf<double> *adopt,
+                                const std::function<hipError_t(double *)> &fill) {
+    ctx->rf = qvq_ctx::RefineState();
+    drop_training(ctx);   // before the new set's allocations: peak memory is one set
+    qvq_ctx::Training ts;   // moved into the context when it is complete
+    ts.N = n;
+    ts.D = dim;
+    ts.Dp = (dim + 3) & ~3u;
+    ts.exact = true;
+    ts.exact_cs = raster_cs;
+    if (adopt) ts.ex.d_X64 = std::move(*adopt);
+    else HIPCHK(ts.ex.d_X64.alloc(n * dim));
+    qvq_status st = ensure_apool(ctx, ts, 1);
+    if (st != QVQ_OK) return st;
+    HIPCHK(ts.d_ties.alloc(n));
+    HIPCHK(ts.ex.d_keys.alloc(n));
+    HIPCHK(ts.ex.d_iota.alloc(n));
+    HIPCHK(ts.ex.d_order.alloc(n));
+    ts.ex.temp_bytes = exact_sort_temp_bytes(n);
+    HIPCHK(ts.ex.d_temp.alloc(std::max<size_t>(ts.ex.temp_bytes, 16)));
+    if (!adopt) HIPCHK(fill(ts.ex.d_X64));
+    HIPCHK(launch_exact_iota(ctx->stream, ts.ex.d_iota, n));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    ctx->ts = std::move(ts);
+    return QVQ_OK;
+}
+// ... from src's rows: on the host, or on the device where the context's stream may read them
+static qvq_status install_exact_copy(qvq_ctx *ctx, const double *src, hipMemcpyKind kind, DevBuf<double> *adopt, uint64_t n,
+                                     uint32_t dim) {
+    return install_exact(ctx, n, dim, -1, adopt, [&](double *dst) {
+        return hipMemcpyAsync(dst, src, n * dim * 8, kind, ctx->stream);
+    });
+}
+// ... from the rasters d_rgb (device memory the context's stream may read) under CIE1931, tiled
+// and converted in one launch (k_tile64.hip): nothing is classified -- the values are never byte
+// images -- and nothing is copied: the launch writes d_X64.  Under
+// qvq_set_timing(-3) events around the launch give its device ms (qvq_get_ingest_ms()[1]).
 static qvq_status install_cie_raster(qvq_ctx *ctx, const uint8_t *d_rgb, uint32_t n_images, uint32_t xSize,
-                                     uint32_t ySize, uint32_t bw, uint32_t bh, uint64_t N, uint32_t D);
+                                     uint32_t ySize, uint32_t bw, uint32_t bh, uint64_t N, uint32_t D) {
+    const bool timed = ctx->timing_level == -3;
+    ctx->ingest_ms[0] = ctx->ingest_ms[1] = 0;
+    const qvq_status st = install_exact(ctx, N, D, QVQ_CS_CIE1931, nullptr, [&](double *dst) {
+        hipError_t e = timed ? hipEventRecord(ctx->ev_ing[1], ctx->stream) : hipSuccess;
+        if (e == hipSuccess) e = launch_tile64(ctx->stream, d_rgb, dst, n_images, xSize, ySize, bw, bh);
+        if (e == hipSuccess && timed) e = hipEventRecord(ctx->ev_ing[2], ctx->stream);
+        return e;
+    });
+    float ms = 0;
+    if (st == QVQ_OK && timed && hipEventElapsedTime(&ms, ctx->ev_ing[1], ctx->ev_ing[2]) == hipSuccess)
+        ctx->ingest_ms[1] = ms;
+    return st;
+}
 
 QVQ_API const char *qvq_version(void) { return "qvq 0.2 (gfx950, f16 MFMA search)"; }
 
@@ -2494,62 +2548,6 @@ static qvq_status check_exact_set(qvq_ctx *ctx, uint64_t n, bool forced, bool fi
     if (n >= (1ull << 31)) return fail(ctx, QVQ_EINVAL, "exact mode: more than 2^31-1 rows");
     if (!finite) return fail(ctx, QVQ_EINVAL, "exact mode: training values must be finite");
     return QVQ_OK;
-}
-
-// The exact-mode set of n rows of dim components: adopt (an upload of the engine's own) taken over
-// as d_X64 as it is, or a fresh d_X64 that fill writes with work on the context's stream (a copy of
-// the caller's rows, or the launch that produces them).  raster_cs: the colour space of the raster
-// the rows come from, -1 for fp64 rows (qvq_get_training_info).  Returns with the stream drained.
-static qvq_status install_exact(qvq_ctx *ctx, uint64_t n, uint32_t dim, int raster_cs, DevBuf<double> *adopt,
-                                const std::function<hipError_t(double *)> &fill) {
-    ctx->rf = qvq_ctx::RefineState();
-    drop_training(ctx);   // before the new set's allocations: peak memory is one set
-    qvq_ctx::Training ts;   // moved into the context when it is complete
-    ts.N = n;
-    ts.D = dim;
-    ts.Dp = (dim + 3) & ~3u;
-    ts.exact = true;
-    ts.exact_cs = raster_cs;
-    if (adopt) ts.ex.d_X64 = std::move(*adopt);
-    else HIPCHK(ts.ex.d_X64.alloc(n * dim));
-    qvq_status st = ensure_apool(ctx, ts, 1);
-    if (st != QVQ_OK) return st;
-    HIPCHK(ts.d_ties.alloc(n));
-    HIPCHK(ts.ex.d_keys.alloc(n));
-    HIPCHK(ts.ex.d_iota.alloc(n));
-    HIPCHK(ts.ex.d_order.alloc(n));
-    ts.ex.temp_bytes = exact_sort_temp_bytes(n);
-    HIPCHK(ts.ex.d_temp.alloc(std::max<size_t>(ts.ex.temp_bytes, 16)));
-    if (!adopt) HIPCHK(fill(ts.ex.d_X64));
-    HIPCHK(launch_exact_iota(ctx->stream, ts.ex.d_iota, n));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    ctx->ts = std::move(ts);
-    return QVQ_OK;
-}
-// ... from src's rows: on the host, or on the device where the context's stream may read them
-static qvq_status install_exact_copy(qvq_ctx *ctx, const double *src, hipMemcpyKind kind, DevBuf<double> *adopt, uint64_t n,
-                                     uint32_t dim) {
-    return install_exact(ctx, n, dim, -1, adopt, [&](double *dst) {
-        return hipMemcpyAsync(dst, src, n * dim * 8, kind, ctx->stream);
-    });
-}
-// ... from rasters under CIE1931 (declared above qvq_set_images_device): nothing is classified -- the
-// values are never byte images -- and nothing is copied: the launch writes d_X64.  Under
-// qvq_set_timing(-3) events around the launch give its device ms (qvq_get_ingest_ms()[1]).
-static qvq_status install_cie_raster(qvq_ctx *ctx, const uint8_t *d_rgb, uint32_t n_images, uint32_t xSize,
-                                     uint32_t ySize, uint32_t bw, uint32_t bh, uint64_t N, uint32_t D) {
-    const bool timed = ctx->timing_level == -3;
-    ctx->ingest_ms[0] = ctx->ingest_ms[1] = 0;
-    const qvq_status st = install_exact(ctx, N, D, QVQ_CS_CIE1931, nullptr, [&](double *dst) {
-        hipError_t e = timed ? hipEventRecord(ctx->ev_ing[1], ctx->stream) : hipSuccess;
-        if (e == hipSuccess) e = launch_tile64(ctx->stream, d_rgb, dst, n_images, xSize, ySize, bw, bh);
-        if (e == hipSuccess && timed) e = hipEventRecord(ctx->ev_ing[2], ctx->stream);
-        return e;
-    });
-    float ms = 0;
-    if (st == QVQ_OK && timed && hipEventElapsedTime(&ms, ctx->ev_ing[1], ctx->ev_ing[2]) == hipSuccess)
-        ctx->ingest_ms[1] = ms;
-    return st;
 }
 
 // The training set from fp64 rows dX [n][dim] that the context's stream may read: classify, then
@@ -2877,6 +2875,40 @@ struct HostPlaceGuard {   // the caller's CPUs narrowed to ctx->place during one
     }
 };
 
+// A finished qvq_lbg's events and published counters into ctx->tm: per level the device times
+// (upd: the level timed a separate sums pass, LevelSums::upd) and the flagged and tie rows (stats:
+// the level counters as copy_out published them), and the mean kernel's time.
+static void lbg_timings(qvq_ctx *ctx, uint32_t bits, const bool *upd, const unsigned *stats) {
+    for (uint32_t lvl = 1; lvl <= bits; lvl++) {
+        // assign: the search kernel; update: the non-fused update; other: the rest of the
+        // level up to the next level's search (recheck, kd-tree, reduce, finalize, tables)
+        float a = 0, u = 0, whole = 0;
+        const bool timed = ctx->timing_level == -1 || ctx->timing_level == (int)lvl - 1;
+        if (timed) {
+            (void)hipEventSynchronize(ctx->ev[lvl - 1][1]);   // complete; the runtime may not know yet
+            (void)hipEventElapsedTime(&a, ctx->ev[lvl - 1][0], ctx->ev[lvl - 1][1]);
+        }
+        if (upd[lvl - 1]) {
+            (void)hipEventSynchronize(ctx->ev[lvl - 1][3]);
+            (void)hipEventElapsedTime(&u, ctx->ev[lvl - 1][2], ctx->ev[lvl - 1][3]);
+        }
+        if (ctx->timing_level == -1) (void)hipEventSynchronize(ctx->ev_end);
+        if (ctx->timing_level == -1)
+            (void)hipEventElapsedTime(&whole, ctx->ev[lvl - 1][0], lvl < bits ? ctx->ev[lvl][0] : ctx->ev_end);
+        ctx->tm.assign_ms[lvl - 1] = a;
+        ctx->tm.other_ms[lvl - 1] = ctx->timing_level == -1 ? std::max(0.f, whole - a - u) : 0.f;
+        ctx->tm.update_ms[lvl - 1] = u;
+        ctx->tm.flagged[lvl - 1] = stats[2 * (lvl - 1)];
+        ctx->tm.host_ties[lvl - 1] = stats[2 * (lvl - 1) + 1];
+    }
+    if (ctx->timing_level == -3) {
+        float m = 0;
+        (void)hipEventSynchronize(ctx->ev[31][1]);
+        (void)hipEventElapsedTime(&m, ctx->ev[31][0], ctx->ev[31][1]);
+        ctx->tm.mean_ms = m;
+    }
+}
+
 QVQ_API qvq_status qvq_lbg(qvq_ctx *ctx, uint32_t bits, double eps, double *codebook, uint32_t *assign,
                            double *distortion) {
     (void)eps;   // cannot change the outputs: one Lloyd step per level
@@ -3162,34 +3194,7 @@ QVQ_API qvq_status qvq_lbg(qvq_ctx *ctx, uint32_t bits, double eps, double *code
     // sum ||x||^2 when the cells are (nearly) exact; a distortion is never negative
     const double dist_final = std::max(0.0, (dres[0] - dres[2]) / (dres[1] * (double)ctx->ts.D));
     if (distortion) *distortion = dist_final;
-    for (uint32_t lvl = 1; lvl <= bits; lvl++) {
-        // assign: the search kernel; update: the non-fused update; other: the rest of the
-        // level up to the next level's search (recheck, kd-tree, reduce, finalize, tables)
-        float a = 0, u = 0, whole = 0;
-        const bool timed = ctx->timing_level == -1 || ctx->timing_level == (int)lvl - 1;
-        if (timed) {
-            (void)hipEventSynchronize(ctx->ev[lvl - 1][1]);   // complete; the runtime may not know yet
-            (void)hipEventElapsedTime(&a, ctx->ev[lvl - 1][0], ctx->ev[lvl - 1][1]);
-        }
-        if (upd[lvl - 1]) {
-            (void)hipEventSynchronize(ctx->ev[lvl - 1][3]);
-            (void)hipEventElapsedTime(&u, ctx->ev[lvl - 1][2], ctx->ev[lvl - 1][3]);
-        }
-        if (ctx->timing_level == -1) (void)hipEventSynchronize(ctx->ev_end);
-        if (ctx->timing_level == -1)
-            (void)hipEventElapsedTime(&whole, ctx->ev[lvl - 1][0], lvl < bits ? ctx->ev[lvl][0] : ctx->ev_end);
-        ctx->tm.assign_ms[lvl - 1] = a;
-        ctx->tm.other_ms[lvl - 1] = ctx->timing_level == -1 ? std::max(0.f, whole - a - u) : 0.f;
-        ctx->tm.update_ms[lvl - 1] = u;
-        ctx->tm.flagged[lvl - 1] = stats[2 * (lvl - 1)];
-        ctx->tm.host_ties[lvl - 1] = stats[2 * (lvl - 1) + 1];
-    }
-    if (ctx->timing_level == -3) {
-        float m = 0;
-        (void)hipEventSynchronize(ctx->ev[31][1]);
-        (void)hipEventElapsedTime(&m, ctx->ev[31][0], ctx->ev[31][1]);
-        ctx->tm.mean_ms = m;
-    }
+    lbg_timings(ctx, bits, upd, stats);
     (void)hipGetLastError();
     ctx->tm.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (htrace) {
@@ -3283,6 +3288,18 @@ QVQ_API qvq_status qvq_update(qvq_ctx *ctx, const uint32_t *assign, uint32_t K, 
     return QVQ_OK;
 }
 
+// The K Kahan centroids in d_kc_cent to the caller (C_out may be null): through context-owned
+// pinned memory, which reaches the caller only after the bounded wait succeeds.
+static qvq_status kahan_result(qvq_ctx *ctx, uint32_t K, double *C_out) {
+    const uint64_t cB = (uint64_t)K * ctx->ts.D * 8;
+    HIPCHK(ctx->h_stage.ensure(cB));
+    HIPCHK(hipMemcpyAsync(ctx->h_stage, ctx->kh.cells.d_kc_cent, cB, hipMemcpyDeviceToHost, ctx->stream));
+    const qvq_status st = wait_stream(ctx);
+    if (st != QVQ_OK) return st;
+    if (C_out) std::memcpy(C_out, ctx->h_stage, cB);
+    return QVQ_OK;
+}
+
 // The reference's centroids bit for bit (Solution::fixCodeVectors, src/Quantizer.cpp:59-87):
 // Kahan sums in ascending row order times fl(1/n) (k_kahan.hip).  One rank; byte rows.
 QVQ_API qvq_status qvq_update_kahan(qvq_ctx *ctx, const uint32_t *assign, uint32_t K, double *C_out) {
@@ -3313,11 +3330,7 @@ QVQ_API qvq_status qvq_update_kahan(qvq_ctx *ctx, const uint32_t *assign, uint32
         HIPCHK(launch_kahan_centroids(ctx->stream, ctx->kh.kw, ctx->ts.d_codes, ctx->ts.Dp, ctx->ts.D, ctx->ts.N,
                                       K == 1 ? nullptr : ctx->ts.d_A, K, ctx->kh.cells.d_kc_cent, nullptr, nullptr, 0, max_rows));
     }
-    const uint64_t cB = (uint64_t)K * ctx->ts.D * 8;
-    HIPCHK(ctx->h_stage.ensure(cB));
-    HIPCHK(hipMemcpyAsync(ctx->h_stage, ctx->kh.cells.d_kc_cent, cB, hipMemcpyDeviceToHost, ctx->stream));
-    if ((st = wait_stream(ctx)) != QVQ_OK) return st;
-    if (C_out) std::memcpy(C_out, ctx->h_stage, cB);
+    if ((st = kahan_result(ctx, K, C_out)) != QVQ_OK) return st;
     if (env_is("QVQ_KAHAN_DEBUG", "1")) {
         unsigned ms[4];
         HIPCHK(hipMemcpy(ms, ctx->kh.kw.stats, sizeof(ms), hipMemcpyDeviceToHost));
@@ -3351,11 +3364,50 @@ QVQ_API qvq_status qvq_update_kahan_split(qvq_ctx *ctx, const uint32_t *assign, 
     const std::vector<uint64_t> cuts(splits, splits + nsplits + 1);
     if ((st = kahan_chained(ctx, K == 1 ? nullptr : ctx->ts.d_A, K, nullptr, K, false, &cuts)) != QVQ_OK)
         return st;
-    const uint64_t cB = (uint64_t)K * ctx->ts.D * 8;
-    HIPCHK(ctx->h_stage.ensure(cB));
-    HIPCHK(hipMemcpyAsync(ctx->h_stage, ctx->kh.cells.d_kc_cent, cB, hipMemcpyDeviceToHost, ctx->stream));
-    if ((st = wait_stream(ctx)) != QVQ_OK) return st;
-    if (C_out) std::memcpy(C_out, ctx->h_stage, cB);
+    return kahan_result(ctx, K, C_out);
+}
+
+// The distortion a finalize published through FinArgs::pub (h_ready + 4: [1] the term's bits), once
+// the host has seen its ready number or drained the stream: the closed form sum ||x||^2 -
+// sum_k (2 c_k.S_k - n_k ||c_k||^2) over the norm (rows * D), never negative.  The fence orders
+// this and the caller's later reads of the page.
+static double published_distortion(const qvq_ctx *ctx, double xsq, double norm) {
+    std::atomic_thread_fence(std::memory_order_acquire);
+    const volatile uint64_t *h_pub = ctx->h_ready + 4;
+    const uint64_t bits = h_pub[1];
+    double term;
+    std::memcpy(&term, &bits, 8);
+    return std::max(0.0, (xsq - term) / norm);
+}
+
+// sum ||x||^2 and the rows of D components, from a byte histogram on the host
+static void hist_totals(const qvq_ctx *ctx, const uint64_t *hist, double &sq_out, uint64_t &rows_out) {
+    long double sq = 0;
+    uint64_t n = 0;
+    for (int b = 0; b < 256; b++) {
+        sq += (long double)hist[b] * (long double)ctx->ts.terms.v64[b] * (long double)ctx->ts.terms.v64[b];
+        n += hist[b];
+    }
+    sq_out = (double)sq;
+    rows_out = n / ctx->ts.D;
+}
+
+// One rank: sum ||x||^2 and the rows from the byte histogram, once per training set (rf.xsq, rf.rows).
+static qvq_status ensure_xsq(qvq_ctx *ctx) {
+    if (ctx->rf.have_xsq) return QVQ_OK;
+    uint64_t hist[256], n;
+    HIPCHK(hipMemcpy(hist, ctx->d_hist, sizeof(hist), hipMemcpyDeviceToHost));
+    hist_totals(ctx, hist, ctx->rf.xsq, n);
+    ctx->rf.rows = (double)n;
+    ctx->rf.have_xsq = true;
+    return QVQ_OK;
+}
+
+// Both iterations' level counters and the rows-changed total, cleared on the stream before a
+// Lloyd run (an earlier run may have dropped a search).
+static qvq_status clear_iteration_counters(qvq_ctx *ctx) {
+    HIPCHK(hipMemsetAsync(ctx->d_counters, 0, 4 * sizeof(unsigned), ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->d_counters + CHANGED_COUNTER, 0, 2 * sizeof(unsigned), ctx->stream));
     return QVQ_OK;
 }
 
@@ -3469,12 +3521,8 @@ static qvq_status lloyd_at_k(qvq_ctx *ctx, LloydRun &r) {
     double d_prev = d0, d_last = d0;
     // iteration t's published count and distortion, and the stop rule
     auto absorb = [&]() {
-        std::atomic_thread_fence(std::memory_order_acquire);
+        const double d = published_distortion(ctx, xsq, norm);
         const uint64_t chg = (t == 1 && !cont) ? rows_all : h_pub[0];
-        const uint64_t bits = h_pub[1];
-        double term;
-        std::memcpy(&term, &bits, 8);
-        const double d = std::max(0.0, (xsq - term) / norm);
         const uint64_t seeds = reseed ? h_pub[2] : 0;
         if (r.reseeds) r.reseeds->push_back(seeds);
         r.seeds += seeds;
@@ -3627,16 +3675,6 @@ QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start, u
     const uint32_t D = ctx->ts.D;
     const uint64_t KD = (uint64_t)K * D;
     // sum ||x||^2 and the rows, from the byte histogram
-    auto hist_totals = [&](const uint64_t *hist, double &sq_out, uint64_t &rows_out) {
-        long double sq = 0;
-        uint64_t n = 0;
-        for (int b = 0; b < 256; b++) {
-            sq += (long double)hist[b] * (long double)ctx->ts.terms.v64[b] * (long double)ctx->ts.terms.v64[b];
-            n += hist[b];
-        }
-        sq_out = (double)sq;
-        rows_out = n / D;
-    };
     double xsq;
     uint64_t rows_all;   // the rows of every rank
     if (sharded) {   // of every rank's rows: the histogram all-reduced as integers, as qvq_lbg does (once per call)
@@ -3645,15 +3683,9 @@ QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start, u
         HIPCHK(ctx->h_stage.ensure(256 * 8));
         HIPCHK(hipMemcpyAsync(ctx->h_stage, ctx->d_hist + 256, 256 * 8, hipMemcpyDeviceToHost, ctx->stream));
         if ((st = wait_stream(ctx)) != QVQ_OK) return st;   // bounded: the all-reduce may wait on peer ranks
-        hist_totals(reinterpret_cast<const uint64_t *>(ctx->h_stage.get()), xsq, rows_all);
+        hist_totals(ctx, reinterpret_cast<const uint64_t *>(ctx->h_stage.get()), xsq, rows_all);
     } else {
-        if (!ctx->rf.have_xsq) {   // once per training set
-            uint64_t hist[256], n;
-            HIPCHK(hipMemcpy(hist, ctx->d_hist, sizeof(hist), hipMemcpyDeviceToHost));
-            hist_totals(hist, ctx->rf.xsq, n);
-            ctx->rf.rows = (double)n;
-            ctx->rf.have_xsq = true;
-        }
+        if ((st = ensure_xsq(ctx)) != QVQ_OK) return st;
         xsq = ctx->rf.xsq;
         rows_all = ctx->ts.N;
     }
@@ -3664,8 +3696,7 @@ QVQ_API qvq_status qvq_refine(qvq_ctx *ctx, uint32_t K, const double *C_start, u
     uint64_t *const changed64 = sharded ? ctx->lv.d_sums + cell_u64 : nullptr;
     if (!cont) HIPCHK(hipMemcpy(ctx->lv.d_C64_cent, C_start, KD * 8, hipMemcpyHostToDevice));
     // both iterations' counters, the changed total; copy 1 of the sums if a quantize left it dirty
-    HIPCHK(hipMemsetAsync(ctx->d_counters, 0, 4 * sizeof(unsigned), ctx->stream));
-    HIPCHK(hipMemsetAsync(ctx->d_counters + CHANGED_COUNTER, 0, 2 * sizeof(unsigned), ctx->stream));
+    if ((st = clear_iteration_counters(ctx)) != QVQ_OK) return st;
     if ((st = clear_dirty_sums(ctx)) != QVQ_OK) return st;
     if (changed64) HIPCHK(hipMemsetAsync(changed64, 0, 8, ctx->stream));
     LloydRun run;
@@ -3711,22 +3742,6 @@ QVQ_API qvq_status qvq_get_refine_reseeds(qvq_ctx *ctx, uint64_t *out, uint32_t 
     const uint32_t n = (uint32_t)ctx->rf.reseeds.size();
     for (uint32_t i = 0; i < std::min(n, cap); i++) out[i] = ctx->rf.reseeds[i];
     if (iters) *iters = n;
-    return QVQ_OK;
-}
-
-// One rank: sum ||x||^2 and the rows from the byte histogram, once per training set (rf.xsq, rf.rows).
-static qvq_status ensure_xsq(qvq_ctx *ctx) {
-    if (ctx->rf.have_xsq) return QVQ_OK;
-    uint64_t hist[256], n = 0;
-    HIPCHK(hipMemcpy(hist, ctx->d_hist, sizeof(hist), hipMemcpyDeviceToHost));
-    long double sq = 0;
-    for (int b = 0; b < 256; b++) {
-        sq += (long double)hist[b] * (long double)ctx->ts.terms.v64[b] * (long double)ctx->ts.terms.v64[b];
-        n += hist[b];
-    }
-    ctx->rf.xsq = (double)sq;
-    ctx->rf.rows = (double)(n / ctx->ts.D);
-    ctx->rf.have_xsq = true;
     return QVQ_OK;
 }
 
@@ -3778,11 +3793,7 @@ QVQ_API qvq_status qvq_lbg_lloyd(qvq_ctx *ctx, uint32_t bits, uint32_t iters, do
         HIPCHK(ctx->h_stage.ensure((uint64_t)D * 8));
         HIPCHK(hipMemcpyAsync(ctx->h_stage, ctx->lv.d_C64_cent, (uint64_t)D * 8, hipMemcpyDeviceToHost, ctx->stream));
         if ((st = wait_stream(ctx)) != QVQ_OK) return st;
-        std::atomic_thread_fence(std::memory_order_acquire);
-        const uint64_t tbits = ctx->h_ready[5];
-        double term;
-        std::memcpy(&term, &tbits, 8);
-        d_last = std::max(0.0, (xsq - term) / norm);
+        d_last = published_distortion(ctx, xsq, norm);
     }
     for (uint32_t l = 1; l <= bits; l++) {
         const uint32_t K = 1u << l, H = K / 2;
@@ -3794,8 +3805,7 @@ QVQ_API qvq_status qvq_lbg_lloyd(qvq_ctx *ctx, uint32_t bits, uint32_t iters, do
         f.seq = ++ctx->seq;
         if ((st = run_finalize(ctx, f)) != QVQ_OK) return st;
         // both iterations' counters and the changed total (the previous level may have dropped a search)
-        HIPCHK(hipMemsetAsync(ctx->d_counters, 0, 4 * sizeof(unsigned), ctx->stream));
-        HIPCHK(hipMemsetAsync(ctx->d_counters + CHANGED_COUNTER, 0, 2 * sizeof(unsigned), ctx->stream));
+        if ((st = clear_iteration_counters(ctx)) != QVQ_OK) return st;
         LloydRun run;
         run.K = K;
         run.max_iters = iters;
@@ -3902,11 +3912,7 @@ QVQ_API qvq_status qvq_median_cut(qvq_ctx *ctx, uint32_t bits, double *codebook,
     HIPCHK(hipMemcpyAsync(stage, ctx->lv.d_C64_cent, cB, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(stage + cB, w.cuts, uB, hipMemcpyDeviceToHost, ctx->stream));
     if ((st = wait_stream(ctx)) != QVQ_OK) return st;
-    std::atomic_thread_fence(std::memory_order_acquire);
-    const uint64_t tbits = ctx->h_ready[5];
-    double term;
-    std::memcpy(&term, &tbits, 8);
-    const double dist = std::max(0.0, (ctx->rf.xsq - term) / (ctx->rf.rows * (double)D));
+    const double dist = published_distortion(ctx, ctx->rf.xsq, ctx->rf.rows * (double)D);
     if (codebook) std::memcpy(codebook, stage, cB);
     if (cuts && bits) std::memcpy(cuts, stage + cB, bits * sizeof(uint32_t));
     if (assign) HIPCHK(host_copy(ctx, assign, A, N * 4, hipMemcpyDeviceToHost));
