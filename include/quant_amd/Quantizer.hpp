@@ -2,6 +2,7 @@
 // src/Quantizer.cpp:119-155), with LBG running on the MI355X engine (include/qvq.h).
 #pragma once
 #include <cstddef>
+#include <cstdint>
 #include <memory>
 #include <tuple>
 #include <vector>
@@ -46,3 +47,11 @@ QuantizerPtr getLloydLBGQuantizer(size_t lloydIters, bool reseed, size_t refineI
 // given).  reseed needs refineIters > 0 (std::invalid_argument otherwise).  Byte images only: any
 // other training set throws std::runtime_error with the engine's message.
 QuantizerPtr getMedianCutQuantizer(size_t refineIters = 0, bool fresh = false, bool reseed = false);
+// k-means++ seeding on the device (qvq_kmeanspp, include/qvq.h: the rule is written there) and Lloyd
+// refinement from the seeds.  quantize(trainingSet, n, eps) seeds K = 2^n code vectors with `seed`,
+// then runs qvq_refine with C_start = the seeds, up to refineIters iterations stopped by eps and the
+// flags as given; with refineIters == 0 it passes QVQ_REFINE_FRESH, so the returned assignment is the
+// nearest seed.  reseed needs refineIters > 0 (std::invalid_argument otherwise).  Byte images only:
+// any other training set throws std::runtime_error with the engine's message.  getQuantizer and the
+// Quantizers enum have no slot for it (3 is the reference's ABC); compress() records LBG.
+QuantizerPtr getKMeansPPQuantizer(uint64_t seed, size_t refineIters = 0, bool fresh = false, bool reseed = false);

@@ -367,6 +367,48 @@ QVQ_API qvq_status qvq_lbg_lloyd(qvq_ctx *ctx, uint32_t bits, uint32_t iters, do
 QVQ_API qvq_status qvq_median_cut(qvq_ctx *ctx, uint32_t bits, double *codebook, uint32_t *assign,
                                   double *distortion, uint32_t *cuts);
 
+/*
+ * k-means++ seeding on the device (D^2-sampling, Arthur & Vassilvitskii 2007): K training rows as a
+ * starting codebook for qvq_refine (C_start = this call's codebook), for any K in 1 .. 2^20.  Every
+ * seed is a training row, K distinct seeds give K non-empty cells, and on the byte path the whole
+ * rule is integer arithmetic.  The reference has no such quantizer: this text is the rule.  One
+ * rank's byte path: N rows of Dp padded components; o[row][d] = (uint8)(code ^ 0x80) is the ordinal
+ * of a code byte.  Both byte colour spaces are affine in it (NORMAL o - 128, SCALED o * fl(1/255));
+ * pad bytes hold the space's zero code in every row and add 0 to any difference.
+ *
+ * Weight: w(a, b) = sum over d < Dp of (o[a][d] - o[b][d])^2, an exact integer <= 64 * 255^2 < 2^22:
+ *   the squared distance in NORMAL, 255^2 times it in SCALED before rounding.
+ * Random numbers (u64, every operation wraps):
+ *   mix(x): x += 0x9E3779B97F4A7C15; x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9;
+ *           x = (x ^ x >> 27) * 0x94D049BB133111EB; return x ^ x >> 31
+ *   draw(seed, j, T) = floor(mix(seed + j) * T / 2^64), the high 64 bits of the 128-bit product: in [0, T).
+ * Seeding: s_0 = draw(seed, 0, N); m[row] = w(row, s_0); potential[0] = sum of m.  For j = 1 .. K - 1:
+ *   T = sum of m over the rows (a u64); T = 0: every row equals a seed, placed = j, stop.  Else
+ *   t = draw(seed, j, T); s_j = the lowest row with (sum of m[i] over i <= row) > t.  The comparison is
+ *   strict: a row with m = 0 is never drawn, so no two seeds are equal rows.  Then
+ *   m[row] = min(m[row], w(row, s_j)) and potential[j] = sum of m.  Without a stop placed = K.
+ *
+ * Outputs (caller-owned host memory, any may be NULL, written only after the bounded wait has
+ * succeeded): codebook (K x dim fp64): entry j < placed the dim values of row s_j, as
+ * qvq_get_vectors(s_j) gives them, entry j >= placed the zero vector (the engine's empty-cell
+ * convention); rows (K): s_j, 0xFFFFFFFF for j >= placed; potential (K): entries from placed on
+ * repeat 0; info->placed.  potential[j] / N is the mean squared error of seeds 0 .. j under
+ * nearest-seed assignment per row in squared ordinal units: divide by dim for the per-component
+ * figure qvq_lbg's distortion uses, and by 65025 = 255^2 for SCALED values.
+ *
+ * The call uses device buffers of its own (m, per-segment sums, the seed list) and touches nothing
+ * resident: qvq_assign_device, the C_start == NULL continuation of qvq_refine and a later qvq_lbg
+ * behave as if it had not happened.  Errors, in this order, each leaving the context as it was:
+ * QVQ_ESTATE without a training set; QVQ_EINVAL for K = 0 or K > 2^20 (K > N is legal: then placed
+ * <= the number of distinct rows); QVQ_EUNSUPPORTED for an exact-mode set; QVQ_EUNSUPPORTED with any
+ * communicator joined (a sharded seeding needs the prefix over the ranks' rows).  qvq_get_timings
+ * reports levels = 0 and the call's total_ms.
+ * (qvq_host_kmpp_draw and qvq_host_kmpp_weight are draw and w on the host.)
+ */
+typedef struct { uint32_t placed; } qvq_kmeanspp_info;
+QVQ_API qvq_status qvq_kmeanspp(qvq_ctx *ctx, uint32_t K, uint64_t seed, double *codebook, uint32_t *rows,
+                                uint64_t *potential, qvq_kmeanspp_info *info);
+
 /* Single steps over the current training set, for tests and benchmarks.
  * qvq_assign: nearest code vector of every row for codebook C (K x dim fp64, host),
  *   with the same MFMA/VALU search + fp64 recheck + kd-tree tie resolution as qvq_lbg.
@@ -605,6 +647,18 @@ typedef struct {
     uint32_t range_group_boxes, hist_group_boxes;
 } qvq_median_cut_plan;
 QVQ_API qvq_status qvq_host_median_cut_plan(uint32_t dim, uint32_t boxes, uint64_t n, qvq_median_cut_plan *out);
+/* qvq_kmeanspp's rule on the host (quant_amd/csrc/kmeanspp_rule.hpp, the text the kernels run).
+ * qvq_host_kmpp_draw: t = draw(seed, j, T), T > 0 (QVQ_EINVAL otherwise).  qvq_host_kmpp_weight: w of
+ * two rows given as their Dp code bytes (pad bytes included), Dp a multiple of 4 up to 64. */
+QVQ_API qvq_status qvq_host_kmpp_draw(uint64_t seed, uint64_t j, uint64_t T, uint64_t *t);
+QVQ_API qvq_status qvq_host_kmpp_weight(const uint8_t *codes_a, const uint8_t *codes_b, uint32_t Dp, uint32_t *w);
+/* The launch shape of qvq_kmeanspp's update pass over n rows (quant_amd/csrc/kmeanspp_plan.hpp, the
+ * function the launchers switch on): the rows are cut into `segments` contiguous segments of
+ * seg_rows rows (a multiple of block, at least one block; the last may be short), one block of
+ * `block` lanes per segment, a lane per row.  At most segments_cap segments, so that the select
+ * scans their sums in one block: more than segments_cap * block rows make seg_rows grow. */
+typedef struct { uint32_t block, segments, seg_rows, segments_cap; } qvq_kmeanspp_plan;
+QVQ_API qvq_status qvq_host_kmeanspp_plan(uint64_t n, qvq_kmeanspp_plan *out);
 /* The engine's bounded-wait policy (quant_amd/csrc/wait.hpp) driven by scripted probes, for
  * tests: scenario 0 the work publishes after ~5 ms; 1 it never does, no communicator; 2 it
  * never does, a healthy communicator; 3 the communicator reports an error after ~5 ms; 4 the

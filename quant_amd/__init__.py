@@ -70,6 +70,10 @@ class _MedianCutPlan(ctypes.Structure):
                                                 "hist_groups", "range_group_boxes", "hist_group_boxes")]
 
 
+class _KMeansPPPlan(ctypes.Structure):   # qvq_kmeanspp_plan
+    _fields_ = [(f, ctypes.c_uint32) for f in ("block", "segments", "seg_rows", "segments_cap")]
+
+
 class _LloydLevel(ctypes.Structure):   # qvq_lloyd_level
     _fields_ = [("iters", ctypes.c_uint32), ("stop", ctypes.c_uint32), ("changed", ctypes.c_uint64),
                 ("empty", ctypes.c_uint64), ("seeds", ctypes.c_uint64), ("distortion", ctypes.c_double)]
@@ -97,7 +101,8 @@ EXPORTED = ["qvq_create", "qvq_destroy", "qvq_last_error", "qvq_version", "qvq_s
             "qvq_host_cie1931", "qvq_host_tile64_grid", "qvq_get_refine_reseeds", "qvq_host_row_error",
             "qvq_host_reseed_far_key", "qvq_host_reseed_select", "qvq_host_reseed_grid", "qvq_host_decode_plan",
             "qvq_median_cut", "qvq_host_median_cut_plan", "qvq_host_median_cut_axis",
-            "qvq_host_median_cut_select", "qvq_lbg_lloyd"]
+            "qvq_host_median_cut_select", "qvq_lbg_lloyd", "qvq_kmeanspp", "qvq_host_kmpp_draw",
+            "qvq_host_kmpp_weight", "qvq_host_kmeanspp_plan"]
 
 COMM_NONE, COMM_RCCL, COMM_HOST = 0, 1, 2
 REFINE_FRESH, REFINE_RESEED = 1, 2            # qvq_refine flags
@@ -176,6 +181,10 @@ def lib():
             "qvq_host_median_cut_axis": ([P, P, u32, ctypes.POINTER(u32)], i),
             "qvq_host_median_cut_select": ([P, u32, u32, u64, ctypes.POINTER(u32)], i),
             "qvq_lbg_lloyd": ([P, u32, u32, ctypes.c_double, u32, P, P, P, P], i),
+            "qvq_kmeanspp": ([P, u32, u64, P, P, P, P], i),
+            "qvq_host_kmpp_draw": ([u64, u64, u64, ctypes.POINTER(u64)], i),
+            "qvq_host_kmpp_weight": ([P, P, u32, ctypes.POINTER(u32)], i),
+            "qvq_host_kmeanspp_plan": ([u64, ctypes.POINTER(_KMeansPPPlan)], i),
         }
         for name, (args, res) in sig.items():
             if os.environ.get("QVQ_LIB") and not hasattr(L, name):
@@ -401,6 +410,22 @@ class Engine:
         cuts = np.zeros(max(bits, 1), np.uint32)
         _check(lib().qvq_median_cut(self._h, bits, _p(C), _p(A) if want_assign else None, _p(d), _p(cuts)), self._h)
         return C, A, float(d[0]), [int(x) for x in cuts[:bits]]
+
+    def kmeanspp(self, K, seed=0):
+        """k-means++ seeding on the device (qvq_kmeanspp, the rule in qvq.h): (codebook, rows,
+        potential, placed).  codebook[j] holds the values of training row rows[j] for j < placed
+        and zeros after; rows[j] is 0xFFFFFFFF and potential[j] 0 from placed on.  potential[j] / n
+        is the mean squared error of seeds 0 .. j in squared ordinal units.  Any K in 1 .. 2**20;
+        one rank's byte path.  The codebook is a start for refine(C=...); nothing resident changes."""
+        K = int(K)
+        if K <= 0:
+            raise QVQError(1, "K must be in 1 .. 2^20")
+        C = np.empty((K, self.dim), np.float64)
+        rows, pot = np.empty(K, np.uint32), np.empty(K, np.uint64)
+        placed = ctypes.c_uint32()
+        _check(lib().qvq_kmeanspp(self._h, K, int(seed) & 0xFFFFFFFFFFFFFFFF, _p(C), _p(rows), _p(pot),
+                                  ctypes.cast(ctypes.byref(placed), ctypes.c_void_p)), self._h)
+        return C, rows, pot, int(placed.value)
 
     def refine_reseeds(self):
         """The seeds the last refine() placed in each iteration (qvq_get_refine_reseeds)."""
@@ -649,6 +674,31 @@ def host_median_cut_select(hist, lo, hi, n=None):
     return t.value
 
 
+def host_kmpp_draw(seed, j, T):
+    """draw(seed, j, T) of qvq_kmeanspp's rule (qvq_host_kmpp_draw): an int in [0, T)."""
+    t = ctypes.c_uint64()
+    _check(lib().qvq_host_kmpp_draw(int(seed) & 0xFFFFFFFFFFFFFFFF, int(j), int(T), ctypes.byref(t)))
+    return int(t.value)
+
+
+def host_kmpp_weight(codes_a, codes_b):
+    """w(a, b) of qvq_kmeanspp's rule from two rows' code bytes, pad bytes included (qvq_host_kmpp_weight)."""
+    a = np.ascontiguousarray(codes_a, np.uint8).ravel()
+    b = np.ascontiguousarray(codes_b, np.uint8).ravel()
+    assert a.size == b.size
+    w = ctypes.c_uint32()
+    _check(lib().qvq_host_kmpp_weight(_p(a), _p(b), a.size, ctypes.byref(w)))
+    return int(w.value)
+
+
+def host_kmeanspp_plan(n):
+    """The launch shape of qvq_kmeanspp's update pass over n rows (qvq_host_kmeanspp_plan): a dict of
+    block, segments, seg_rows, segments_cap."""
+    p = _KMeansPPPlan()
+    _check(lib().qvq_host_kmeanspp_plan(int(n), ctypes.byref(p)))
+    return {f: int(getattr(p, f)) for f, _ in _KMeansPPPlan._fields_}
+
+
 def host_row_error(x, c, colorspace=SCALED):
     """The quantised per-row error of QVQ_REFINE_RESEED (qvq_host_row_error): values x against code vector c."""
     x = np.ascontiguousarray(x, np.float64).ravel()
@@ -833,6 +883,33 @@ class MedianCutQuantizer(AbstractQuantizer):
             res = self._engine.refine(C=res[0], max_iters=self._refine_iters, eps=eps, fresh=self._fresh,
                                       reseed=self._reseed)[:3]
         return res
+
+
+class KMeansPPQuantizer(AbstractQuantizer):
+    """k-means++ seeding on the MI355X engine (Engine.kmeanspp) and Lloyd refinement from the seeds.
+    The reference has no such quantizer and the Quantizers enum no slot for it."""
+
+    def __init__(self, device=0, seed=0, refine_iters=0, fresh=False, reseed=False):
+        """quantize seeds 2**n code vectors with `seed`, then runs Engine.refine from them for up to
+        refine_iters iterations stopped by eps.  refine_iters = 0 returns the nearest-seed assignment
+        (a fresh assignment with no iteration).  reseed needs refine_iters > 0."""
+        if reseed and int(refine_iters) <= 0:
+            raise QVQError(1, "reseed needs refine_iters > 0")
+        self._device = device
+        self._engine = None
+        self._seed = int(seed)
+        self._refine_iters = int(refine_iters)
+        self._fresh = bool(fresh)
+        self._reseed = bool(reseed)
+
+    def quantize(self, trainingSet, n, eps):
+        if self._engine is None:
+            self._engine = Engine(self._device)
+        dev = getattr(trainingSet, "is_cuda", False)
+        self._engine.set_vectors(trainingSet if dev else np.asarray(trainingSet, np.float64))
+        C = self._engine.kmeanspp(1 << int(n), self._seed)[0]
+        return self._engine.refine(C=C, max_iters=self._refine_iters, eps=eps,
+                                   fresh=self._fresh or self._refine_iters == 0, reseed=self._reseed)[:3]
 
 
 def getQuantizer(q):

@@ -53,6 +53,8 @@ struct Params {   // include/ProgramParameters.hpp:5-19, defaults of src/main.cp
     bool fresh = false;   // --fresh: indices of the written codebook
     bool reseed = false;  // --reseed: the iterations reseed their empty cells
     int lloyd = 0;        // --lloyd: Lloyd iterations at every level (0: qvq_lbg's one assignment per level)
+    bool kmeanspp = false;   // --init kmeans++: the codebook starts from k-means++ seeds (default split: LBG's schedule)
+    uint64_t seed = 0;       // --seed: of the k-means++ draws
     std::string file, saveto;
 };
 
@@ -73,7 +75,10 @@ const char *kHelp =
     "  --refine arg (=0)      Lloyd iterations at the final codebook size (LBG, stopped by -e)\n"
     "  --fresh                Indices re-assigned to the written codebook\n"
     "  --reseed               Empty cells reseeded from the worst cells (with --refine or --lloyd)\n"
-    "  --lloyd arg (=0)       Lloyd iterations after every split (LBG, stopped by -e)\n";
+    "  --lloyd arg (=0)       Lloyd iterations after every split (LBG, stopped by -e)\n"
+    "  --init arg (=split)    Starting codebook: split (LBG's schedule) or kmeans++ (2^n training\n"
+    "                         rows by D^2-sampling, then --refine iterations; -q 0, not with --lloyd)\n"
+    "  --seed arg (=0)        Seed of the kmeans++ draws\n";
 
 bool parse_bool(const std::string &v) {   // program_options' bool values
     if (v == "1" || v == "true" || v == "yes" || v == "on") return true;
@@ -94,7 +99,8 @@ bool parse(int argc, char **argv, Params &p) {
     const std::map<std::string, std::string> names = {
         {"-n", "n"}, {"-e", "e"}, {"-w", "w"}, {"-h", "h"}, {"-o", "o"}, {"--saveto", "o"}, {"-r", "r"},
         {"-q", "q"}, {"--quantizer", "q"}, {"-c", "c"}, {"--colorspace", "c"}, {"--c", "c"}, {"--file", "file"},
-        {"--device", "device"}, {"--refine", "refine"}, {"--lloyd", "lloyd"}};
+        {"--device", "device"}, {"--refine", "refine"}, {"--lloyd", "lloyd"},
+        {"--init", "init"}, {"--seed", "seed"}};
     bool have_file = false, have_out = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
@@ -146,6 +152,17 @@ bool parse(int argc, char **argv, Params &p) {
             p.lloyd = parse_int(val, "--lloyd");
             if (p.lloyd < 0) throw std::invalid_argument("the argument ('" + val + "') for option '--lloyd' is invalid");
         }
+        else if (key == "init") {
+            if (val != "split" && val != "kmeans++")
+                throw std::invalid_argument("the argument ('" + val + "') for option '--init' is invalid");
+            p.kmeanspp = val == "kmeans++";
+        }
+        else if (key == "seed") {
+            size_t pos = 0;
+            if (val.empty() || val[0] == '-') pos = std::string::npos;
+            else p.seed = std::stoull(val, &pos);
+            if (pos != val.size()) throw std::invalid_argument("the argument ('" + val + "') for option '--seed' is invalid");
+        }
         else if (key == "o") {
             p.saveto = val;
             have_out = true;
@@ -163,6 +180,10 @@ bool parse(int argc, char **argv, Params &p) {
         throw std::invalid_argument("option '--reseed' needs the LBG quantizer");
     if (p.lloyd > 0 && p.quantizer != (int)Quantizers::LBG)
         throw std::invalid_argument("option '--lloyd' needs the LBG quantizer");
+    if (p.kmeanspp && p.quantizer != (int)Quantizers::LBG)
+        throw std::invalid_argument("option '--init kmeans++' needs the LBG quantizer");
+    if (p.kmeanspp && p.lloyd > 0)
+        throw std::invalid_argument("option '--init kmeans++' cannot be combined with '--lloyd'");
     if (p.reseed && p.refine <= 0 && p.lloyd <= 0)
         throw std::invalid_argument("option '--reseed' needs '--refine' > 0 or '--lloyd' > 0");
     return false;
@@ -187,7 +208,8 @@ int main(int argc, char **argv) {
         auto run_compression = [&]() {   // src/main.cpp:76-84
             RGBImage img(par.file);
             QuantizerPtr refined;
-            if (par.lloyd > 0) refined = getLloydLBGQuantizer((size_t)par.lloyd, par.reseed, (size_t)par.refine, par.fresh);
+            if (par.kmeanspp) refined = getKMeansPPQuantizer(par.seed, (size_t)par.refine, par.fresh, par.reseed);
+            else if (par.lloyd > 0) refined = getLloydLBGQuantizer((size_t)par.lloyd, par.reseed, (size_t)par.refine, par.fresh);
             else if (par.refine > 0 || par.fresh) refined = getRefinedLBGQuantizer((size_t)par.refine, par.fresh, par.reseed);
             auto result = refined ? CompressedImage::compress(img, *refined, (ColorSpaces)par.colorspace, par.width,
                                                               par.height, par.eps, par.n)

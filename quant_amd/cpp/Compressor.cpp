@@ -139,6 +139,20 @@ std::tuple<std::vector<Vector>, std::vector<size_t>, VectorType> quantize_raster
         for (size_t k = 0; k < K; k++) std::copy(C.begin() + k * D, C.begin() + (k + 1) * D, codebook[k].begin());
         return std::make_tuple(std::move(codebook), std::vector<size_t>(A.begin(), A.end()), distortion);
     }
+    if (opt.kmeanspp) {   // k-means++ seeds, then the refinement from them (no iteration: the nearest seed)
+        if (n > 20) throw std::runtime_error("compress: bits must be <= 20");
+        std::vector<double> start(K * D);
+        EngineHandle::check(qvq_kmeanspp(ctx, (uint32_t)K, opt.kmeansppSeed, start.data(), nullptr, nullptr, nullptr),
+                            "qvq_kmeanspp");
+        const bool fresh = opt.fresh || opt.maxIters == 0;
+        EngineHandle::check(qvq_refine(ctx, (uint32_t)K, start.data(), (uint32_t)opt.maxIters, eps,
+                                       (fresh ? QVQ_REFINE_FRESH : 0u) | (opt.reseed ? QVQ_REFINE_RESEED : 0u), C.data(),
+                                       A.data(), &distortion, nullptr, nullptr, nullptr),
+                            "qvq_refine");
+        std::vector<Vector> codebook(K, Vector(D));
+        for (size_t k = 0; k < K; k++) std::copy(C.begin() + k * D, C.begin() + (k + 1) * D, codebook[k].begin());
+        return std::make_tuple(std::move(codebook), std::vector<size_t>(A.begin(), A.end()), distortion);
+    }
     if (opt.lloydIters > 0 && n > 20) throw std::runtime_error("compress: bits must be <= 20");
     if (opt.lloydIters > 0xFFFFFFFFull) throw std::runtime_error("compress: too many Lloyd iterations per level");
     if (opt.lloydIters > 0)   // Lloyd iterations at every level; the refinement, if any, continues from it
@@ -230,7 +244,7 @@ std::pair<CompressedImage, CompressionRaport> CompressedImage::compress(const RG
 }
 
 // The caller's quantizer over the image's blocks.  The engine's own quantizers (getQuantizer,
-// getRefinedLBGQuantizer, getMedianCutQuantizer) train straight from the raster as the enum overload
+// getRefinedLBGQuantizer, getMedianCutQuantizer, getKMeansPPQuantizer) train straight from the raster as the enum overload
 // does, with their refinement; any other quantizer gets the host-built vectors.
 std::pair<CompressedImage, CompressionRaport> CompressedImage::compress(const RGBImage &image,
                                                                         AbstractQuantizer &quantizer,
@@ -247,6 +261,10 @@ std::pair<CompressedImage, CompressionRaport> CompressedImage::compress(const RG
     if (quant_amd::engine_median_cut_options(quantizer, opt) &&
         (colorSpace == ColorSpaces::NORMAL || colorSpace == ColorSpaces::SCALED)) {
         recorded = opt.maxIters > 0 || opt.fresh ? Quantizers::LBG_MEDIAN_CUT : Quantizers::MEDIAN_CUT;
+        std::tie(codebook, assigned, distortion) =
+            quantize_raster(image, colorSpace, blockWidth, blockHeight, eps, N, opt);
+    } else if (quant_amd::engine_kmeanspp_options(quantizer, opt) &&
+               (colorSpace == ColorSpaces::NORMAL || colorSpace == ColorSpaces::SCALED)) {
         std::tie(codebook, assigned, distortion) =
             quantize_raster(image, colorSpace, blockWidth, blockHeight, eps, N, opt);
     } else if (quant_amd::engine_lbg_options(quantizer, opt) &&

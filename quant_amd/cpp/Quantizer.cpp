@@ -134,7 +134,58 @@ public:
     }
 };
 
+// k-means++ seeding on the engine (qvq_kmeanspp), then qvq_refine from the seeds.  With no
+// iterations the refinement is the fresh assignment alone: the nearest seed of every row.
+class HipKMeansPPQuantizer : public AbstractQuantizer {
+    uint64_t seed_ = 0;
+    size_t maxIters_ = 0;
+    bool fresh_ = false, reseed_ = false;
+
+public:
+    HipKMeansPPQuantizer(uint64_t seed, size_t maxIters, bool fresh, bool reseed)
+        : seed_(seed), maxIters_(maxIters), fresh_(fresh), reseed_(reseed) {}
+    quant_amd::RefineOptions options() const {
+        quant_amd::RefineOptions o;
+        o.maxIters = maxIters_, o.fresh = fresh_, o.reseed = reseed_, o.kmeanspp = true, o.kmeansppSeed = seed_;
+        return o;
+    }
+    std::tuple<std::vector<Vector>, std::vector<size_t>, VectorType> quantize(const std::vector<Vector> &trainingSet,
+                                                                              size_t n, VectorType eps) override {
+        using quant_amd::EngineHandle;
+        if (trainingSet.empty()) throw std::runtime_error("k-means++ quantize: empty training set");
+        if (n > 20) throw std::runtime_error("k-means++ quantize: bits must be <= 20");
+        if (maxIters_ > 0xFFFFFFFFull) throw std::runtime_error("k-means++ quantize: too many refinement iterations");
+        const size_t N = trainingSet.size(), D = trainingSet[0].size();
+        std::vector<double> flat(N * D);
+        for (size_t i = 0; i < N; i++) {
+            if (trainingSet[i].size() != D) throw std::runtime_error("k-means++ quantize: vectors of different sizes");
+            std::copy(trainingSet[i].begin(), trainingSet[i].end(), flat.begin() + i * D);
+        }
+        qvq_ctx *ctx = EngineHandle::get();
+        EngineHandle::check(qvq_set_vectors(ctx, flat.data(), N, (uint32_t)D), "qvq_set_vectors");
+        const size_t K = (size_t)1 << n;
+        std::vector<double> start(K * D), C(K * D);
+        std::vector<uint32_t> A(N);
+        double distortion = 0;
+        EngineHandle::check(qvq_kmeanspp(ctx, (uint32_t)K, seed_, start.data(), nullptr, nullptr, nullptr), "qvq_kmeanspp");
+        const bool fresh = fresh_ || maxIters_ == 0;
+        EngineHandle::check(qvq_refine(ctx, (uint32_t)K, start.data(), (uint32_t)maxIters_, eps,
+                                       (fresh ? QVQ_REFINE_FRESH : 0u) | (reseed_ ? QVQ_REFINE_RESEED : 0u), C.data(),
+                                       A.data(), &distortion, nullptr, nullptr, nullptr),
+                            "qvq_refine");
+        std::vector<Vector> codebook(K, Vector(D));
+        for (size_t k = 0; k < K; k++) std::copy(C.begin() + k * D, C.begin() + (k + 1) * D, codebook[k].begin());
+        return std::make_tuple(std::move(codebook), std::vector<size_t>(A.begin(), A.end()), distortion);
+    }
+};
+
 }  // namespace
+
+bool quant_amd::engine_kmeanspp_options(const AbstractQuantizer &q, RefineOptions &out) {
+    const HipKMeansPPQuantizer *h = dynamic_cast<const HipKMeansPPQuantizer *>(&q);
+    if (h) out = h->options();
+    return h != nullptr;
+}
 
 bool quant_amd::engine_median_cut_options(const AbstractQuantizer &q, RefineOptions &out) {
     const HipMedianCutQuantizer *h = dynamic_cast<const HipMedianCutQuantizer *>(&q);
@@ -166,4 +217,9 @@ QuantizerPtr getLloydLBGQuantizer(size_t lloydIters, bool reseed, size_t refineI
 QuantizerPtr getMedianCutQuantizer(size_t refineIters, bool fresh, bool reseed) {
     if (reseed && refineIters == 0) throw std::invalid_argument("getMedianCutQuantizer: reseed needs refineIters > 0");
     return QuantizerPtr(new HipMedianCutQuantizer(refineIters, fresh, reseed));
+}
+
+QuantizerPtr getKMeansPPQuantizer(uint64_t seed, size_t refineIters, bool fresh, bool reseed) {
+    if (reseed && refineIters == 0) throw std::invalid_argument("getKMeansPPQuantizer: reseed needs refineIters > 0");
+    return QuantizerPtr(new HipKMeansPPQuantizer(seed, refineIters, fresh, reseed));
 }

@@ -1,5 +1,6 @@
 // One engine context per host thread for the C++ API (include/qvq.h underneath).
 #pragma once
+#include <cstdint>
 #include <stdexcept>
 #include <string>
 
@@ -24,9 +25,14 @@ struct RefineOptions {
     bool medianCut = false;   // the codebook starts from qvq_median_cut, and the refinement is a warm start from it
     size_t lloydIters = 0;    // > 0: qvq_lbg_lloyd with that many iterations per level in place of qvq_lbg (reseed
                               // then holds for the levels too); the refinement, if any, continues from it
+    bool kmeanspp = false;    // the codebook starts from qvq_kmeanspp's seeds (kmeansppSeed); the refinement starts from
+    uint64_t kmeansppSeed = 0;   // them, and with maxIters == 0 it is the fresh assignment alone
 };
 bool engine_lbg_options(const AbstractQuantizer &q, RefineOptions &out);
 // The same for the engine's median-cut quantizer (getMedianCutQuantizer): out.medianCut is set.
 bool engine_median_cut_options(const AbstractQuantizer &q, RefineOptions &out);
+
+// The same for the engine's k-means++ quantizer (getKMeansPPQuantizer): out.kmeanspp and the seed are set.
+bool engine_kmeanspp_options(const AbstractQuantizer &q, RefineOptions &out);
 
 }  // namespace quant_amd

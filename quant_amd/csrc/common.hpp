@@ -487,6 +487,29 @@ hipError_t launch_mc_axis(hipStream_t s, uint32_t boxes, uint32_t D, const McWor
 hipError_t launch_mc_hist(hipStream_t s, const uint8_t *codes, uint32_t Dp, uint32_t D, uint64_t N, const uint32_t *A,
                           uint32_t boxes, const McWork &w);
 hipError_t launch_mc_cut(hipStream_t s, uint32_t boxes, uint32_t D, uint32_t level, const McWork &w);
+// qvq_kmeanspp (k_kmeanspp.hip, kmeanspp_rule.hpp, kmeanspp_plan.hpp): the call's own state.  All but
+// m sit in one allocation of kmpp_layout(K, Dp).total bytes (offsets in bytes).
+struct KmppWork {
+    uint32_t *state = nullptr;       // [0] the stop flag (every row equals a seed), [1] placed
+    uint32_t *seedw = nullptr;       // [16] the newest seed's code words as ordinals: the next update's input
+    uint64_t *partial = nullptr;     // [KMPP_SEGMENTS_CAP] the segments' sums of m
+    uint64_t *potential = nullptr;   // [K]
+    uint32_t *rows = nullptr;        // [K] the seeds' rows
+    uint32_t *seedcodes = nullptr;   // [K][Dp / 4] the seeds' code words as stored
+    uint32_t *m = nullptr;           // [N] the rows' weight to their nearest seed (an allocation of its own)
+};
+struct KmppLayout {
+    uint64_t seedw = 0, partial = 0, potential = 0, rows = 0, seedcodes = 0, total = 0;
+};
+KmppLayout kmpp_layout(uint32_t K, uint32_t Dp);
+KmppWork kmpp_work(uint8_t *base, uint32_t *m, uint32_t K, uint32_t Dp);
+// A call: init(row0 = the first seed); update(first); for j = 1 .. K - 1: select(j), update; select(K),
+// which only publishes potential[K - 1].  After a select has raised the stop flag the rest return at once.
+hipError_t launch_kmpp_init(hipStream_t s, const uint8_t *codes, uint32_t Dp, uint64_t N, uint32_t row0, uint32_t K,
+                            const KmppWork &w);
+hipError_t launch_kmpp_update(hipStream_t s, const uint8_t *codes, uint32_t Dp, uint64_t N, bool first, const KmppWork &w);
+hipError_t launch_kmpp_select(hipStream_t s, const uint8_t *codes, uint32_t Dp, uint64_t N, uint32_t j, uint32_t K,
+                              uint64_t seed, const KmppWork &w);
 // Host-resolved rows: A[rows[i]] = vals[i]; with xslab their terms move from the
 // provisional index (A before) to the new one (move_row_terms).
 hipError_t launch_fix_rows(hipStream_t s, const uint8_t *codes, uint32_t Dp, uint32_t D, uint32_t *A,

@@ -39,6 +39,8 @@
 #include "decode_plan.hpp"
 #include "exact_plan.hpp"
 #include "kdtree.hpp"
+#include "kmeanspp_plan.hpp"
+#include "kmeanspp_rule.hpp"
 #include "median_cut_plan.hpp"
 #include "median_cut_rule.hpp"
 #include "owned.hpp"
@@ -219,6 +221,13 @@ struct qvq_ctx {
             DevBuf<uint8_t> d_temp;
             size_t temp_bytes = 0;
         } ex;
+        // qvq_kmeanspp's own state, cached between calls: m [N] and the work of kmpp_layout for up
+        // to K seeds.  Part of the training set, so whatever replaces the set drops it.
+        struct KMeansPP {
+            DevBuf<uint32_t> d_m;
+            DevBuf<uint8_t> d_work;
+            uint32_t K = 0;
+        } kpp;
     } ts;
 
     // ---- level buffers for up to Kcap code vectors: replaced as a whole by ensure_levels
@@ -3931,6 +3940,69 @@ QVQ_API qvq_status qvq_median_cut(qvq_ctx *ctx, uint32_t bits, double *codebook,
     return QVQ_OK;
 }
 
+// k-means++ seeding on the device (the rule in qvq.h, kmeanspp_rule.hpp).  The first
+// seed is drawn here; then K - 1 rounds of select and update are queued on the stream with no host
+// round trip, a last select publishes the final potential, and one bounded wait ends the call.
+// Everything the call writes on the device is its own (ts.kpp): no resident state is touched.
+QVQ_API qvq_status qvq_kmeanspp(qvq_ctx *ctx, uint32_t K, uint64_t seed, double *codebook, uint32_t *rows,
+                                uint64_t *potential, qvq_kmeanspp_info *info) {
+    if (!ctx) return QVQ_EINVAL;
+    GUARD(ctx);
+    if (ctx->ts.N == 0) return fail(ctx, QVQ_ESTATE, "no training set");
+    if (K == 0 || K > (1u << 20)) return fail(ctx, QVQ_EINVAL, "K must be in 1 .. 2^20");
+    if (ctx->ts.exact) return fail(ctx, QVQ_EUNSUPPORTED, "k-means++ seeding of an exact-mode training set is not supported");
+    if (ctx->comm || ctx->host_ar)
+        return fail(ctx, QVQ_EUNSUPPORTED, "k-means++ seeding is not supported on a communicator (no prefix over ranks)");
+    const auto t0 = std::chrono::steady_clock::now();
+    HIPCHK(hipSetDevice(ctx->dev));
+    const uint32_t D = ctx->ts.D, Dp = ctx->ts.Dp;
+    const uint64_t N = ctx->ts.N;
+    qvq_ctx::Training::KMeansPP &kp = ctx->ts.kpp;
+    HIPCHK(kp.d_m.ensure(N));
+    if (kp.K < K) {
+        kp.K = 0;
+        HIPCHK(kp.d_work.alloc(kmpp_layout(K, Dp).total));
+        kp.K = K;
+    }
+    const KmppLayout lay = kmpp_layout(kp.K, Dp);
+    const uint64_t pB = 8ull * K, rB = 4ull * K, cB = (uint64_t)K * Dp;   // staged: potential | rows | codes | state
+    HIPCHK(ctx->h_stage.ensure(pB + rB + cB + 8));
+    std::memset(&ctx->tm, 0, sizeof(ctx->tm));
+    const KmppWork w = kmpp_work(kp.d_work, kp.d_m, kp.K, Dp);
+    const uint8_t *codes = ctx->ts.d_codes;
+    HIPCHK(launch_kmpp_init(ctx->stream, codes, Dp, N, (uint32_t)kmpp_draw(seed, 0, N), K, w));
+    HIPCHK(launch_kmpp_update(ctx->stream, codes, Dp, N, true, w));
+    for (uint32_t j = 1; j < K; j++) {
+        HIPCHK(launch_kmpp_select(ctx->stream, codes, Dp, N, j, K, seed, w));
+        HIPCHK(launch_kmpp_update(ctx->stream, codes, Dp, N, false, w));
+    }
+    HIPCHK(launch_kmpp_select(ctx->stream, codes, Dp, N, K, K, seed, w));
+    // results land in context-owned pinned memory and reach the caller only after the bounded wait
+    uint8_t *stage = static_cast<uint8_t *>(ctx->h_stage);
+    const uint8_t *base = kp.d_work;
+    HIPCHK(hipMemcpyAsync(stage, base + lay.potential, pB, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(stage + pB, base + lay.rows, rB, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(stage + pB + rB, base + lay.seedcodes, cB, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(stage + pB + rB + cB, base, 8, hipMemcpyDeviceToHost, ctx->stream));
+    qvq_status st = wait_stream(ctx);
+    if (st != QVQ_OK) return st;
+    uint32_t state[2];
+    std::memcpy(state, stage + pB + rB + cB, 8);
+    const uint32_t placed = state[1];
+    if (potential) std::memcpy(potential, stage, pB);
+    if (rows) std::memcpy(rows, stage + pB, rB);
+    if (codebook) {   // a seed's values are its row's, as qvq_get_vectors gives them; past placed: the zero vector
+        const uint8_t *sc = stage + pB + rB;
+        for (uint32_t j = 0; j < K; j++)
+            for (uint32_t d = 0; d < D; d++)
+                codebook[(uint64_t)j * D + d] = j < placed ? ctx->ts.terms.v64[sc[(uint64_t)j * Dp + d]] : 0.0;
+    }
+    if (info) info->placed = placed;
+    ctx->tm.levels = 0;
+    ctx->tm.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return QVQ_OK;
+}
+
 // ---------------------------------------------------------------------------------------
 // Decode: CompressedImage::decompress (src/Compressor.cpp:156-165) as one device gather.
 // ---------------------------------------------------------------------------------------
@@ -4334,6 +4406,33 @@ QVQ_API qvq_status qvq_host_median_cut_axis(const uint32_t *lo, const uint32_t *
 QVQ_API qvq_status qvq_host_median_cut_select(const uint32_t *hist, uint32_t lo, uint32_t hi, uint64_t n, uint32_t *t) {
     if (!hist || !t || lo >= hi || hi > 255) return QVQ_EINVAL;
     *t = mc_select(hist, lo, hi, n);
+    return QVQ_OK;
+}
+
+QVQ_API qvq_status qvq_host_kmpp_draw(uint64_t seed, uint64_t j, uint64_t T, uint64_t *t) {
+    if (!t || T == 0) return QVQ_EINVAL;
+    *t = kmpp_draw(seed, j, T);
+    return QVQ_OK;
+}
+
+QVQ_API qvq_status qvq_host_kmpp_weight(const uint8_t *codes_a, const uint8_t *codes_b, uint32_t Dp, uint32_t *w) {
+    if (!codes_a || !codes_b || !w || Dp == 0 || Dp > 64 || (Dp & 3)) return QVQ_EINVAL;
+    uint32_t a[16], b[16];
+    std::memcpy(a, codes_a, Dp);
+    std::memcpy(b, codes_b, Dp);
+    const uint32_t nw = Dp / 4;
+    for (uint32_t i = 0; i < nw; i++) a[i] = kmpp_ordinals(a[i]), b[i] = kmpp_ordinals(b[i]);
+    *w = kmpp_weight(a, kmpp_norm(a, nw), b, kmpp_norm(b, nw), nw);
+    return QVQ_OK;
+}
+
+QVQ_API qvq_status qvq_host_kmeanspp_plan(uint64_t n, qvq_kmeanspp_plan *out) {
+    if (!out || n == 0 || n > 0xFFFFFFFFull) return QVQ_EINVAL;
+    const KMeansPPPlan p = kmeanspp_plan(n);
+    out->block = p.block;
+    out->segments = p.segments;
+    out->seg_rows = p.seg_rows;
+    out->segments_cap = KMPP_SEGMENTS_CAP;
     return QVQ_OK;
 }
 
