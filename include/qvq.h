@@ -437,6 +437,17 @@ QVQ_API qvq_status qvq_update_kahan(qvq_ctx *ctx, const uint32_t *assign, uint32
  * evaluation run rank after rank on one device; equals qvq_update_kahan for any cuts. */
 QVQ_API qvq_status qvq_update_kahan_split(qvq_ctx *ctx, const uint32_t *assign, uint32_t K, const uint64_t *splits,
                                           uint32_t nsplits, double *C_out);
+/* Both accept any K (qvq_lbg uses up to 2^20): the device's stable sort by cell keeps one counter per key in
+ * LDS and takes the keys in windows (qvq_host_kahan_sort_plan), so K is not bound by the LDS.
+ *
+ * Test entry: what the last qvq_update_kahan / qvq_update_kahan_split call on this context ran.
+ * route: the step-by-step kernel (every cell at most QVQ_KAHAN_DIRECT_MAX rows, default 4096), the
+ * segment functions, or the chained evaluation (several ranks, and every qvq_update_kahan_split).
+ * The counters are the function routes': blocks of 64 segments whose functions did not compose,
+ * block functions that did not answer at evaluation, and segments replayed step by step. */
+enum { QVQ_KAHAN_ROUTE_DIRECT = 1, QVQ_KAHAN_ROUTE_FUNCTIONS = 2, QVQ_KAHAN_ROUTE_CHAINED = 3 };
+typedef struct { uint32_t route, blocks_not_composable, block_misses, replays; } qvq_kahan_stats;
+QVQ_API qvq_status qvq_get_kahan_stats(qvq_ctx *ctx, qvq_kahan_stats *out);
 
 /* Decode (replaces CompressedImage::decompress, reference src/Compressor.cpp:156-165, and the
  * getImageFromVectors it calls, src/Compressor.cpp:64-85): raster[x*ySize+y] = the code-vector bytes
@@ -659,6 +670,11 @@ QVQ_API qvq_status qvq_host_kmpp_weight(const uint8_t *codes_a, const uint8_t *c
  * scans their sums in one block: more than segments_cap * block rows make seg_rows grow. */
 typedef struct { uint32_t block, segments, seg_rows, segments_cap; } qvq_kmeanspp_plan;
 QVQ_API qvq_status qvq_host_kmeanspp_plan(uint64_t n, qvq_kmeanspp_plan *out);
+/* The Kahan centroids' sort by cell over K >= 1 keys: window_keys keys per launch
+ * window (one u32 LDS counter each, within the 160 KB of a workgroup), windows = ceil(K /
+ * window_keys) windows, lds_bytes of dynamic LDS per workgroup. */
+typedef struct { uint32_t window_keys, windows, lds_bytes; } qvq_kahan_sort_plan;
+QVQ_API qvq_status qvq_host_kahan_sort_plan(uint32_t K, qvq_kahan_sort_plan *out);
 /* The engine's bounded-wait policy (quant_amd/csrc/wait.hpp) driven by scripted probes, for
  * tests: scenario 0 the work publishes after ~5 ms; 1 it never does, no communicator; 2 it
  * never does, a healthy communicator; 3 the communicator reports an error after ~5 ms; 4 the

@@ -74,6 +74,14 @@ class _KMeansPPPlan(ctypes.Structure):   # qvq_kmeanspp_plan
     _fields_ = [(f, ctypes.c_uint32) for f in ("block", "segments", "seg_rows", "segments_cap")]
 
 
+class _KahanSortPlan(ctypes.Structure):   # qvq_kahan_sort_plan
+    _fields_ = [(f, ctypes.c_uint32) for f in ("window_keys", "windows", "lds_bytes")]
+
+
+class _KahanStats(ctypes.Structure):   # qvq_kahan_stats
+    _fields_ = [(f, ctypes.c_uint32) for f in ("route", "blocks_not_composable", "block_misses", "replays")]
+
+
 class _LloydLevel(ctypes.Structure):   # qvq_lloyd_level
     _fields_ = [("iters", ctypes.c_uint32), ("stop", ctypes.c_uint32), ("changed", ctypes.c_uint64),
                 ("empty", ctypes.c_uint64), ("seeds", ctypes.c_uint64), ("distortion", ctypes.c_double)]
@@ -86,6 +94,8 @@ PLAN_UPDATE_RUNS, PLAN_UPDATE_SORTED, PLAN_UPDATE_LDS = 0, 1, 2
 # qvq_decode_plan enumerators and qvq_host_decode_plan's align_flags (qvq.h)
 DECODE_PIXELS, DECODE_ROWS, DECODE_ROWS_H = 0, 1, 2
 DECODE_RASTER_UNALIGNED, DECODE_ORIG_UNALIGNED, DECODE_INDEX_UNALIGNED, DECODE_CODEBOOK_ODD = 1, 2, 4, 8
+# qvq_kahan_stats.route (qvq.h)
+KAHAN_ROUTE_DIRECT, KAHAN_ROUTE_FUNCTIONS, KAHAN_ROUTE_CHAINED = 1, 2, 3
 
 _lib = None
 EXPORTED = ["qvq_create", "qvq_destroy", "qvq_last_error", "qvq_version", "qvq_set_images",
@@ -102,7 +112,7 @@ EXPORTED = ["qvq_create", "qvq_destroy", "qvq_last_error", "qvq_version", "qvq_s
             "qvq_host_reseed_far_key", "qvq_host_reseed_select", "qvq_host_reseed_grid", "qvq_host_decode_plan",
             "qvq_median_cut", "qvq_host_median_cut_plan", "qvq_host_median_cut_axis",
             "qvq_host_median_cut_select", "qvq_lbg_lloyd", "qvq_kmeanspp", "qvq_host_kmpp_draw",
-            "qvq_host_kmpp_weight", "qvq_host_kmeanspp_plan"]
+            "qvq_host_kmpp_weight", "qvq_host_kmeanspp_plan", "qvq_get_kahan_stats", "qvq_host_kahan_sort_plan"]
 
 COMM_NONE, COMM_RCCL, COMM_HOST = 0, 1, 2
 REFINE_FRESH, REFINE_RESEED = 1, 2            # qvq_refine flags
@@ -185,6 +195,8 @@ def lib():
             "qvq_host_kmpp_draw": ([u64, u64, u64, ctypes.POINTER(u64)], i),
             "qvq_host_kmpp_weight": ([P, P, u32, ctypes.POINTER(u32)], i),
             "qvq_host_kmeanspp_plan": ([u64, ctypes.POINTER(_KMeansPPPlan)], i),
+            "qvq_get_kahan_stats": ([P, ctypes.POINTER(_KahanStats)], i),
+            "qvq_host_kahan_sort_plan": ([u32, ctypes.POINTER(_KahanSortPlan)], i),
         }
         for name, (args, res) in sig.items():
             if os.environ.get("QVQ_LIB") and not hasattr(L, name):
@@ -464,6 +476,13 @@ class Engine:
         _check(lib().qvq_update_kahan_split(self._h, _p(A), K, _p(sp), sp.size - 1, _p(C)), self._h)
         return C
 
+    def kahan_stats(self):
+        """What the last update_kahan / update_kahan_split ran (qvq_get_kahan_stats, test entry): a
+        dict of the qvq_kahan_stats fields; route is one of KAHAN_ROUTE_*."""
+        st = _KahanStats()
+        _check(lib().qvq_get_kahan_stats(self._h, ctypes.byref(st)), self._h)
+        return {f: int(getattr(st, f)) for f, _ in _KahanStats._fields_}
+
     def assign_device_ptr(self):
         return lib().qvq_assign_device(self._h)
 
@@ -619,6 +638,14 @@ def host_ingest_grid():
     g = _IngestGrid()
     _check(lib().qvq_host_ingest_grid(ctypes.byref(g)))
     return {f: int(getattr(g, f)) for f, _ in _IngestGrid._fields_}
+
+
+def host_kahan_sort_plan(K):
+    """The key windows of the Kahan centroids' sort by cell over K keys (qvq_host_kahan_sort_plan): a
+    dict of the qvq_kahan_sort_plan fields."""
+    p = _KahanSortPlan()
+    _check(lib().qvq_host_kahan_sort_plan(int(K), ctypes.byref(p)))
+    return {f: int(getattr(p, f)) for f, _ in _KahanSortPlan._fields_}
 
 
 def host_tile64_grid():

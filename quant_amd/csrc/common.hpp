@@ -581,6 +581,9 @@ struct KahanWork {
     static size_t fn_bytes();
     static size_t segfn_bytes();
     static uint32_t sort_blocks(uint64_t N);
+    // the sort's keys per launch window (its LDS counters) and the windows K keys take: any K sorts
+    static uint32_t sort_window_keys();
+    static uint32_t sort_windows(uint32_t K);
 };
 // C [K][D] = the reference's centroids of assignment A (nullptr: K = 1, the mean of every row):
 // Kahan sums in ascending row order times fl(1/n), empty cells 0, bit for bit (SCALED byte

@@ -283,6 +283,7 @@ struct qvq_ctx {
         } work;
         KahanWork kw;   // view of work, and its capacities
         DevBuf<uint64_t> d_kc_chain;   // chained Kahan sums: gather | state (k_kahan.hip), grown on demand
+        uint32_t last_route = 0;       // qvq_get_kahan_stats: the last qvq_update_kahan* call's route
         // several ranks: the checks whose rows wait for cells summed over every rank's rows (status
         // 2), finished together at the end of qvq_lbg; A_prev stays valid (one assignment buffer per level)
         struct Deferred {
@@ -3326,6 +3327,8 @@ QVQ_API qvq_status qvq_update_kahan(qvq_ctx *ctx, const uint32_t *assign, uint32
     if (st != QVQ_OK) return st;
     if ((st = ensure_kahan(ctx, K)) != QVQ_OK) return st;
     HIPCHK(hipMemcpy(ctx->ts.d_A, assign, ctx->ts.N * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemsetAsync(ctx->kh.kw.stats, 0, 4 * sizeof(unsigned), ctx->stream));   // this call's counters
+    ctx->kh.last_route = QVQ_KAHAN_ROUTE_CHAINED;
     if (ctx->nranks > 1) {   // every rank's rows: the chains pass from rank to rank (kahan_chained)
         if ((st = kahan_chained(ctx, K == 1 ? nullptr : ctx->ts.d_A, K, nullptr, K, false)) != QVQ_OK)
             return st;
@@ -3336,6 +3339,7 @@ QVQ_API qvq_status qvq_update_kahan(qvq_ctx *ctx, const uint32_t *assign, uint32
             for (uint64_t i = 0; i < ctx->ts.N; i++) n[assign[i]]++;   // (checked < K above)
             max_rows = std::max<uint64_t>(1, *std::max_element(n.begin(), n.end()));
         }
+        ctx->kh.last_route = max_rows <= kahan_direct_max() ? QVQ_KAHAN_ROUTE_DIRECT : QVQ_KAHAN_ROUTE_FUNCTIONS;
         HIPCHK(launch_kahan_centroids(ctx->stream, ctx->kh.kw, ctx->ts.d_codes, ctx->ts.Dp, ctx->ts.D, ctx->ts.N,
                                       K == 1 ? nullptr : ctx->ts.d_A, K, ctx->kh.cells.d_kc_cent, nullptr, nullptr, 0, max_rows));
     }
@@ -3343,10 +3347,26 @@ QVQ_API qvq_status qvq_update_kahan(qvq_ctx *ctx, const uint32_t *assign, uint32
     if (env_is("QVQ_KAHAN_DEBUG", "1")) {
         unsigned ms[4];
         HIPCHK(hipMemcpy(ms, ctx->kh.kw.stats, sizeof(ms), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemset(ctx->kh.kw.stats, 0, sizeof(ms)));
         std::fprintf(stderr, "qvq kahan: K %u blocks not composable %u block misses %u replays %u\n", K, ms[0], ms[1],
                      ms[2]);
     }
+    return QVQ_OK;
+}
+
+// Test entry: the route of the last qvq_update_kahan / qvq_update_kahan_split call and the
+// counters its kernels kept (k_kahan.hip Geo::stats).
+QVQ_API qvq_status qvq_get_kahan_stats(qvq_ctx *ctx, qvq_kahan_stats *out) {
+    if (!ctx) return QVQ_EINVAL;
+    GUARD(ctx);
+    if (!out) return fail(ctx, QVQ_EINVAL, "null output");
+    if (!ctx->kh.last_route || !ctx->kh.kw.stats) return fail(ctx, QVQ_ESTATE, "no qvq_update_kahan has run");
+    HIPCHK(hipSetDevice(ctx->dev));
+    unsigned ms[4];
+    HIPCHK(hipMemcpy(ms, ctx->kh.kw.stats, sizeof(ms), hipMemcpyDeviceToHost));
+    out->route = ctx->kh.last_route;
+    out->blocks_not_composable = ms[0];
+    out->block_misses = ms[1];
+    out->replays = ms[2];
     return QVQ_OK;
 }
 
@@ -3371,6 +3391,9 @@ QVQ_API qvq_status qvq_update_kahan_split(qvq_ctx *ctx, const uint32_t *assign, 
     if (st != QVQ_OK) return st;
     HIPCHK(hipMemcpy(ctx->ts.d_A, assign, ctx->ts.N * 4, hipMemcpyHostToDevice));
     const std::vector<uint64_t> cuts(splits, splits + nsplits + 1);
+    if ((st = ensure_kahan(ctx, K)) != QVQ_OK) return st;
+    HIPCHK(hipMemsetAsync(ctx->kh.kw.stats, 0, 4 * sizeof(unsigned), ctx->stream));   // this call's counters
+    ctx->kh.last_route = QVQ_KAHAN_ROUTE_CHAINED;
     if ((st = kahan_chained(ctx, K == 1 ? nullptr : ctx->ts.d_A, K, nullptr, K, false, &cuts)) != QVQ_OK)
         return st;
     return kahan_result(ctx, K, C_out);
@@ -4433,6 +4456,14 @@ QVQ_API qvq_status qvq_host_kmeanspp_plan(uint64_t n, qvq_kmeanspp_plan *out) {
     out->segments = p.segments;
     out->seg_rows = p.seg_rows;
     out->segments_cap = KMPP_SEGMENTS_CAP;
+    return QVQ_OK;
+}
+
+QVQ_API qvq_status qvq_host_kahan_sort_plan(uint32_t K, qvq_kahan_sort_plan *out) {
+    if (!out || K == 0) return QVQ_EINVAL;
+    out->window_keys = KahanWork::sort_window_keys();
+    out->windows = KahanWork::sort_windows(K);
+    out->lds_bytes = std::min(K, out->window_keys) * 4;
     return QVQ_OK;
 }
 

@@ -50,6 +50,12 @@ using kahan::SPB;
 namespace {
 
 constexpr uint32_t SROWS = 1024;   // rows per sort block (one wave)
+// The sort's counters, one u32 per key, live in dynamic LDS: a launch handles a window of at most
+// KS_WIN keys, and more keys take several windows (blockIdx.y): a row whose key lies outside the
+// block's window counts as not asked for there.  The windows write disjoint histogram columns and
+// disjoint positions of the planes, so the stable order is that of one window over every key.
+constexpr uint32_t KS_LDS_MAX = 160 * 1024;
+constexpr uint32_t KS_WIN = KS_LDS_MAX / 4;
 constexpr uint32_t BLK_STEPS = L * SPB;
 
 __device__ inline uint32_t lane_id() { return threadIdx.x & 63; }
@@ -62,18 +68,26 @@ __device__ inline void wave_sync() {
 
 // ---- 1. stable counting sort, writing the planes ----------------------------------------------
 // hist[k][g]: rows of 4096-row block g with index k (transposed: a key's column is contiguous)
-// a row's key: its cell, or with sel its cell's slot; ~0u for a row not summed
-__device__ inline uint32_t ks_key(uint32_t a, uint32_t K, const uint32_t *__restrict__ sel, uint32_t n_sel) {
-    if (!sel) return a < K ? a : ~0u;
-    const uint32_t s = a < n_sel ? sel[a] : 0u;
-    return s ? s - 1 : ~0u;
+// a row's key inside the window [k0, k0 + kw) of the K keys: its cell, or with sel its cell's
+// slot, less k0; ~0u for a row not summed or of another window
+__device__ inline uint32_t ks_key(uint32_t a, uint32_t K, uint32_t k0, uint32_t kw, const uint32_t *__restrict__ sel,
+                                  uint32_t n_sel) {
+    uint32_t key;
+    if (!sel) key = a;
+    else {
+        const uint32_t s = a < n_sel ? sel[a] : 0u;
+        if (!s) return ~0u;
+        key = s - 1;
+    }
+    return key < K && key - k0 < kw ? key - k0 : ~0u;   // (key < k0 wraps past kw)
 }
 
 __global__ __launch_bounds__(64) void ks_hist_kernel(const uint32_t *__restrict__ A, uint64_t N, uint32_t K,
                                                     uint32_t G, uint32_t *__restrict__ hist,
                                                     const uint32_t *__restrict__ sel, uint32_t n_sel) {
     extern __shared__ uint32_t h[];
-    for (uint32_t i = threadIdx.x; i < K; i += 64) h[i] = 0;
+    const uint32_t k0 = blockIdx.y * KS_WIN, kw = min(KS_WIN, K - k0);
+    for (uint32_t i = threadIdx.x; i < kw; i += 64) h[i] = 0;
     __syncthreads();
     // the block's 1024 indices in four 16-byte loads per lane, all in flight before the first
     // use (a load per row and loop trip waited for each: 12.8 us for C3's 16.8 MB)
@@ -95,11 +109,11 @@ __global__ __launch_bounds__(64) void ks_hist_kernel(const uint32_t *__restrict_
     for (int i = 0; i < (int)(SROWS / 256); i++)
 #pragma unroll
         for (int j = 0; j < 4; j++) {
-            const uint32_t a = ks_key(j == 0 ? q[i].x : j == 1 ? q[i].y : j == 2 ? q[i].z : q[i].w, K, sel, n_sel);
+            const uint32_t a = ks_key(j == 0 ? q[i].x : j == 1 ? q[i].y : j == 2 ? q[i].z : q[i].w, K, k0, kw, sel, n_sel);
             if (a != ~0u) atomicAdd(&h[a], 1u);
         }
     __syncthreads();
-    for (uint32_t i = threadIdx.x; i < K; i += 64) hist[(uint64_t)i * G + blockIdx.x] = h[i];
+    for (uint32_t i = threadIdx.x; i < kw; i += 64) hist[(uint64_t)(k0 + i) * G + blockIdx.x] = h[i];
 }
 
 // Per key (a block each): hist[k][g] <- rows of blocks before g with index k; tot[k].
@@ -184,7 +198,8 @@ __global__ __launch_bounds__(64) void ks_scatter_kernel(const uint8_t *__restric
                                                        uint32_t n_sel) {
     constexpr int W = DP / 4;
     extern __shared__ uint32_t cur[];
-    for (uint32_t i = threadIdx.x; i < K; i += 64) cur[i] = koff[i] + hist[(uint64_t)i * G + blockIdx.x];
+    const uint32_t k0 = blockIdx.y * KS_WIN, kw = min(KS_WIN, K - k0);
+    for (uint32_t i = threadIdx.x; i < kw; i += 64) cur[i] = koff[k0 + i] + hist[(uint64_t)(k0 + i) * G + blockIdx.x];
     __syncthreads();
     const uint32_t lane = lane_id();
     constexpr uint32_t NOKEY = (1u << 26) - 1;
@@ -202,7 +217,7 @@ __global__ __launch_bounds__(64) void ks_scatter_kernel(const uint8_t *__restric
         const uint64_t base = r0 + 64 * i;
         if (base >= r1) break;
         const uint64_t r = base + lane;
-        uint32_t a = r < r1 ? ks_key(ak[i], K, sel, n_sel) : ~0u;
+        uint32_t a = r < r1 ? ks_key(ak[i], K, k0, kw, sel, n_sel) : ~0u;
         if (a == ~0u) a = NOKEY;   // a row of a cell not asked for
         if (__ballot(a != NOKEY) == 0) continue;      // (wave-uniform)
         uint32_t w[W];
@@ -229,7 +244,7 @@ __global__ __launch_bounds__(64) void ks_scatter_kernel(const uint8_t *__restric
         for (int u = 0; u < W; u++) row[u] = __shfl(w[u], from, 64);
         if (key != NOKEY) {
             const uint32_t dst = cur[key] + (lane - rs);
-            KCHK(key < K && dst < PL && (uint64_t)(D - 1) * PL + dst < (uint64_t)PL * D + 64);
+            KCHK(key < kw && dst < PL && (uint64_t)(D - 1) * PL + dst < (uint64_t)PL * D + 64);
 #pragma unroll
             for (int d = 0; d < DP; d++)
                 if ((uint32_t)d < D) planes[(uint64_t)d * PL + dst] = (uint8_t)(row[d >> 2] >> (8 * (d & 3)));
@@ -794,6 +809,8 @@ size_t KahanWork::meta_bytes() { return sizeof(SegMeta); }
 size_t KahanWork::fn_bytes() { return sizeof(Fn); }
 size_t KahanWork::segfn_bytes() { return sizeof(kahan::SegFn); }
 uint32_t KahanWork::sort_blocks(uint64_t N) { return (uint32_t)((N + SROWS - 1) / SROWS); }
+uint32_t KahanWork::sort_window_keys() { return KS_WIN; }
+uint32_t KahanWork::sort_windows(uint32_t K) { return (K + KS_WIN - 1) / KS_WIN; }
 
 namespace {
 
@@ -805,8 +822,10 @@ hipError_t kahan_sort(hipStream_t s, const KahanWork &w, const uint8_t *codes, u
         return hipErrorInvalidValue;
     const uint32_t G = KahanWork::sort_blocks(N);
     const uint64_t PL = KahanWork::plane_len(N);
+    // the key windows (KS_WIN): every launch's LDS is within KS_LDS_MAX for any K
+    const uint32_t nwin = KahanWork::sort_windows(K), lds = std::min(K, KS_WIN) * 4;
     if (A) {
-        hipLaunchKernelGGL(ks_hist_kernel, dim3(G), dim3(64), K * 4, s, A, N, K, G, w.hist, sel, n_sel);
+        hipLaunchKernelGGL(ks_hist_kernel, dim3(G, nwin), dim3(64), lds, s, A, N, K, G, w.hist, sel, n_sel);
         hipLaunchKernelGGL(ks_colscan_kernel, dim3(K), dim3(256), 0, s, w.hist, G, w.tot);
     } else {
         if (K != 1) return hipErrorInvalidValue;
@@ -817,7 +836,7 @@ hipError_t kahan_sort(hipStream_t s, const KahanWork &w, const uint8_t *codes, u
 #define X(DPV)                                                                                                     \
     case DPV:                                                                                                      \
         if (A)                                                                                                     \
-            hipLaunchKernelGGL(ks_scatter_kernel<DPV>, dim3(G), dim3(64), K * 4, s, codes, A, N, K, D, G, w.hist,  \
+            hipLaunchKernelGGL(ks_scatter_kernel<DPV>, dim3(G, nwin), dim3(64), lds, s, codes, A, N, K, D, G, w.hist, \
                                w.koff, PL, w.planes, sel, n_sel);                                                  \
         else                                                                                                       \
             hipLaunchKernelGGL(ks_transpose_kernel<DPV>, dim3((uint32_t)((N + 1023) / 1024)), dim3(256), 0, s,     \
