@@ -670,6 +670,19 @@ QVQ_API qvq_status qvq_host_kmpp_weight(const uint8_t *codes_a, const uint8_t *c
  * scans their sums in one block: more than segments_cap * block rows make seg_rows grow. */
 typedef struct { uint32_t block, segments, seg_rows, segments_cap; } qvq_kmeanspp_plan;
 QVQ_API qvq_status qvq_host_kmeanspp_plan(uint64_t n, qvq_kmeanspp_plan *out);
+/* The launch shape of the K = 1 sums (the mean every qvq_lbg starts from) over n rows of dim
+ * components (quant_amd/csrc/mean_plan.hpp, the function the launcher calls): `blocks` summing blocks
+ * of `block` lanes.  A lane adds its rows' exact terms in 16-bit fields, 257 adds of 255 at the most,
+ * and the kernel does not count them: `blocks` is what keeps every lane within that.  The rows go in
+ * groups of group_rows consecutive rows.  chunk_loop (dim <= 16): chunks of chunk_groups groups, chunk
+ * c to wave c mod (blocks * block / 64), chunks_in_flight of them per trip, a group of the chunk per
+ * lane.  Then the groups left (all of them without the chunk loop), the g-th of them to lane g mod
+ * (blocks * block), groups_in_flight per trip; then the last n mod group_rows rows, one each to the first lanes
+ * of block 0.  n: 1 .. 2^32 - 1.  For tests (tests/helpers/sums_capacity_ref.py). */
+typedef struct {
+    uint32_t blocks, block, group_rows, chunk_groups, chunks_in_flight, groups_in_flight, chunk_loop;
+} qvq_mean_grid;
+QVQ_API qvq_status qvq_host_mean_grid(uint64_t n, uint32_t dim, qvq_mean_grid *out);
 /* The Kahan centroids' sort by cell over K >= 1 keys: window_keys keys per launch
  * window (one u32 LDS counter each, within the 160 KB of a workgroup), windows = ceil(K /
  * window_keys) windows, lds_bytes of dynamic LDS per workgroup. */

@@ -74,6 +74,11 @@ class _KMeansPPPlan(ctypes.Structure):   # qvq_kmeanspp_plan
     _fields_ = [(f, ctypes.c_uint32) for f in ("block", "segments", "seg_rows", "segments_cap")]
 
 
+class _MeanGrid(ctypes.Structure):   # qvq_mean_grid
+    _fields_ = [(f, ctypes.c_uint32) for f in ("blocks", "block", "group_rows", "chunk_groups", "chunks_in_flight",
+                                                "groups_in_flight", "chunk_loop")]
+
+
 class _KahanSortPlan(ctypes.Structure):   # qvq_kahan_sort_plan
     _fields_ = [(f, ctypes.c_uint32) for f in ("window_keys", "windows", "lds_bytes")]
 
@@ -112,7 +117,8 @@ EXPORTED = ["qvq_create", "qvq_destroy", "qvq_last_error", "qvq_version", "qvq_s
             "qvq_host_reseed_far_key", "qvq_host_reseed_select", "qvq_host_reseed_grid", "qvq_host_decode_plan",
             "qvq_median_cut", "qvq_host_median_cut_plan", "qvq_host_median_cut_axis",
             "qvq_host_median_cut_select", "qvq_lbg_lloyd", "qvq_kmeanspp", "qvq_host_kmpp_draw",
-            "qvq_host_kmpp_weight", "qvq_host_kmeanspp_plan", "qvq_get_kahan_stats", "qvq_host_kahan_sort_plan"]
+            "qvq_host_kmpp_weight", "qvq_host_kmeanspp_plan", "qvq_get_kahan_stats", "qvq_host_kahan_sort_plan",
+            "qvq_host_mean_grid"]
 
 COMM_NONE, COMM_RCCL, COMM_HOST = 0, 1, 2
 REFINE_FRESH, REFINE_RESEED = 1, 2            # qvq_refine flags
@@ -197,6 +203,7 @@ def lib():
             "qvq_host_kmeanspp_plan": ([u64, ctypes.POINTER(_KMeansPPPlan)], i),
             "qvq_get_kahan_stats": ([P, ctypes.POINTER(_KahanStats)], i),
             "qvq_host_kahan_sort_plan": ([u32, ctypes.POINTER(_KahanSortPlan)], i),
+            "qvq_host_mean_grid": ([u64, u32, ctypes.POINTER(_MeanGrid)], i),
         }
         for name, (args, res) in sig.items():
             if os.environ.get("QVQ_LIB") and not hasattr(L, name):
@@ -724,6 +731,15 @@ def host_kmeanspp_plan(n):
     p = _KMeansPPPlan()
     _check(lib().qvq_host_kmeanspp_plan(int(n), ctypes.byref(p)))
     return {f: int(getattr(p, f)) for f, _ in _KMeansPPPlan._fields_}
+
+
+def host_mean_grid(n, dim):
+    """The launch shape of the K = 1 sums (the mean) over n rows of dim components
+    (qvq_host_mean_grid): a dict of blocks, block, group_rows, chunk_groups, chunks_in_flight,
+    groups_in_flight, chunk_loop."""
+    p = _MeanGrid()
+    _check(lib().qvq_host_mean_grid(int(n), int(dim), ctypes.byref(p)))
+    return {f: int(getattr(p, f)) for f, _ in _MeanGrid._fields_}
 
 
 def host_row_error(x, c, colorspace=SCALED):

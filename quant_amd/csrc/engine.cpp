@@ -40,6 +40,7 @@
 #include "exact_plan.hpp"
 #include "kdtree.hpp"
 #include "kmeanspp_plan.hpp"
+#include "mean_plan.hpp"
 #include "kmeanspp_rule.hpp"
 #include "median_cut_plan.hpp"
 #include "median_cut_rule.hpp"
@@ -4456,6 +4457,19 @@ QVQ_API qvq_status qvq_host_kmeanspp_plan(uint64_t n, qvq_kmeanspp_plan *out) {
     out->segments = p.segments;
     out->seg_rows = p.seg_rows;
     out->segments_cap = KMPP_SEGMENTS_CAP;
+    return QVQ_OK;
+}
+
+QVQ_API qvq_status qvq_host_mean_grid(uint64_t n, uint32_t dim, qvq_mean_grid *out) {
+    if (!out || n == 0 || n > 0xFFFFFFFFull || dim == 0 || dim > 64) return QVQ_EINVAL;
+    const MeanPlan p = mean_plan(n, (dim + 3) & ~3u);   // the plan launch_mean_sums launches
+    out->blocks = (uint32_t)p.grid;
+    out->block = p.threads;
+    out->group_rows = p.group_rows;
+    out->chunk_groups = p.chunk_groups;
+    out->chunks_in_flight = p.chunks_in_flight;
+    out->groups_in_flight = p.groups_in_flight;
+    out->chunk_loop = p.chunk_loop;
     return QVQ_OK;
 }
 

@@ -6,6 +6,7 @@
 // Workgroup slabs (update kernels): part[g][d][k] packed (hi << 32 | lo), part_cnt[g][k].
 #include "common.hpp"
 #include "decode_plan.hpp"
+#include "mean_plan.hpp"
 #include "mfma_util.hpp"
 
 namespace qvq {
@@ -659,12 +660,11 @@ hipError_t launch_reduce(hipStream_t s, const uint64_t *part, const uint32_t *pa
 // buffer is cleared once at creation and again by the finalize that consumes it).  A thread takes
 // groups of 4 consecutive rows (4*DP bytes: DP/4 16-byte loads), two groups per trip so the
 // loads of both are in flight together, and adds each component's exact term as
-// (b ^ 0x80) << 16 | lo8[b] in u32 registers: the grid gives every thread at most 256 rows,
-// so neither 16-bit field carries.  Block 0 also writes the quantize's initial state (the
-// distortion inputs, zeroed counters), which saves two host calls per quantize.
-constexpr int MEAN_THREADS = 1024;
-constexpr uint64_t MEAN_ROWS_PER_THREAD = 256;
-constexpr int MEAN_U = 4;   // groups of 4 rows in flight per thread
+// (b ^ 0x80) << 16 | lo8[b] in u32 registers: neither 16-bit field carries while a thread makes
+// at most MEAN_FIELD_ADDS adds, which the kernel does not count: the launcher's grid (mean_plan.hpp,
+// with the constants of these loops) keeps every thread within them.  The last block writes the
+// quantize's initial state (the distortion inputs, zeroed counters), which saves two host calls
+// per quantize.
 struct MeanInit {
     unsigned *zero;     // n_zero counters to clear
     uint32_t n_zero;
@@ -715,7 +715,7 @@ __device__ void hist_moments(const uint64_t *hist, const double *v64, uint32_t D
 // time as 16-bit fields (u of components 4q, 4q+2 in ue[q], of 4q+1, 4q+3 in uo[q]: three VALU
 // per word), the low parts (<= 128 each) from a 256-BYTE LDS table (ds_read_u8: at most two
 // lanes' dwords per bank, where a dword table conflicts up to 8-way), also as 16-bit fields.
-// <= MEAN_ROWS_PER_THREAD rows per thread keep every field from carrying.
+// <= MEAN_FIELD_ADDS adds per thread (mean_plan's grid) keep every field from carrying.
 template <int DP>
 __global__ __launch_bounds__(MEAN_THREADS) void mean_sums_kernel(const uint8_t *__restrict__ codes, uint64_t N,
                                                                  uint32_t D, const uint64_t *__restrict__ plut,
@@ -750,12 +750,12 @@ __global__ __launch_bounds__(MEAN_THREADS) void mean_sums_kernel(const uint8_t *
     constexpr int Q = DP / 4;   // 16-byte loads per group of 4 rows
     const uint64_t groups = N / 4;
     uint64_t g_begin = 0;   // groups before this are done by the wave-chunk loop
-    if constexpr (Q <= 4) {
+    if constexpr (mean_chunk_loop(DP)) {
         // Wave chunks of 64 groups (64 Q 16-byte words), loaded lane-contiguously: load j of lane
         // l is 16-byte word 64 j + l of the chunk, whose 4-byte word k is word 4(64 j + l) + k,
         // i.e. component quad (256 j + 4 l + k) mod Q.  Words go to slot (256 j + k) mod Q; the
         // lane's slots are rotated by 4 l mod Q at the end.  MEAN_U chunks per trip in flight.
-        const uint64_t chunks = groups / 64;
+        const uint64_t chunks = groups / MEAN_CHUNK_GROUPS;
         const uint64_t wave_id = (uint64_t)blockIdx.x * (MEAN_THREADS / 64) + (threadIdx.x >> 6);
         const uint64_t nwaves = (uint64_t)nblk * (MEAN_THREADS / 64);
         const int lane = threadIdx.x & 63;
@@ -802,11 +802,11 @@ __global__ __launch_bounds__(MEAN_THREADS) void mean_sums_kernel(const uint8_t *
             lo2[2 * qd] = l2[2 * qd];
             lo2[2 * qd + 1] = l2[2 * qd + 1];
         }
-        g_begin = chunks * 64;
+        g_begin = chunks * MEAN_CHUNK_GROUPS;
     }
     // groups past the wave chunks (every group for wide rows): one group per thread, MEAN_U
     // groups per trip with all their loads issued first
-    constexpr int U = DP <= 16 ? MEAN_U : (DP <= 32 ? 2 : 1);   // (wide rows: fewer, by registers)
+    constexpr int U = mean_groups_in_flight(DP);
     const uint64_t stride = (uint64_t)nblk * MEAN_THREADS;
     for (uint64_t g = g_begin + (uint64_t)blockIdx.x * MEAN_THREADS + threadIdx.x; g < groups; g += U * stride) {
         if constexpr (DP > 32) {   // wide rows: the group's 16-byte loads one by one (registers)
@@ -877,13 +877,7 @@ hipError_t launch_mean_sums(hipStream_t s, uint32_t Dp, const uint8_t *codes, ui
                             const uint64_t *plut, uint64_t *sums, unsigned *zero, uint32_t n_zero, double *dist,
                             const uint64_t *hist, const double *v64) {
     if (n_zero > MEAN_THREADS) return hipErrorInvalidValue;
-    // one block per CU (few same-address atomics at the end), more only where a thread would
-    // otherwise take over MEAN_ROWS_PER_THREAD rows (u32 fields)
-    constexpr uint64_t grid_cap = 256;
-    const uint64_t per_block = MEAN_THREADS * MEAN_ROWS_PER_THREAD;
-    const uint64_t grid_min = (N + per_block - 1) / per_block;
-    const uint64_t grid = std::max<uint64_t>(std::max<uint64_t>(grid_min, 1),
-                                             std::min<uint64_t>((N + 4 * MEAN_THREADS - 1) / (4 * MEAN_THREADS), grid_cap));
+    const uint64_t grid = mean_plan(N, Dp).grid;   // the grid that keeps every thread's fields from carrying
     if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
     const MeanInit init{zero, n_zero, dist, hist, v64};
     switch (Dp) {
