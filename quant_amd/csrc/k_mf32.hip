@@ -176,8 +176,26 @@ __global__ __launch_bounds__(M32_THREADS) void assign_mf32_kernel(
             q[3 * T + 2] = p[2];
         }
     };
-    uint64_t chunk = (uint64_t)blockIdx.x * M32_WAVES + wave;
+    // The workgroup's chunks are its slots s = 0, 1, ...: chunk 16 blockIdx + s % 16 + (s / 16)
+    // stride, increasing in s.  Wave w starts on slot w and claims every further slot from a
+    // counter in LDS (the flag list's scratch word, free until the flush), so a wave that runs
+    // ahead takes more chunks.  The SIMD issues its oldest wave first: with 16 chunks fixed per
+    // wave (C3, K = 128) the four waves of a SIMD left the loop at 54, 63, 77 and 91 % of the
+    // launch, the youngest running a seventh of it alone, far below the rate the SIMD reaches
+    // with three or four waves (clock stamps, profiles/chunk_loop).  Which rows a workgroup
+    // takes does not depend on it, nor do its sums and its slab.  Without room for the list
+    // (fcap 0) the waves keep their fixed chunks.
     const uint64_t stride = (uint64_t)gridDim.x * M32_WAVES;
+    const bool dyn = L.fcap != 0;
+    auto slot_chunk = [&](uint32_t s) {
+        return (uint64_t)blockIdx.x * M32_WAVES + (s & (M32_WAVES - 1)) + (uint64_t)(s / M32_WAVES) * stride;
+    };
+    auto claim = [&]() {   // lane 0's value is the slot: read (readfirstlane) a chunk later
+        uint32_t v = 0;
+        if (lane == 0) v = atomicAdd(&fl[1], 1u);
+        return v;
+    };
+    uint64_t chunk = slot_chunk((uint32_t)wave);
     uint32_t qn[6];
     load_codes(chunk, qn);   // the first chunk's rows go out before the LDS staging, under its latency
     m32_stage_pq(lds, L.q, g_rows, Kp, tid, ROWS0, PRUNE ? g_perm : nullptr);
@@ -189,6 +207,7 @@ __global__ __launch_bounds__(M32_THREADS) void assign_mf32_kernel(
         for (uint32_t i = tid; i < Kp * (MF_D / 4); i += M32_THREADS) dst[i] = src[i];
     }
     if (tid == 0) fl[0] = 0;
+    if (tid == 0 && dyn) fl[1] = M32_WAVES;   // the first slot no wave starts on
     if (FUSE) {
         for (uint32_t i = tid; i < copies * m32_sum_stride(K, copies); i += M32_THREADS) sums[i] = 0;
         for (uint32_t i = tid; i < copies * m32_cnt_stride(K, copies); i += M32_THREADS) cnt[i] = 0;
@@ -238,12 +257,17 @@ __global__ __launch_bounds__(M32_THREADS) void assign_mf32_kernel(
         ring[j] = (scp * m32_sum_stride(K, copies) + d * m32_kstride(K)) * 8;
     }
 
-    for (; chunk < nchunks; chunk += stride) {
+    uint32_t after = dyn ? claim() : 0;   // the slot after this wave's first
+    while (chunk < nchunks) {
         const uint64_t base = chunk * M32_ROWS;
         uint32_t q[6];
 #pragma unroll
         for (int i = 0; i < 6; i++) q[i] = qn[i];
-        load_codes(chunk + stride, qn);   // prefetch the next chunk under this one's search
+        // the next chunk: claimed a chunk ago, so the claim's round trip lay under that chunk's search
+        const uint64_t next =
+            dyn ? slot_chunk((uint32_t)__builtin_amdgcn_readfirstlane((int)after)) : chunk + stride;
+        load_codes(next, qn);   // prefetch the next chunk under this one's search
+        if (dyn) after = claim();
         const uint32_t own[3] = {h ? q[3] : q[0], h ? q[4] : q[1], h ? q[5] : q[2]};
         half8 b1[2], b2[2];
 #pragma unroll
@@ -489,6 +513,7 @@ __global__ __launch_bounds__(M32_THREADS) void assign_mf32_kernel(
                 }
             }
         }
+        chunk = next;
     }
     __syncthreads();
     flag_list_flush(fl, L.fcap, tid, M32_THREADS, flags, flag_cnt);

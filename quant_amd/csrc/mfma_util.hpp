@@ -199,7 +199,8 @@ __device__ inline void pair_update2(const f32x4 &p0, const f32x4 &p1, uint32_t p
 
 // A workgroup's flagged rows, kept in LDS and appended to the global list with one add per
 // workgroup.  fl (LDS, 8 + 4 cap bytes): [0] rows listed so far (cleared before the first call,
-// behind a barrier), [1] scratch, [2 ..] cap rows.  A returning device-scope atomic per flagged
+// behind a barrier), [1] scratch of the flush (until then the caller's: assign_mf32_kernel
+// counts its claimed chunks there), [2 ..] cap rows.  A returning device-scope atomic per flagged
 // row, all on one counter, parked the row's wave for its round trip behind every other
 // workgroup's adds (C3, K = 64: 7,478 rows, 28 us of the launch's 88).  Rows past the list's end
 // still go that way.  The global list's order was and is arbitrary: the rechecks' sums are
