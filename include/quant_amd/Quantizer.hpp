@@ -55,3 +55,6 @@ QuantizerPtr getMedianCutQuantizer(size_t refineIters = 0, bool fresh = false, b
 // any other training set throws std::runtime_error with the engine's message.  getQuantizer and the
 // Quantizers enum have no slot for it (3 is the reference's ABC); compress() records LBG.
 QuantizerPtr getKMeansPPQuantizer(uint64_t seed, size_t refineIters = 0, bool fresh = false, bool reseed = false);
+// The same with k-means|| seeding (qvq_kmeans_par, include/qvq.h, default options): a few passes over
+// the rows in place of K - 1.  n <= 16.
+QuantizerPtr getKMeansParQuantizer(uint64_t seed, size_t refineIters = 0, bool fresh = false, bool reseed = false);

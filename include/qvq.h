@@ -409,6 +409,66 @@ typedef struct { uint32_t placed; } qvq_kmeanspp_info;
 QVQ_API qvq_status qvq_kmeanspp(qvq_ctx *ctx, uint32_t K, uint64_t seed, double *codebook, uint32_t *rows,
                                 uint64_t *potential, qvq_kmeanspp_info *info);
 
+/*
+ * k-means|| seeding on the device (Bahmani, Moseley, Vattani, Kumar, Vassilvitskii, "Scalable
+ * K-Means++", VLDB 2012): qvq_kmeanspp's K - 1 dependent passes over the rows become `rounds` passes.
+ * In each, every row decides independently whether it becomes a candidate; the candidates are weighted
+ * by the rows nearest to them, and a weighted k-means++ over the candidates picks the K seeds.  The
+ * reference has no such quantizer: this text is the rule.  One rank's byte path, in qvq_kmeanspp's
+ * terms: the ordinals o = (uint8)(code ^ 0x80), the weight w(a, b) = sum over d < Dp of
+ * (o[a][d] - o[b][d])^2, an exact integer below 2^22, and mix and draw(seed, j, T) as above.
+ * mulhi64(a, b) is the high 64 bits of the 128-bit product.
+ *
+ * Options (opts may be NULL; a 0 field is its default): rounds = 5, ell = K, round_cap = 2 * ell + 64.
+ * 1. Candidate 0: c_0 = draw(seed, 0, N), qvq_kmeanspp's first seed.  m[row] = w(row, c_0),
+ *    near[row] = 0, potential[0] = sum of m.  M = 1.
+ * 2. Rounds r = 1 .. rounds: phi = sum of m (u64); phi = 0: the rounds end.  key_r = mix(seed + r),
+ *    u(r, row) = mix(key_r + row).  Row `row` joins iff mulhi64(u(r, row), phi) < ell * m[row]: strict,
+ *    the right side below 2^39; a row with m = 0 never joins.  The joining rows become candidates M,
+ *    M + 1, ... in ascending row order; if more than round_cap join, the round_cap lowest rows are
+ *    taken and `truncated` counts the round.  Then for every row and every new candidate c in index
+ *    order: if w(row, c) < m[row] then m[row] = w, near[row] = c (strict: the lowest index keeps a tie).
+ *    potential[r] = sum of m; rounds_run = r; round_candidates[r - 1] = the candidates added.
+ * 3. Weights: wt[c] = the rows with near = c; their sum is N.  Two equal rows that join in one round
+ *    give a candidate of weight 0: it is legal and is never drawn below.
+ * 4. Reduction: weighted k-means++ over the M candidates, draws from the stream seed + 2^32.
+ *    s_0 = the lowest c with (sum of wt[i] over i <= c) > draw(seed + 2^32, 0, N); g[c] = w(c, s_0).
+ *    For j = 1 .. K - 1: T = sum of wt[c] * g[c] (below 2^54); T = 0: placed = j, stop.  Else
+ *    t = draw(seed + 2^32, j, T), s_j = the lowest c whose prefix of wt * g exceeds t, g = min(g, w(., s_j)).
+ *    Without a stop placed = K.  K > M is legal and gives placed <= M.
+ *
+ * Outputs (caller-owned host memory, any may be NULL, written only after the bounded wait has
+ * succeeded): rows (K): the training row of s_j, 0xFFFFFFFF from placed on; codebook (K x dim fp64):
+ * entry j < placed that row's values as qvq_get_vectors gives them, the zero vector from placed on;
+ * cand_rows and cand_weights (1 + rounds * round_cap entries each, qvq_host_kmeans_par_plan's
+ * max_candidates): the candidates' rows and wt, entries from M on 0xFFFFFFFF and 0; info: placed,
+ * candidates = M, rounds_run, truncated, round_candidates (0 for rounds not run) and potential
+ * (entries 0 .. rounds_run; 0 after).
+ *
+ * The call uses device buffers of its own (m, near, the join bits, per-segment sums and counts, the
+ * candidate list) and touches nothing resident: qvq_assign_device, the C_start == NULL continuation
+ * of qvq_refine and a later qvq_lbg behave as if it had not happened.  Errors, in this order, each
+ * leaving the context as it was: QVQ_ESTATE without a training set; QVQ_EINVAL for K = 0 or K > 2^16,
+ * rounds > 16, ell > 2^17, round_cap < 1 or 1 + rounds * round_cap > 2^20 (after the defaults);
+ * QVQ_EUNSUPPORTED for an exact-mode set; QVQ_EUNSUPPORTED with any communicator joined.
+ * qvq_get_timings reports levels = 0 and the call's total_ms; under qvq_set_timing(-3) also, per round
+ * r, other_ms[r - 1] the sample and assign_ms[r - 1] the update, update_ms[0] candidate 0's pass,
+ * update_ms[1] the weights and update_ms[2] the reduction (device ms).
+ * (qvq_host_kmeans_par_join is the sampling test on the host.)
+ */
+typedef struct { uint32_t rounds, ell, round_cap; } qvq_kmeans_par_opts;   /* a 0 field = its default */
+typedef struct {
+    uint32_t placed;               /* seeds placed, <= K */
+    uint32_t candidates;           /* M */
+    uint32_t rounds_run;           /* rounds that sampled (they stop early when phi = 0) */
+    uint32_t truncated;            /* rounds whose sample passed round_cap */
+    uint32_t round_candidates[16]; /* candidates added per round */
+    uint64_t potential[17];        /* phi after candidate 0, then after each round run */
+} qvq_kmeans_par_info;
+QVQ_API qvq_status qvq_kmeans_par(qvq_ctx *ctx, uint32_t K, uint64_t seed, const qvq_kmeans_par_opts *opts,
+                                  double *codebook, uint32_t *rows, uint32_t *cand_rows, uint64_t *cand_weights,
+                                  qvq_kmeans_par_info *info);
+
 /* Single steps over the current training set, for tests and benchmarks.
  * qvq_assign: nearest code vector of every row for codebook C (K x dim fp64, host),
  *   with the same MFMA/VALU search + fp64 recheck + kd-tree tie resolution as qvq_lbg.
@@ -670,6 +730,27 @@ QVQ_API qvq_status qvq_host_kmpp_weight(const uint8_t *codes_a, const uint8_t *c
  * scans their sums in one block: more than segments_cap * block rows make seg_rows grow. */
 typedef struct { uint32_t block, segments, seg_rows, segments_cap; } qvq_kmeanspp_plan;
 QVQ_API qvq_status qvq_host_kmeanspp_plan(uint64_t n, qvq_kmeanspp_plan *out);
+/* qvq_kmeans_par's sampling test on the host (quant_amd/csrc/kmeans_par_rule.hpp, the text the kernels
+ * run): *joins = mulhi64(mix(mix(seed + r) + row), phi) < ell * m.  r in 1 .. 16, ell <= 2^17, m < 2^22
+ * (QVQ_EINVAL otherwise). */
+QVQ_API qvq_status qvq_host_kmeans_par_join(uint64_t seed, uint32_t r, uint64_t row, uint64_t phi, uint32_t ell, uint32_t m,
+                                            int *joins);
+/* qvq_kmeans_par's options with the defaults filled in and its launch shape over n rows of dim
+ * components (quant_amd/csrc/kmeans_par_plan.hpp, the functions the entry point calls; QVQ_EINVAL
+ * where qvq_kmeans_par gives it).  The row passes take qvq_kmeanspp's segments (block, segments,
+ * seg_rows, segments_cap as in qvq_kmeanspp_plan); the update holds `chunk` new candidates in LDS per
+ * trip; max_candidates = 1 + rounds * round_cap is the length of cand_rows and cand_weights.  The
+ * reduction is one block of reduce_block lanes with lds_bytes of dynamic LDS: gw_lds: g and wt per
+ * candidate sit there (global memory otherwise), codes_lds: so do the candidates' code words.  Both
+ * follow from max_candidates and the padded width, not from the M a call reaches. */
+typedef struct {
+    uint32_t rounds, ell, round_cap;
+    uint32_t block, segments, seg_rows, segments_cap;
+    uint32_t chunk, max_candidates;
+    uint32_t reduce_block, gw_lds, codes_lds, lds_bytes;
+} qvq_kmeans_par_plan;
+QVQ_API qvq_status qvq_host_kmeans_par_plan(uint64_t n, uint32_t dim, uint32_t K, const qvq_kmeans_par_opts *opts,
+                                            qvq_kmeans_par_plan *out);
 /* The launch shape of the K = 1 sums (the mean every qvq_lbg starts from) over n rows of dim
  * components (quant_amd/csrc/mean_plan.hpp, the function the launcher calls): `blocks` summing blocks
  * of `block` lanes.  A lane adds its rows' exact terms in 16-bit fields, 257 adds of 255 at the most,

@@ -74,6 +74,22 @@ class _KMeansPPPlan(ctypes.Structure):   # qvq_kmeanspp_plan
     _fields_ = [(f, ctypes.c_uint32) for f in ("block", "segments", "seg_rows", "segments_cap")]
 
 
+class _KMeansParOpts(ctypes.Structure):   # qvq_kmeans_par_opts
+    _fields_ = [(f, ctypes.c_uint32) for f in ("rounds", "ell", "round_cap")]
+
+
+class _KMeansParInfo(ctypes.Structure):   # qvq_kmeans_par_info
+    _fields_ = [("placed", ctypes.c_uint32), ("candidates", ctypes.c_uint32), ("rounds_run", ctypes.c_uint32),
+                ("truncated", ctypes.c_uint32), ("round_candidates", ctypes.c_uint32 * 16),
+                ("potential", ctypes.c_uint64 * 17)]
+
+
+class _KMeansParPlan(ctypes.Structure):   # qvq_kmeans_par_plan
+    _fields_ = [(f, ctypes.c_uint32) for f in ("rounds", "ell", "round_cap", "block", "segments", "seg_rows",
+                                                "segments_cap", "chunk", "max_candidates", "reduce_block", "gw_lds",
+                                                "codes_lds", "lds_bytes")]
+
+
 class _MeanGrid(ctypes.Structure):   # qvq_mean_grid
     _fields_ = [(f, ctypes.c_uint32) for f in ("blocks", "block", "group_rows", "chunk_groups", "chunks_in_flight",
                                                 "groups_in_flight", "chunk_loop")]
@@ -118,7 +134,7 @@ EXPORTED = ["qvq_create", "qvq_destroy", "qvq_last_error", "qvq_version", "qvq_s
             "qvq_median_cut", "qvq_host_median_cut_plan", "qvq_host_median_cut_axis",
             "qvq_host_median_cut_select", "qvq_lbg_lloyd", "qvq_kmeanspp", "qvq_host_kmpp_draw",
             "qvq_host_kmpp_weight", "qvq_host_kmeanspp_plan", "qvq_get_kahan_stats", "qvq_host_kahan_sort_plan",
-            "qvq_host_mean_grid"]
+            "qvq_host_mean_grid", "qvq_kmeans_par", "qvq_host_kmeans_par_join", "qvq_host_kmeans_par_plan"]
 
 COMM_NONE, COMM_RCCL, COMM_HOST = 0, 1, 2
 REFINE_FRESH, REFINE_RESEED = 1, 2            # qvq_refine flags
@@ -201,6 +217,9 @@ def lib():
             "qvq_host_kmpp_draw": ([u64, u64, u64, ctypes.POINTER(u64)], i),
             "qvq_host_kmpp_weight": ([P, P, u32, ctypes.POINTER(u32)], i),
             "qvq_host_kmeanspp_plan": ([u64, ctypes.POINTER(_KMeansPPPlan)], i),
+            "qvq_kmeans_par": ([P, u32, u64, ctypes.POINTER(_KMeansParOpts), P, P, P, P, ctypes.POINTER(_KMeansParInfo)], i),
+            "qvq_host_kmeans_par_join": ([u64, u32, u64, u64, u32, u32, ctypes.POINTER(ctypes.c_int)], i),
+            "qvq_host_kmeans_par_plan": ([u64, u32, u32, ctypes.POINTER(_KMeansParOpts), ctypes.POINTER(_KMeansParPlan)], i),
             "qvq_get_kahan_stats": ([P, ctypes.POINTER(_KahanStats)], i),
             "qvq_host_kahan_sort_plan": ([u32, ctypes.POINTER(_KahanSortPlan)], i),
             "qvq_host_mean_grid": ([u64, u32, ctypes.POINTER(_MeanGrid)], i),
@@ -445,6 +464,28 @@ class Engine:
         _check(lib().qvq_kmeanspp(self._h, K, int(seed) & 0xFFFFFFFFFFFFFFFF, _p(C), _p(rows), _p(pot),
                                   ctypes.cast(ctypes.byref(placed), ctypes.c_void_p)), self._h)
         return C, rows, pot, int(placed.value)
+
+    def kmeans_par(self, K, seed=0, rounds=0, ell=0, round_cap=0):
+        """k-means|| seeding on the device (qvq_kmeans_par, the rule in qvq.h): (codebook, rows,
+        cand_rows, cand_weights, info).  A 0 option is its default (rounds 5, ell K, round_cap
+        2 ell + 64).  codebook[j] holds the values of training row rows[j] for j < info["placed"] and
+        zeros after; rows[j] is 0xFFFFFFFF from placed on.  cand_rows and cand_weights have
+        host_kmeans_par_plan's max_candidates entries, 0xFFFFFFFF and 0 from info["candidates"] on.
+        info: placed, candidates, rounds_run, truncated, round_candidates (16) and potential (17) as
+        lists.  K in 1 .. 2**16; one rank's byte path.  The codebook is a start for refine(C=...);
+        nothing resident changes."""
+        K = int(K)
+        opts = _KMeansParOpts(int(rounds), int(ell), int(round_cap))
+        try:
+            n_cand = host_kmeans_par_plan(max(self.n, 1), self.dim or 1, K, rounds, ell, round_cap)["max_candidates"]
+        except QVQError:
+            n_cand = 1   # outside the limits: the call below reports it, in the contract's order
+        C = np.empty((max(K, 0), self.dim), np.float64)
+        rows, crows, cwt = np.empty(K, np.uint32), np.empty(n_cand, np.uint32), np.empty(n_cand, np.uint64)
+        info = _KMeansParInfo()
+        _check(lib().qvq_kmeans_par(self._h, K, int(seed) & 0xFFFFFFFFFFFFFFFF, ctypes.byref(opts), _p(C), _p(rows),
+                                    _p(crows), _p(cwt), ctypes.byref(info)), self._h)
+        return C, rows, crows, cwt, _kmeans_par_info(info)
 
     def refine_reseeds(self):
         """The seeds the last refine() placed in each iteration (qvq_get_refine_reseeds)."""
@@ -725,6 +766,32 @@ def host_kmpp_weight(codes_a, codes_b):
     return int(w.value)
 
 
+def _kmeans_par_info(info):
+    return {"placed": int(info.placed), "candidates": int(info.candidates), "rounds_run": int(info.rounds_run),
+            "truncated": int(info.truncated), "round_candidates": [int(v) for v in info.round_candidates],
+            "potential": [int(v) for v in info.potential]}
+
+
+def host_kmeans_par_join(seed, r, row, phi, ell, m):
+    """The sampling test of qvq_kmeans_par's rule (qvq_host_kmeans_par_join): does `row` with weight m
+    join round r under potential phi."""
+    j = ctypes.c_int()
+    _check(lib().qvq_host_kmeans_par_join(int(seed) & 0xFFFFFFFFFFFFFFFF, int(r), int(row), int(phi), int(ell), int(m),
+                                          ctypes.byref(j)))
+    return bool(j.value)
+
+
+def host_kmeans_par_plan(n, dim, K, rounds=0, ell=0, round_cap=0):
+    """qvq_kmeans_par's options with the defaults filled in and its launch shape over n rows of dim
+    components (qvq_host_kmeans_par_plan): a dict of rounds, ell, round_cap, block, segments, seg_rows,
+    segments_cap, chunk, max_candidates, reduce_block, gw_lds, codes_lds, lds_bytes.  Raises QVQError
+    (status 1) outside the contract's limits."""
+    p = _KMeansParPlan()
+    opts = _KMeansParOpts(int(rounds), int(ell), int(round_cap))
+    _check(lib().qvq_host_kmeans_par_plan(int(n), int(dim), int(K), ctypes.byref(opts), ctypes.byref(p)))
+    return {f: int(getattr(p, f)) for f, _ in _KMeansParPlan._fields_}
+
+
 def host_kmeanspp_plan(n):
     """The launch shape of qvq_kmeanspp's update pass over n rows (qvq_host_kmeanspp_plan): a dict of
     block, segments, seg_rows, segments_cap."""
@@ -951,6 +1018,35 @@ class KMeansPPQuantizer(AbstractQuantizer):
         dev = getattr(trainingSet, "is_cuda", False)
         self._engine.set_vectors(trainingSet if dev else np.asarray(trainingSet, np.float64))
         C = self._engine.kmeanspp(1 << int(n), self._seed)[0]
+        return self._engine.refine(C=C, max_iters=self._refine_iters, eps=eps,
+                                   fresh=self._fresh or self._refine_iters == 0, reseed=self._reseed)[:3]
+
+
+class KMeansParQuantizer(AbstractQuantizer):
+    """k-means|| seeding on the MI355X engine (Engine.kmeans_par) and Lloyd refinement from the seeds.
+    The reference has no such quantizer and the Quantizers enum no slot for it."""
+
+    def __init__(self, device=0, seed=0, refine_iters=0, fresh=False, reseed=False, rounds=0, ell=0, round_cap=0):
+        """quantize seeds 2**n code vectors with `seed` (rounds, ell, round_cap: Engine.kmeans_par's
+        options, 0 the default), then runs Engine.refine from them for up to refine_iters iterations
+        stopped by eps.  refine_iters = 0 returns the nearest-seed assignment (a fresh assignment with
+        no iteration).  reseed needs refine_iters > 0."""
+        if reseed and int(refine_iters) <= 0:
+            raise QVQError(1, "reseed needs refine_iters > 0")
+        self._device = device
+        self._engine = None
+        self._seed = int(seed)
+        self._refine_iters = int(refine_iters)
+        self._fresh = bool(fresh)
+        self._reseed = bool(reseed)
+        self._opts = (int(rounds), int(ell), int(round_cap))
+
+    def quantize(self, trainingSet, n, eps):
+        if self._engine is None:
+            self._engine = Engine(self._device)
+        dev = getattr(trainingSet, "is_cuda", False)
+        self._engine.set_vectors(trainingSet if dev else np.asarray(trainingSet, np.float64))
+        C = self._engine.kmeans_par(1 << int(n), self._seed, *self._opts)[0]
         return self._engine.refine(C=C, max_iters=self._refine_iters, eps=eps,
                                    fresh=self._fresh or self._refine_iters == 0, reseed=self._reseed)[:3]
 

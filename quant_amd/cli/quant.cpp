@@ -54,7 +54,8 @@ struct Params {   // include/ProgramParameters.hpp:5-19, defaults of src/main.cp
     bool reseed = false;  // --reseed: the iterations reseed their empty cells
     int lloyd = 0;        // --lloyd: Lloyd iterations at every level (0: qvq_lbg's one assignment per level)
     bool kmeanspp = false;   // --init kmeans++: the codebook starts from k-means++ seeds (default split: LBG's schedule)
-    uint64_t seed = 0;       // --seed: of the k-means++ draws
+    bool kmeanspar = false;  // --init kmeans-par: ... from k-means|| seeds
+    uint64_t seed = 0;       // --seed: of the k-means++ / k-means|| draws
     std::string file, saveto;
 };
 
@@ -76,9 +77,10 @@ const char *kHelp =
     "  --fresh                Indices re-assigned to the written codebook\n"
     "  --reseed               Empty cells reseeded from the worst cells (with --refine or --lloyd)\n"
     "  --lloyd arg (=0)       Lloyd iterations after every split (LBG, stopped by -e)\n"
-    "  --init arg (=split)    Starting codebook: split (LBG's schedule) or kmeans++ (2^n training\n"
-    "                         rows by D^2-sampling, then --refine iterations; -q 0, not with --lloyd)\n"
-    "  --seed arg (=0)        Seed of the kmeans++ draws\n";
+    "  --init arg (=split)    Starting codebook: split (LBG's schedule), kmeans++ (2^n training\n"
+    "                         rows by D^2-sampling) or kmeans-par (the same from a few sampling\n"
+    "                         passes, n <= 16), then --refine iterations; -q 0, not with --lloyd\n"
+    "  --seed arg (=0)        Seed of the kmeans++ / kmeans-par draws\n";
 
 bool parse_bool(const std::string &v) {   // program_options' bool values
     if (v == "1" || v == "true" || v == "yes" || v == "on") return true;
@@ -153,9 +155,10 @@ bool parse(int argc, char **argv, Params &p) {
             if (p.lloyd < 0) throw std::invalid_argument("the argument ('" + val + "') for option '--lloyd' is invalid");
         }
         else if (key == "init") {
-            if (val != "split" && val != "kmeans++")
+            if (val != "split" && val != "kmeans++" && val != "kmeans-par")
                 throw std::invalid_argument("the argument ('" + val + "') for option '--init' is invalid");
             p.kmeanspp = val == "kmeans++";
+            p.kmeanspar = val == "kmeans-par";
         }
         else if (key == "seed") {
             size_t pos = 0;
@@ -184,6 +187,10 @@ bool parse(int argc, char **argv, Params &p) {
         throw std::invalid_argument("option '--init kmeans++' needs the LBG quantizer");
     if (p.kmeanspp && p.lloyd > 0)
         throw std::invalid_argument("option '--init kmeans++' cannot be combined with '--lloyd'");
+    if (p.kmeanspar && p.quantizer != (int)Quantizers::LBG)
+        throw std::invalid_argument("option '--init kmeans-par' needs the LBG quantizer");
+    if (p.kmeanspar && p.lloyd > 0)
+        throw std::invalid_argument("option '--init kmeans-par' cannot be combined with '--lloyd'");
     if (p.reseed && p.refine <= 0 && p.lloyd <= 0)
         throw std::invalid_argument("option '--reseed' needs '--refine' > 0 or '--lloyd' > 0");
     return false;
@@ -208,7 +215,8 @@ int main(int argc, char **argv) {
         auto run_compression = [&]() {   // src/main.cpp:76-84
             RGBImage img(par.file);
             QuantizerPtr refined;
-            if (par.kmeanspp) refined = getKMeansPPQuantizer(par.seed, (size_t)par.refine, par.fresh, par.reseed);
+            if (par.kmeanspar) refined = getKMeansParQuantizer(par.seed, (size_t)par.refine, par.fresh, par.reseed);
+            else if (par.kmeanspp) refined = getKMeansPPQuantizer(par.seed, (size_t)par.refine, par.fresh, par.reseed);
             else if (par.lloyd > 0) refined = getLloydLBGQuantizer((size_t)par.lloyd, par.reseed, (size_t)par.refine, par.fresh);
             else if (par.refine > 0 || par.fresh) refined = getRefinedLBGQuantizer((size_t)par.refine, par.fresh, par.reseed);
             auto result = refined ? CompressedImage::compress(img, *refined, (ColorSpaces)par.colorspace, par.width,

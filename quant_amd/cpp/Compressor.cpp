@@ -140,10 +140,16 @@ std::tuple<std::vector<Vector>, std::vector<size_t>, VectorType> quantize_raster
         return std::make_tuple(std::move(codebook), std::vector<size_t>(A.begin(), A.end()), distortion);
     }
     if (opt.kmeanspp) {   // k-means++ seeds, then the refinement from them (no iteration: the nearest seed)
-        if (n > 20) throw std::runtime_error("compress: bits must be <= 20");
+        const int maxBits = opt.kmeansPar ? 16 : 20;
+        if (n > maxBits) throw std::runtime_error("compress: bits must be <= " + std::to_string(maxBits));
         std::vector<double> start(K * D);
-        EngineHandle::check(qvq_kmeanspp(ctx, (uint32_t)K, opt.kmeansppSeed, start.data(), nullptr, nullptr, nullptr),
-                            "qvq_kmeanspp");
+        if (opt.kmeansPar)
+            EngineHandle::check(qvq_kmeans_par(ctx, (uint32_t)K, opt.kmeansppSeed, nullptr, start.data(), nullptr, nullptr,
+                                               nullptr, nullptr),
+                                "qvq_kmeans_par");
+        else
+            EngineHandle::check(qvq_kmeanspp(ctx, (uint32_t)K, opt.kmeansppSeed, start.data(), nullptr, nullptr, nullptr),
+                                "qvq_kmeanspp");
         const bool fresh = opt.fresh || opt.maxIters == 0;
         EngineHandle::check(qvq_refine(ctx, (uint32_t)K, start.data(), (uint32_t)opt.maxIters, eps,
                                        (fresh ? QVQ_REFINE_FRESH : 0u) | (opt.reseed ? QVQ_REFINE_RESEED : 0u), C.data(),

@@ -134,19 +134,20 @@ public:
     }
 };
 
-// k-means++ seeding on the engine (qvq_kmeanspp), then qvq_refine from the seeds.  With no
-// iterations the refinement is the fresh assignment alone: the nearest seed of every row.
+// k-means++ seeding on the engine (qvq_kmeanspp; par: k-means||, qvq_kmeans_par with its default
+// options), then qvq_refine from the seeds.  With no iterations the refinement is the fresh assignment
+// alone: the nearest seed of every row.
 class HipKMeansPPQuantizer : public AbstractQuantizer {
     uint64_t seed_ = 0;
     size_t maxIters_ = 0;
-    bool fresh_ = false, reseed_ = false;
+    bool fresh_ = false, reseed_ = false, par_ = false;
 
 public:
-    HipKMeansPPQuantizer(uint64_t seed, size_t maxIters, bool fresh, bool reseed)
-        : seed_(seed), maxIters_(maxIters), fresh_(fresh), reseed_(reseed) {}
+    HipKMeansPPQuantizer(uint64_t seed, size_t maxIters, bool fresh, bool reseed, bool par = false)
+        : seed_(seed), maxIters_(maxIters), fresh_(fresh), reseed_(reseed), par_(par) {}
     quant_amd::RefineOptions options() const {
         quant_amd::RefineOptions o;
-        o.maxIters = maxIters_, o.fresh = fresh_, o.reseed = reseed_, o.kmeanspp = true, o.kmeansppSeed = seed_;
+        o.maxIters = maxIters_, o.fresh = fresh_, o.reseed = reseed_, o.kmeanspp = true, o.kmeansppSeed = seed_, o.kmeansPar = par_;
         return o;
     }
     std::tuple<std::vector<Vector>, std::vector<size_t>, VectorType> quantize(const std::vector<Vector> &trainingSet,
@@ -154,6 +155,7 @@ public:
         using quant_amd::EngineHandle;
         if (trainingSet.empty()) throw std::runtime_error("k-means++ quantize: empty training set");
         if (n > 20) throw std::runtime_error("k-means++ quantize: bits must be <= 20");
+        if (par_ && n > 16) throw std::runtime_error("k-means|| quantize: bits must be <= 16");
         if (maxIters_ > 0xFFFFFFFFull) throw std::runtime_error("k-means++ quantize: too many refinement iterations");
         const size_t N = trainingSet.size(), D = trainingSet[0].size();
         std::vector<double> flat(N * D);
@@ -167,7 +169,11 @@ public:
         std::vector<double> start(K * D), C(K * D);
         std::vector<uint32_t> A(N);
         double distortion = 0;
-        EngineHandle::check(qvq_kmeanspp(ctx, (uint32_t)K, seed_, start.data(), nullptr, nullptr, nullptr), "qvq_kmeanspp");
+        if (par_)
+            EngineHandle::check(qvq_kmeans_par(ctx, (uint32_t)K, seed_, nullptr, start.data(), nullptr, nullptr, nullptr, nullptr),
+                                "qvq_kmeans_par");
+        else
+            EngineHandle::check(qvq_kmeanspp(ctx, (uint32_t)K, seed_, start.data(), nullptr, nullptr, nullptr), "qvq_kmeanspp");
         const bool fresh = fresh_ || maxIters_ == 0;
         EngineHandle::check(qvq_refine(ctx, (uint32_t)K, start.data(), (uint32_t)maxIters_, eps,
                                        (fresh ? QVQ_REFINE_FRESH : 0u) | (reseed_ ? QVQ_REFINE_RESEED : 0u), C.data(),
@@ -222,4 +228,9 @@ QuantizerPtr getMedianCutQuantizer(size_t refineIters, bool fresh, bool reseed) 
 QuantizerPtr getKMeansPPQuantizer(uint64_t seed, size_t refineIters, bool fresh, bool reseed) {
     if (reseed && refineIters == 0) throw std::invalid_argument("getKMeansPPQuantizer: reseed needs refineIters > 0");
     return QuantizerPtr(new HipKMeansPPQuantizer(seed, refineIters, fresh, reseed));
+}
+
+QuantizerPtr getKMeansParQuantizer(uint64_t seed, size_t refineIters, bool fresh, bool reseed) {
+    if (reseed && refineIters == 0) throw std::invalid_argument("getKMeansParQuantizer: reseed needs refineIters > 0");
+    return QuantizerPtr(new HipKMeansPPQuantizer(seed, refineIters, fresh, reseed, true));
 }

@@ -27,12 +27,14 @@ struct RefineOptions {
                               // then holds for the levels too); the refinement, if any, continues from it
     bool kmeanspp = false;    // the codebook starts from qvq_kmeanspp's seeds (kmeansppSeed); the refinement starts from
     uint64_t kmeansppSeed = 0;   // them, and with maxIters == 0 it is the fresh assignment alone
+    bool kmeansPar = false;   // with kmeanspp: the seeds are qvq_kmeans_par's (getKMeansParQuantizer), default options
 };
 bool engine_lbg_options(const AbstractQuantizer &q, RefineOptions &out);
 // The same for the engine's median-cut quantizer (getMedianCutQuantizer): out.medianCut is set.
 bool engine_median_cut_options(const AbstractQuantizer &q, RefineOptions &out);
 
-// The same for the engine's k-means++ quantizer (getKMeansPPQuantizer): out.kmeanspp and the seed are set.
+// The same for the engine's k-means++ quantizer (getKMeansPPQuantizer; getKMeansParQuantizer: kmeansPar too):
+// out.kmeanspp and the seed are set.
 bool engine_kmeanspp_options(const AbstractQuantizer &q, RefineOptions &out);
 
 }  // namespace quant_amd

@@ -510,6 +510,46 @@ hipError_t launch_kmpp_init(hipStream_t s, const uint8_t *codes, uint32_t Dp, ui
 hipError_t launch_kmpp_update(hipStream_t s, const uint8_t *codes, uint32_t Dp, uint64_t N, bool first, const KmppWork &w);
 hipError_t launch_kmpp_select(hipStream_t s, const uint8_t *codes, uint32_t Dp, uint64_t N, uint32_t j, uint32_t K,
                               uint64_t seed, const KmppWork &w);
+// qvq_kmeans_par (k_kmeans_par.hip, kmeans_par_rule.hpp, kmeans_par_plan.hpp): the call's own state.
+// All but m, near and mask sit in one allocation of kmpar_layout(K, Dp, plan).total bytes (offsets in
+// bytes); the first 256 bytes are the state words and, from byte 96, potential[17].
+struct KMeansParPlan;
+struct KmparWork {
+    uint32_t *state = nullptr;       // [0] the stop flag (phi = 0), [1] M, [2] [3] the newest candidates' range (first, count),
+                                     // [4] rounds_run, [5] truncated, [6] placed, [8 .. 23] round_candidates
+    uint64_t *potential = nullptr;   // [17]
+    uint64_t *partial = nullptr;     // [KMPP_SEGMENTS_CAP] the segments' sums of m
+    uint32_t *counts = nullptr;      // [KMPP_SEGMENTS_CAP] the segments' joining rows of the round ...
+    uint32_t *offsets = nullptr;     // ... and their exclusive prefix
+    uint32_t *cand_rows = nullptr;   // [max_candidates] the candidates' rows
+    uint32_t *cand_wt = nullptr;     // [max_candidates] rows nearest to each
+    uint32_t *cand_codes = nullptr;  // [max_candidates][Dp / 4] their code words as stored
+    uint32_t *rows = nullptr;        // [K] the seeds' rows
+    uint32_t *seedcodes = nullptr;   // [K][Dp / 4] the seeds' code words as stored
+    uint32_t *gw = nullptr;          // [2][slots] the reduction's g and wt when they do not fit LDS
+    uint32_t *slotcodes = nullptr;   // [slots][Dp / 4] ... and its lane-strided copy of the code words when they do not
+    uint32_t *m = nullptr;           // [N] the rows' weight to their nearest candidate (an allocation of its own)
+    uint32_t *near = nullptr;        // [N] ... and that candidate (an allocation of its own)
+    uint64_t *mask = nullptr;        // [ceil(N / 64)] the round's joining rows, a bit each (an allocation of its own)
+};
+struct KmparLayout {
+    uint64_t partial = 0, counts = 0, offsets = 0, cand_rows = 0, cand_wt = 0, rows = 0, cand_codes = 0, seedcodes = 0,
+             gw = 0, slotcodes = 0, total = 0;
+};
+KmparLayout kmpar_layout(uint32_t K, uint32_t Dp, const KMeansParPlan &p);
+KmparWork kmpar_work(uint8_t *base, uint32_t *m, uint32_t *near, uint64_t *mask, const KmparLayout &l);
+// A call: init(row0 = candidate 0); update(first); for r = 1 .. rounds: sample(r) (count, scan, scatter),
+// update; weights; reduce.  After a scan has raised the stop flag the rounds' launches return at once.
+hipError_t launch_kmpar_init(hipStream_t s, const uint8_t *codes, uint32_t Dp, uint64_t N, uint32_t row0, uint32_t K,
+                             const KMeansParPlan &p, const KmparLayout &l, const KmparWork &w);
+hipError_t launch_kmpar_update(hipStream_t s, const uint8_t *codes, uint32_t Dp, uint64_t N, const KMeansParPlan &p,
+                               bool first, const KmparWork &w);
+hipError_t launch_kmpar_sample(hipStream_t s, const uint8_t *codes, uint32_t Dp, uint64_t N, const KMeansParPlan &p,
+                               uint32_t r, uint64_t seed, const KmparWork &w);
+hipError_t launch_kmpar_weights(hipStream_t s, const uint8_t *codes, uint32_t Dp, uint64_t N, const KMeansParPlan &p,
+                                const KmparWork &w);
+hipError_t launch_kmpar_reduce(hipStream_t s, const uint8_t *codes, uint32_t Dp, uint64_t N, const KMeansParPlan &p,
+                               uint32_t K, uint64_t seed, const KmparWork &w);
 // Host-resolved rows: A[rows[i]] = vals[i]; with xslab their terms move from the
 // provisional index (A before) to the new one (move_row_terms).
 hipError_t launch_fix_rows(hipStream_t s, const uint8_t *codes, uint32_t Dp, uint32_t D, uint32_t *A,

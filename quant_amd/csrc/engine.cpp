@@ -39,6 +39,8 @@
 #include "decode_plan.hpp"
 #include "exact_plan.hpp"
 #include "kdtree.hpp"
+#include "kmeans_par_plan.hpp"
+#include "kmeans_par_rule.hpp"
 #include "kmeanspp_plan.hpp"
 #include "mean_plan.hpp"
 #include "kmeanspp_rule.hpp"
@@ -229,6 +231,13 @@ struct qvq_ctx {
             DevBuf<uint8_t> d_work;
             uint32_t K = 0;
         } kpp;
+        // qvq_kmeans_par's own state, cached between calls: m, near [N], the rounds' join bits and the
+        // work of kmpar_layout (at least work_bytes).  Part of the training set as well.
+        struct KMeansPar {
+            DevBuf<uint32_t> d_m, d_near;
+            DevBuf<uint64_t> d_mask;
+            DevBuf<uint8_t> d_work;
+        } kpar;
     } ts;
 
     // ---- level buffers for up to Kcap code vectors: replaced as a whole by ensure_levels
@@ -4027,6 +4036,113 @@ QVQ_API qvq_status qvq_kmeanspp(qvq_ctx *ctx, uint32_t K, uint64_t seed, double 
     return QVQ_OK;
 }
 
+// k-means|| seeding on the device (the rule in qvq.h, kmeans_par_rule.hpp).  Candidate 0
+// is drawn here; the rounds (count, scan, scatter, update), the weights and the one-block reduction are
+// queued on the stream with no host round trip, and one bounded wait ends the call.  Everything the
+// call writes on the device is its own (ts.kpar): no resident state is touched.
+QVQ_API qvq_status qvq_kmeans_par(qvq_ctx *ctx, uint32_t K, uint64_t seed, const qvq_kmeans_par_opts *opts,
+                                  double *codebook, uint32_t *rows, uint32_t *cand_rows, uint64_t *cand_weights,
+                                  qvq_kmeans_par_info *info) {
+    if (!ctx) return QVQ_EINVAL;
+    GUARD(ctx);
+    if (ctx->ts.N == 0) return fail(ctx, QVQ_ESTATE, "no training set");
+    KMeansParPlan p{};
+    if (!kmeans_par_options(K, opts ? opts->rounds : 0, opts ? opts->ell : 0, opts ? opts->round_cap : 0, &p))
+        return fail(ctx, QVQ_EINVAL,
+                    "k-means||: K must be in 1 .. 2^16, rounds <= 16, ell <= 2^17, round_cap >= 1, 1 + rounds * round_cap <= 2^20");
+    if (ctx->ts.exact) return fail(ctx, QVQ_EUNSUPPORTED, "k-means|| seeding of an exact-mode training set is not supported");
+    if (ctx->comm || ctx->host_ar)
+        return fail(ctx, QVQ_EUNSUPPORTED, "k-means|| seeding is not supported on a communicator (no sample over ranks)");
+    const auto t0 = std::chrono::steady_clock::now();
+    HIPCHK(hipSetDevice(ctx->dev));
+    const uint32_t D = ctx->ts.D, Dp = ctx->ts.Dp;
+    const uint64_t N = ctx->ts.N;
+    kmeans_par_shape(N, Dp, &p);
+    qvq_ctx::Training::KMeansPar &kp = ctx->ts.kpar;
+    const KmparLayout lay = kmpar_layout(K, Dp, p);
+    HIPCHK(kp.d_m.ensure(N));
+    HIPCHK(kp.d_near.ensure(N));
+    HIPCHK(kp.d_mask.ensure((N + 63) / 64));
+    HIPCHK(kp.d_work.ensure(lay.total));
+    const uint64_t mc = p.max_candidates;
+    const uint64_t sB = 256, crB = 4 * mc, cwB = 4 * mc, rB = 4ull * K, cB = (uint64_t)K * Dp;   // staged: state | cand_rows | cand_wt | rows | codes
+    HIPCHK(ctx->h_stage.ensure(sB + crB + cwB + rB + cB));
+    std::memset(&ctx->tm, 0, sizeof(ctx->tm));
+    const KmparWork w = kmpar_work(kp.d_work, kp.d_m, kp.d_near, kp.d_mask, lay);
+    const uint8_t *codes = ctx->ts.d_codes;
+    const bool timed = ctx->timing_level == -3;   // events around the phases (qvq_set_timing)
+    hipStream_t s = ctx->stream;
+    if (timed) HIPCHK(hipEventRecord(ctx->ev[16][0], s));
+    HIPCHK(launch_kmpar_init(s, codes, Dp, N, (uint32_t)kmpp_draw(seed, 0, N), K, p, lay, w));
+    HIPCHK(launch_kmpar_update(s, codes, Dp, N, p, true, w));
+    for (uint32_t r = 1; r <= p.rounds; r++) {
+        if (timed) HIPCHK(hipEventRecord(ctx->ev[r - 1][0], s));
+        HIPCHK(launch_kmpar_sample(s, codes, Dp, N, p, r, seed, w));
+        if (timed) HIPCHK(hipEventRecord(ctx->ev[r - 1][1], s));
+        HIPCHK(launch_kmpar_update(s, codes, Dp, N, p, false, w));
+        if (timed) HIPCHK(hipEventRecord(ctx->ev[r - 1][2], s));
+    }
+    if (timed) HIPCHK(hipEventRecord(ctx->ev[16][1], s));
+    HIPCHK(launch_kmpar_weights(s, codes, Dp, N, p, w));
+    if (timed) HIPCHK(hipEventRecord(ctx->ev[16][2], s));
+    HIPCHK(launch_kmpar_reduce(s, codes, Dp, N, p, K, seed, w));
+    if (timed) HIPCHK(hipEventRecord(ctx->ev_end, s));
+    // results land in context-owned pinned memory and reach the caller only after the bounded wait
+    uint8_t *stage = static_cast<uint8_t *>(ctx->h_stage);
+    const uint8_t *base = kp.d_work;
+    HIPCHK(hipMemcpyAsync(stage, base, sB, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(stage + sB, base + lay.cand_rows, crB, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(stage + sB + crB, base + lay.cand_wt, cwB, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(stage + sB + crB + cwB, base + lay.rows, rB, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(stage + sB + crB + cwB + rB, base + lay.seedcodes, cB, hipMemcpyDeviceToHost, s));
+    qvq_status st = wait_stream(ctx);
+    if (st != QVQ_OK) return st;
+    uint32_t state[24];
+    std::memcpy(state, stage, sizeof(state));
+    const uint32_t placed = state[6];
+    if (cand_rows) std::memcpy(cand_rows, stage + sB, crB);
+    if (cand_weights) {
+        const uint32_t *wt = reinterpret_cast<const uint32_t *>(stage + sB + crB);
+        for (uint64_t c = 0; c < mc; c++) cand_weights[c] = wt[c];
+    }
+    if (rows) std::memcpy(rows, stage + sB + crB + cwB, rB);
+    if (codebook) {   // a seed's values are its row's, as qvq_get_vectors gives them; past placed: the zero vector
+        const uint8_t *sc = stage + sB + crB + cwB + rB;
+        for (uint32_t j = 0; j < K; j++)
+            for (uint32_t d = 0; d < D; d++)
+                codebook[(uint64_t)j * D + d] = j < placed ? ctx->ts.terms.v64[sc[(uint64_t)j * Dp + d]] : 0.0;
+    }
+    if (info) {
+        info->placed = placed;
+        info->candidates = state[1];
+        info->rounds_run = state[4];
+        info->truncated = state[5];
+        std::memcpy(info->round_candidates, state + 8, sizeof(info->round_candidates));
+        std::memcpy(info->potential, stage + 96, sizeof(info->potential));
+    }
+    if (timed) {   // other_ms[r - 1] round r's sample, assign_ms[r - 1] its update; update_ms[0] candidate 0's pass,
+                   // update_ms[1] the weights, update_ms[2] the reduction
+        float a = 0;
+        (void)hipEventSynchronize(ctx->ev_end);
+        for (uint32_t r = 1; r <= p.rounds; r++) {
+            (void)hipEventElapsedTime(&a, ctx->ev[r - 1][0], ctx->ev[r - 1][1]);
+            ctx->tm.other_ms[r - 1] = a;
+            (void)hipEventElapsedTime(&a, ctx->ev[r - 1][1], ctx->ev[r - 1][2]);
+            ctx->tm.assign_ms[r - 1] = a;
+        }
+        (void)hipEventElapsedTime(&a, ctx->ev[16][0], ctx->ev[0][0]);
+        ctx->tm.update_ms[0] = a;
+        (void)hipEventElapsedTime(&a, ctx->ev[16][1], ctx->ev[16][2]);
+        ctx->tm.update_ms[1] = a;
+        (void)hipEventElapsedTime(&a, ctx->ev[16][2], ctx->ev_end);
+        ctx->tm.update_ms[2] = a;
+        (void)hipGetLastError();
+    }
+    ctx->tm.levels = 0;
+    ctx->tm.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return QVQ_OK;
+}
+
 // ---------------------------------------------------------------------------------------
 // Decode: CompressedImage::decompress (src/Compressor.cpp:156-165) as one device gather.
 // ---------------------------------------------------------------------------------------
@@ -4457,6 +4573,26 @@ QVQ_API qvq_status qvq_host_kmeanspp_plan(uint64_t n, qvq_kmeanspp_plan *out) {
     out->segments = p.segments;
     out->seg_rows = p.seg_rows;
     out->segments_cap = KMPP_SEGMENTS_CAP;
+    return QVQ_OK;
+}
+
+QVQ_API qvq_status qvq_host_kmeans_par_join(uint64_t seed, uint32_t r, uint64_t row, uint64_t phi, uint32_t ell, uint32_t m,
+                                            int *joins) {
+    if (!joins || r == 0 || r > KMPAR_ROUNDS_MAX || ell > KMPAR_ELL_MAX || m >= (1u << 22)) return QVQ_EINVAL;
+    *joins = kmpar_joins(kmpar_round_key(seed, r), row, phi, ell, m) ? 1 : 0;
+    return QVQ_OK;
+}
+
+QVQ_API qvq_status qvq_host_kmeans_par_plan(uint64_t n, uint32_t dim, uint32_t K, const qvq_kmeans_par_opts *opts,
+                                            qvq_kmeans_par_plan *out) {
+    if (!out || n == 0 || n > 0xFFFFFFFFull || dim == 0 || dim > 64) return QVQ_EINVAL;
+    KMeansParPlan p{};
+    if (!kmeans_par_options(K, opts ? opts->rounds : 0, opts ? opts->ell : 0, opts ? opts->round_cap : 0, &p)) return QVQ_EINVAL;
+    kmeans_par_shape(n, (dim + 3) & ~3u, &p);
+    out->rounds = p.rounds, out->ell = p.ell, out->round_cap = p.round_cap;
+    out->block = p.block, out->segments = p.segments, out->seg_rows = p.seg_rows, out->segments_cap = KMPP_SEGMENTS_CAP;
+    out->chunk = p.chunk, out->max_candidates = p.max_candidates;
+    out->reduce_block = KMPAR_RED_THREADS, out->gw_lds = p.gw_lds, out->codes_lds = p.codes_lds, out->lds_bytes = p.lds_bytes;
     return QVQ_OK;
 }
 
