@@ -32,6 +32,7 @@ namespace qvq {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
 typedef uint64_t u64x2v __attribute__((ext_vector_type(2)));
+typedef _Float16 half4v __attribute__((ext_vector_type(4)));
 
 constexpr int M32_THREADS = 1024;   // 16 waves, 4 per SIMD, one workgroup per CU
 constexpr int M32_WAVES = M32_THREADS / 64;
@@ -536,14 +537,26 @@ __global__ __launch_bounds__(M32_THREADS) void assign_mf32_kernel(
 
 // =======================================================================================
 // Recheck of flagged rows on the same MFMA scores (D = 12).  A wave takes 32 flagged rows (one
-// data tile, both lane halves) through every code tile twice: pass 1 takes each row's minimum
-// score m; pass 2 lists the code vectors whose score is within m + 2E, E the row's MFMA bound
-// (m0 + m1 sum|w|, scaled) -- every other code vector is farther than the best in exact
-// arithmetic by more than the tie tolerance.  Those candidates (a few per row) get the fp64
-// distance in the reference's order (ref_l2_hd; lut64 values, C64); the row then takes the
-// lexicographic (distance, index) minimum, or goes to the kd-tree tie list when its best two
-// are within tie_rel.  Replaces the fp32 pass over all K per row (a wave per row) of
-// recheck_kernel: ~16 VALU per row and code tile pair instead of ~28 per code vector.
+// data tile, both lane halves) through every code tile once and lists the code vectors whose
+// score is within seed + 2E, E the row's MFMA bound (m0 + m1 sum|w|, scaled).  Those candidates
+// (a few per row) get the fp64 distance in the reference's order (ref_l2_hd; lut64 values,
+// C64); the row then takes the lexicographic (distance, index) minimum, or goes to the kd-tree
+// tie list when its best two are within tie_rel.  Replaces the fp32 pass over all K per row (a
+// wave per row) of recheck_kernel: ~36 VALU per row and code tile instead of ~28 per code vector.
+//
+// The seed, and why one pass is exact.  With m the row's minimum MFMA score, every code vector
+// whose score is above m + 2E is farther than the best in exact arithmetic by more than the tie
+// tolerance, so the band m + 2E holds every code vector the fp64 part needs; a first pass over
+// the tiles used to find m.  Instead the seed is the score of ks = A[row], the search's own
+// provisional index, evaluated in fp32 from its staged terms and the row, plus 1.65 E: two
+// evaluations of one code vector's score, the MFMAs' and this one, differ by less than that
+// (derived at the seed's code), so
+//     m <= MFMA score of ks <= seed,
+// the band seed + 2E contains m + 2E, and the listed code vectors are a superset of the two
+// passes'.  Each still gets the fp64 distance in the reference's order, and the (distance,
+// index) minimum k1, d1, the second distance d2 and the tie test over a superset of the band
+// are what they were, every code vector outside the band being farther than the best.  A
+// longer list can only overflow RC_CAP more often, and the all-K scan is exact.
 // =======================================================================================
 constexpr int RC_CAP = 16;   // candidates listed per row; more: the row's lane scans all K in fp64
 
@@ -612,6 +625,7 @@ __global__ __launch_bounds__(M32_THREADS) void recheck_mf32_kernel(
         const uint32_t row = flags[valid ? f : nflag - 1];
         const uint32_t *cw = reinterpret_cast<const uint32_t *>(codes + (uint64_t)row * MF_D);
         const uint32_t w0 = cw[0], w1 = cw[1], w2 = cw[2];
+        const uint32_t ks = min(A[row], K - 1);   // the search's index, on the way with the row's bytes
         half8 b1, b2;
         {
             uint32_t w01, w23, w45, w67, w89, wab;
@@ -628,11 +642,6 @@ __global__ __launch_bounds__(M32_THREADS) void recheck_mf32_kernel(
         sad = __builtin_amdgcn_sad_u8(w2 ^ 0x80808080u, 0x7F7F7F7Fu, sad);
         // two scores' MFMA bounds, scaled, with a margin for the fp32 band arithmetic
         const float band_add = 2.002f * scale_t * __fmaf_rn((float)(2 * sad + MF_D), th.m1, th.m0);
-        auto min16 = [](const f32x16 &c) {
-            return min2f(min3f(min3f(min3f(c[0], c[1], c[2]), min3f(c[3], c[4], c[5]), min3f(c[6], c[7], c[8])),
-                               min3f(c[9], c[10], c[11]), min3f(c[12], c[13], c[14])),
-                         c[15]);
-        };
         // scores of code tiles t and t + 1 (clamped: an odd count repeats the last tile), both
         // tiles' MFMAs issued before either result is read
         half8 a1, a2, a3, a4;
@@ -644,28 +653,60 @@ __global__ __launch_bounds__(M32_THREADS) void recheck_mf32_kernel(
             c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a2, b2, c, 0, 0, 0);
             d = __builtin_amdgcn_mfma_f32_32x32x16_f16(a4, b2, d, 0, 0, 0);
         };
-        // pass 1: the row's minimum score
-        float m = INFINITY;
-        for (uint32_t t = 0; t < ntiles; t += 2) {
-            f32x16 c, d;
-            pair(t, c, d);
-            m = min3f(m, min16(c), min16(d));
+        // The seed (header): the score of ks from the same f16 terms the MFMAs multiply -- the
+        // staged P / Q row of ks against this row's w, every product exact in fp32 -- as an fma
+        // chain from n_hi + n_lo: 25 roundings, each of a partial sum below T = sum |terms|, so
+        // within 25 u (1 + u)^25 T of the exact sum, u = 2^-24.  The MFMA score of ks is within
+        // 33 u T of that sum (mfma_setup's `rounds`; engine.cpp), and E >= 1.25 * 33 u S_row with
+        // T <= (1 + 2^-10) S_row (|hi| + |lo| of a term against the term), so the two evaluations
+        // differ by less than 58.07 u S_row <= 1.408 E; 1.65 leaves 10 u S_row for the roundings
+        // of the three fp32 operations of the last line.  Both lanes of a row compute the same.
+        float m;
+        {
+            const unsigned char *p = lds + (size_t)ks * 32, *q = lds + L.q + (size_t)ks * 24;
+            const bool sw = (ks >> 3) & 1;
+            const half8 ph = *reinterpret_cast<const half8 *>(p + (sw ? 16 : 0));   // hi(0..7)
+            const half8 pl = *reinterpret_cast<const half8 *>(p + (sw ? 0 : 16));   // lo(0..7)
+            const half4v ql = *reinterpret_cast<const half4v *>(q), qh = *reinterpret_cast<const half4v *>(q + 8);
+            const half4v qn = *reinterpret_cast<const half4v *>(q + 16);
+            float s = (float)qn[0] + (float)qn[1];
+#pragma unroll
+            for (int d = 0; d < 8; d++) {
+                const float w = byte_w(d < 4 ? w0 : w1, d % 4);
+                s = __fmaf_rn(w, (float)ph[d], s);
+                s = __fmaf_rn(w, (float)pl[d], s);
+            }
+#pragma unroll
+            for (int d = 0; d < 4; d++) {
+                const float w = byte_w(w2, d);
+                s = __fmaf_rn(w, (float)qh[d], s);
+                s = __fmaf_rn(w, (float)ql[d], s);
+            }
+            m = s + 1.65f * (scale_t * __fmaf_rn((float)(2 * sad + MF_D), th.m1, th.m0));
         }
-        m = min2f(m, xor32_f32(m));
         const float band = valid ? m + band_add * (1.0f + 1e-6f) + fabsf(m) * 1e-6f : -INFINITY;
-        // pass 2: list the code vectors inside the band, each lane into its own list (one
-        // shared counter per row made every listing a returning LDS atomic, and the 16
-        // listing branches of a tile ran whenever any of the wave's 32 rows had a candidate
-        // there: pass 2 took 3-4x pass 1)
+        // The one pass: list the code vectors inside the band, each lane into its own list (one
+        // shared counter per row made every listing a returning LDS atomic).  A lane's 16 scores
+        // of a tile against the band become a bit mask without a branch: the sign of band - c[v]
+        // is clear exactly when c[v] <= band (finite scores; band = -inf gives -inf), and
+        // v_alignbit shifts it in, v = 15 first, so bit v ends up set iff c[v] is outside.  Then
+        // one wave-uniform branch and a loop over the hits: its trip count is the largest number
+        // of candidates any lane has in this tile, normally 1 or 2.  (Sixteen compare-and-branch
+        // blocks ran here whenever any of the wave's 32 rows had a candidate in the tile, which is
+        // most tiles: ~700 cycles a tile for a wave alone on its SIMD.)  A tile's entries come
+        // out in v order per lane; `take` below does not depend on the order.
         uint32_t nmine = 0;
         auto list = [&](const f32x16 &c, uint32_t t) {
-            if (__ballot(min16(c) <= band)) {   // some row of the wave has a candidate here
+            uint32_t out = 0;
 #pragma unroll
-                for (int v = 0; v < 16; v++) {
-                    if (c[v] <= band) {
-                        if (nmine < RC_CAP) mine[nmine] = t * 32 + (v & 3) + 8 * (v >> 2) + 4 * h;
-                        nmine++;
-                    }
+            for (int v = 15; v >= 0; v--) out = __builtin_amdgcn_alignbit(out, __float_as_uint(band - c[v]), 31);
+            uint32_t hits = ~out & 0xFFFFu;
+            if (__ballot(hits != 0)) {   // some row of the wave has a candidate here
+                while (hits) {
+                    const uint32_t v = (uint32_t)__builtin_ctz(hits);
+                    hits &= hits - 1;
+                    if (nmine < RC_CAP) mine[nmine] = t * 32 + (v & 3) + 8 * (v >> 2) + 4 * h;
+                    nmine++;
                 }
             }
         };
