@@ -58,3 +58,8 @@ QuantizerPtr getKMeansPPQuantizer(uint64_t seed, size_t refineIters = 0, bool fr
 // The same with k-means|| seeding (qvq_kmeans_par, include/qvq.h, default options): a few passes over
 // the rows in place of K - 1.  n <= 16.
 QuantizerPtr getKMeansParQuantizer(uint64_t seed, size_t refineIters = 0, bool fresh = false, bool reseed = false);
+// The same with greedy k-means++ seeding (qvq_kmeanspp_greedy, include/qvq.h): `trials` candidate rows
+// a round, the one that lowers the potential most is kept.  trials in 0 .. 16, 0 the default count
+// (std::invalid_argument otherwise).
+QuantizerPtr getGreedyKMeansPPQuantizer(uint64_t seed, unsigned trials = 0, size_t refineIters = 0, bool fresh = false,
+                                        bool reseed = false);

@@ -469,6 +469,42 @@ QVQ_API qvq_status qvq_kmeans_par(qvq_ctx *ctx, uint32_t K, uint64_t seed, const
                                   double *codebook, uint32_t *rows, uint32_t *cand_rows, uint64_t *cand_weights,
                                   qvq_kmeans_par_info *info);
 
+/*
+ * Greedy k-means++ seeding on the device (Arthur & Vassilvitskii 2007, section 6; scikit-learn's
+ * n_local_trials): every round draws L candidate rows by D^2-sampling and keeps the one that lowers
+ * the potential most.  The reference has no such quantizer: this text is the rule.  The terms are
+ * qvq_kmeanspp's: the ordinals o, the weight w(a, b), mix and draw(seed, j, T); one rank's byte path.
+ *
+ * Trial count: trials lies in 0 .. 16.  trials = 0: L = 2 + (7 * floor(log2 K)) / 10 in integer
+ *   division (2 for K = 1, 9 for K = 1024, 16 for K = 2^20); otherwise L = trials.  info->trials = L.
+ * First seed: s_0 = draw(seed, 0, N); m[row] = w(row, s_0); potential[0] = sum of m.
+ * Rounds j = 1 .. K - 1: T = sum of m (a u64).  T = 0: placed = j, stop.  Else for l = 0 .. L - 1:
+ *   t_l = draw(seed + l * 2^32, j, T), all arithmetic wrapping (l = 0 is qvq_kmeanspp's own stream);
+ *   c_l = the lowest row with (sum of m[i] over i <= row) > t_l; the comparison is strict, so a row
+ *     with m = 0 is never drawn;
+ *   P_l = sum over the rows of min(m[row], w(row, c_l)), a u64 below 2^54.
+ *   Two trials may draw the same row; their P are then equal.  The winner is the l with the smallest
+ *   P_l, on equal P the lowest l.  s_j = c_winner, m = min(m, w(., s_j)), potential[j] = P_winner,
+ *   trial[j] = the winning l.  Without a stop placed = K.
+ * With L = 1 the call returns qvq_kmeanspp's rows, potentials, placed and codebook bit for bit.
+ *
+ * Outputs (caller-owned host memory, any may be NULL, written only after the bounded wait has
+ * succeeded): codebook (K x dim fp64), rows (K) and potential (K) as in qvq_kmeanspp; trial (K):
+ * trial[0] = 0, 0xFFFFFFFF from placed on; trial_rows and trial_potential (K x 16 each, row-major):
+ * entry [j][l] holds c_l and P_l of round j for l < L; row 0 holds s_0 and potential[0] at l = 0;
+ * everything else (l >= L, j >= placed, row 0 at l > 0) is 0xFFFFFFFF and 0.
+ *
+ * Like qvq_kmeanspp the call uses device buffers of its own and touches nothing resident.  Errors,
+ * in this order, each leaving the context as it was: QVQ_ESTATE without a training set; QVQ_EINVAL
+ * for K = 0, K > 2^20 or trials > 16; QVQ_EUNSUPPORTED for an exact-mode set; QVQ_EUNSUPPORTED with
+ * any communicator joined.  qvq_get_timings reports levels = 0 and the call's total_ms.
+ * (qvq_host_kmpp_trials is the trial count on the host.)
+ */
+typedef struct { uint32_t placed, trials; } qvq_kmeanspp_greedy_info;
+QVQ_API qvq_status qvq_kmeanspp_greedy(qvq_ctx *ctx, uint32_t K, uint64_t seed, uint32_t trials, double *codebook,
+                                       uint32_t *rows, uint64_t *potential, uint32_t *trial, uint32_t *trial_rows,
+                                       uint64_t *trial_potential, qvq_kmeanspp_greedy_info *info);
+
 /* Single steps over the current training set, for tests and benchmarks.
  * qvq_assign: nearest code vector of every row for codebook C (K x dim fp64, host),
  *   with the same MFMA/VALU search + fp64 recheck + kd-tree tie resolution as qvq_lbg.
@@ -730,6 +766,10 @@ QVQ_API qvq_status qvq_host_kmpp_weight(const uint8_t *codes_a, const uint8_t *c
  * scans their sums in one block: more than segments_cap * block rows make seg_rows grow. */
 typedef struct { uint32_t block, segments, seg_rows, segments_cap; } qvq_kmeanspp_plan;
 QVQ_API qvq_status qvq_host_kmeanspp_plan(uint64_t n, qvq_kmeanspp_plan *out);
+/* qvq_kmeanspp_greedy's trial count on the host (quant_amd/csrc/kmeanspp_greedy_plan.hpp, the function
+ * the call runs): *L = trials, or the default for trials = 0.  QVQ_EINVAL where the call gives it
+ * (K = 0, K > 2^20, trials > 16). */
+QVQ_API qvq_status qvq_host_kmpp_trials(uint32_t K, uint32_t trials, uint32_t *L);
 /* qvq_kmeans_par's sampling test on the host (quant_amd/csrc/kmeans_par_rule.hpp, the text the kernels
  * run): *joins = mulhi64(mix(mix(seed + r) + row), phi) < ell * m.  r in 1 .. 16, ell <= 2^17, m < 2^22
  * (QVQ_EINVAL otherwise). */

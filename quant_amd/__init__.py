@@ -74,6 +74,10 @@ class _KMeansPPPlan(ctypes.Structure):   # qvq_kmeanspp_plan
     _fields_ = [(f, ctypes.c_uint32) for f in ("block", "segments", "seg_rows", "segments_cap")]
 
 
+class _KMeansPPGreedyInfo(ctypes.Structure):   # qvq_kmeanspp_greedy_info
+    _fields_ = [("placed", ctypes.c_uint32), ("trials", ctypes.c_uint32)]
+
+
 class _KMeansParOpts(ctypes.Structure):   # qvq_kmeans_par_opts
     _fields_ = [(f, ctypes.c_uint32) for f in ("rounds", "ell", "round_cap")]
 
@@ -134,7 +138,8 @@ EXPORTED = ["qvq_create", "qvq_destroy", "qvq_last_error", "qvq_version", "qvq_s
             "qvq_median_cut", "qvq_host_median_cut_plan", "qvq_host_median_cut_axis",
             "qvq_host_median_cut_select", "qvq_lbg_lloyd", "qvq_kmeanspp", "qvq_host_kmpp_draw",
             "qvq_host_kmpp_weight", "qvq_host_kmeanspp_plan", "qvq_get_kahan_stats", "qvq_host_kahan_sort_plan",
-            "qvq_host_mean_grid", "qvq_kmeans_par", "qvq_host_kmeans_par_join", "qvq_host_kmeans_par_plan"]
+            "qvq_host_mean_grid", "qvq_kmeans_par", "qvq_host_kmeans_par_join", "qvq_host_kmeans_par_plan",
+            "qvq_kmeanspp_greedy", "qvq_host_kmpp_trials"]
 
 COMM_NONE, COMM_RCCL, COMM_HOST = 0, 1, 2
 REFINE_FRESH, REFINE_RESEED = 1, 2            # qvq_refine flags
@@ -217,6 +222,8 @@ def lib():
             "qvq_host_kmpp_draw": ([u64, u64, u64, ctypes.POINTER(u64)], i),
             "qvq_host_kmpp_weight": ([P, P, u32, ctypes.POINTER(u32)], i),
             "qvq_host_kmeanspp_plan": ([u64, ctypes.POINTER(_KMeansPPPlan)], i),
+            "qvq_kmeanspp_greedy": ([P, u32, u64, u32, P, P, P, P, P, P, ctypes.POINTER(_KMeansPPGreedyInfo)], i),
+            "qvq_host_kmpp_trials": ([u32, u32, ctypes.POINTER(u32)], i),
             "qvq_kmeans_par": ([P, u32, u64, ctypes.POINTER(_KMeansParOpts), P, P, P, P, ctypes.POINTER(_KMeansParInfo)], i),
             "qvq_host_kmeans_par_join": ([u64, u32, u64, u64, u32, u32, ctypes.POINTER(ctypes.c_int)], i),
             "qvq_host_kmeans_par_plan": ([u64, u32, u32, ctypes.POINTER(_KMeansParOpts), ctypes.POINTER(_KMeansParPlan)], i),
@@ -464,6 +471,28 @@ class Engine:
         _check(lib().qvq_kmeanspp(self._h, K, int(seed) & 0xFFFFFFFFFFFFFFFF, _p(C), _p(rows), _p(pot),
                                   ctypes.cast(ctypes.byref(placed), ctypes.c_void_p)), self._h)
         return C, rows, pot, int(placed.value)
+
+    def kmeanspp_greedy(self, K, seed=0, trials=0):
+        """Greedy k-means++ seeding on the device (qvq_kmeanspp_greedy, the rule in qvq.h): every round
+        draws `trials` candidate rows (0: the default 2 + 7 floor(log2 K) / 10, at most 16) and keeps
+        the one that lowers the potential most.  Returns (codebook, rows, potential, info): codebook,
+        rows and potential as kmeanspp's; info is a dict of placed, trials (the count used), trial
+        [K] (the winning trial of every round), trial_rows and trial_potential [K, 16] (every
+        candidate's row and potential; 0xFFFFFFFF and 0 where a round had no such trial).  trials = 1
+        is kmeanspp.  Nothing resident changes."""
+        K = int(K)
+        if K <= 0:
+            raise QVQError(1, "K must be in 1 .. 2^20")
+        if not 0 <= int(trials) <= 16:
+            raise QVQError(1, "trials must be in 0 .. 16")
+        C = np.empty((K, self.dim), np.float64)
+        rows, pot, trial = np.empty(K, np.uint32), np.empty(K, np.uint64), np.empty(K, np.uint32)
+        trows, tpot = np.empty((K, 16), np.uint32), np.empty((K, 16), np.uint64)
+        info = _KMeansPPGreedyInfo()
+        _check(lib().qvq_kmeanspp_greedy(self._h, K, int(seed) & 0xFFFFFFFFFFFFFFFF, int(trials), _p(C), _p(rows),
+                                         _p(pot), _p(trial), _p(trows), _p(tpot), ctypes.byref(info)), self._h)
+        return C, rows, pot, {"placed": int(info.placed), "trials": int(info.trials), "trial": trial,
+                              "trial_rows": trows, "trial_potential": tpot}
 
     def kmeans_par(self, K, seed=0, rounds=0, ell=0, round_cap=0):
         """k-means|| seeding on the device (qvq_kmeans_par, the rule in qvq.h): (codebook, rows,
@@ -766,6 +795,17 @@ def host_kmpp_weight(codes_a, codes_b):
     return int(w.value)
 
 
+def host_kmpp_trials(K, trials=0):
+    """The trial count qvq_kmeanspp_greedy uses for K seeds (qvq_host_kmpp_trials): `trials`, or for 0
+    the default 2 + 7 floor(log2 K) / 10.  QVQError where the call gives QVQ_EINVAL."""
+    K, trials = int(K), int(trials)
+    if not (0 <= K < 1 << 32 and 0 <= trials < 1 << 32):
+        raise QVQError(1, "K must be in 1 .. 2^20 and trials in 0 .. 16")
+    L = ctypes.c_uint32()
+    _check(lib().qvq_host_kmpp_trials(K, trials, ctypes.byref(L)))
+    return int(L.value)
+
+
 def _kmeans_par_info(info):
     return {"placed": int(info.placed), "candidates": int(info.candidates), "rounds_run": int(info.rounds_run),
             "truncated": int(info.truncated), "round_candidates": [int(v) for v in info.round_candidates],
@@ -1018,6 +1058,36 @@ class KMeansPPQuantizer(AbstractQuantizer):
         dev = getattr(trainingSet, "is_cuda", False)
         self._engine.set_vectors(trainingSet if dev else np.asarray(trainingSet, np.float64))
         C = self._engine.kmeanspp(1 << int(n), self._seed)[0]
+        return self._engine.refine(C=C, max_iters=self._refine_iters, eps=eps,
+                                   fresh=self._fresh or self._refine_iters == 0, reseed=self._reseed)[:3]
+
+
+class GreedyKMeansPPQuantizer(AbstractQuantizer):
+    """Greedy k-means++ seeding on the MI355X engine (Engine.kmeanspp_greedy) and Lloyd refinement
+    from the seeds.  The reference has no such quantizer and the Quantizers enum no slot for it."""
+
+    def __init__(self, device=0, seed=0, trials=0, refine_iters=0, fresh=False, reseed=False):
+        """quantize seeds 2**n code vectors with `seed`, `trials` candidate rows a round (0: the
+        default count), then runs Engine.refine from them for up to refine_iters iterations stopped
+        by eps.  refine_iters = 0 returns the nearest-seed assignment.  reseed needs refine_iters > 0."""
+        if reseed and int(refine_iters) <= 0:
+            raise QVQError(1, "reseed needs refine_iters > 0")
+        if not 0 <= int(trials) <= 16:
+            raise QVQError(1, "trials must be in 0 .. 16")
+        self._device = device
+        self._engine = None
+        self._seed = int(seed)
+        self._trials = int(trials)
+        self._refine_iters = int(refine_iters)
+        self._fresh = bool(fresh)
+        self._reseed = bool(reseed)
+
+    def quantize(self, trainingSet, n, eps):
+        if self._engine is None:
+            self._engine = Engine(self._device)
+        dev = getattr(trainingSet, "is_cuda", False)
+        self._engine.set_vectors(trainingSet if dev else np.asarray(trainingSet, np.float64))
+        C = self._engine.kmeanspp_greedy(1 << int(n), self._seed, self._trials)[0]
         return self._engine.refine(C=C, max_iters=self._refine_iters, eps=eps,
                                    fresh=self._fresh or self._refine_iters == 0, reseed=self._reseed)[:3]
 

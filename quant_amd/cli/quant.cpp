@@ -56,6 +56,7 @@ struct Params {   // include/ProgramParameters.hpp:5-19, defaults of src/main.cp
     bool kmeanspp = false;   // --init kmeans++: the codebook starts from k-means++ seeds (default split: LBG's schedule)
     bool kmeanspar = false;  // --init kmeans-par: ... from k-means|| seeds
     uint64_t seed = 0;       // --seed: of the k-means++ / k-means|| draws
+    int trials = -1;         // --trials: greedy k-means++ with that many candidate rows a round (0: the default count)
     std::string file, saveto;
 };
 
@@ -80,7 +81,9 @@ const char *kHelp =
     "  --init arg (=split)    Starting codebook: split (LBG's schedule), kmeans++ (2^n training\n"
     "                         rows by D^2-sampling) or kmeans-par (the same from a few sampling\n"
     "                         passes, n <= 16), then --refine iterations; -q 0, not with --lloyd\n"
-    "  --seed arg (=0)        Seed of the kmeans++ / kmeans-par draws\n";
+    "  --seed arg (=0)        Seed of the kmeans++ / kmeans-par draws\n"
+    "  --trials arg           Greedy kmeans++: candidate rows drawn per round, the best is kept\n"
+    "                         (0 .. 16, 0 = 2 + 7 floor(log2 K) / 10; with --init kmeans++)\n";
 
 bool parse_bool(const std::string &v) {   // program_options' bool values
     if (v == "1" || v == "true" || v == "yes" || v == "on") return true;
@@ -102,7 +105,7 @@ bool parse(int argc, char **argv, Params &p) {
         {"-n", "n"}, {"-e", "e"}, {"-w", "w"}, {"-h", "h"}, {"-o", "o"}, {"--saveto", "o"}, {"-r", "r"},
         {"-q", "q"}, {"--quantizer", "q"}, {"-c", "c"}, {"--colorspace", "c"}, {"--c", "c"}, {"--file", "file"},
         {"--device", "device"}, {"--refine", "refine"}, {"--lloyd", "lloyd"},
-        {"--init", "init"}, {"--seed", "seed"}};
+        {"--init", "init"}, {"--seed", "seed"}, {"--trials", "trials"}};
     bool have_file = false, have_out = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
@@ -166,6 +169,11 @@ bool parse(int argc, char **argv, Params &p) {
             else p.seed = std::stoull(val, &pos);
             if (pos != val.size()) throw std::invalid_argument("the argument ('" + val + "') for option '--seed' is invalid");
         }
+        else if (key == "trials") {
+            if (val.empty() || val[0] == '-' || val[0] == '+') throw std::invalid_argument("the argument ('" + val + "') for option '--trials' is invalid");
+            p.trials = parse_int(val, "--trials");
+            if (p.trials > 16) throw std::invalid_argument("the argument ('" + val + "') for option '--trials' is invalid");
+        }
         else if (key == "o") {
             p.saveto = val;
             have_out = true;
@@ -191,6 +199,8 @@ bool parse(int argc, char **argv, Params &p) {
         throw std::invalid_argument("option '--init kmeans-par' needs the LBG quantizer");
     if (p.kmeanspar && p.lloyd > 0)
         throw std::invalid_argument("option '--init kmeans-par' cannot be combined with '--lloyd'");
+    if (p.trials >= 0 && !p.kmeanspp)
+        throw std::invalid_argument("option '--trials' needs '--init kmeans++'");
     if (p.reseed && p.refine <= 0 && p.lloyd <= 0)
         throw std::invalid_argument("option '--reseed' needs '--refine' > 0 or '--lloyd' > 0");
     return false;
@@ -216,6 +226,8 @@ int main(int argc, char **argv) {
             RGBImage img(par.file);
             QuantizerPtr refined;
             if (par.kmeanspar) refined = getKMeansParQuantizer(par.seed, (size_t)par.refine, par.fresh, par.reseed);
+            else if (par.kmeanspp && par.trials >= 0)
+                refined = getGreedyKMeansPPQuantizer(par.seed, (unsigned)par.trials, (size_t)par.refine, par.fresh, par.reseed);
             else if (par.kmeanspp) refined = getKMeansPPQuantizer(par.seed, (size_t)par.refine, par.fresh, par.reseed);
             else if (par.lloyd > 0) refined = getLloydLBGQuantizer((size_t)par.lloyd, par.reseed, (size_t)par.refine, par.fresh);
             else if (par.refine > 0 || par.fresh) refined = getRefinedLBGQuantizer((size_t)par.refine, par.fresh, par.reseed);

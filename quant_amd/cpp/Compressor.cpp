@@ -147,6 +147,10 @@ std::tuple<std::vector<Vector>, std::vector<size_t>, VectorType> quantize_raster
             EngineHandle::check(qvq_kmeans_par(ctx, (uint32_t)K, opt.kmeansppSeed, nullptr, start.data(), nullptr, nullptr,
                                                nullptr, nullptr),
                                 "qvq_kmeans_par");
+        else if (opt.kmeansppTrials >= 0)
+            EngineHandle::check(qvq_kmeanspp_greedy(ctx, (uint32_t)K, opt.kmeansppSeed, (uint32_t)opt.kmeansppTrials,
+                                                    start.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr),
+                                "qvq_kmeanspp_greedy");
         else
             EngineHandle::check(qvq_kmeanspp(ctx, (uint32_t)K, opt.kmeansppSeed, start.data(), nullptr, nullptr, nullptr),
                                 "qvq_kmeanspp");
@@ -250,7 +254,7 @@ std::pair<CompressedImage, CompressionRaport> CompressedImage::compress(const RG
 }
 
 // The caller's quantizer over the image's blocks.  The engine's own quantizers (getQuantizer,
-// getRefinedLBGQuantizer, getMedianCutQuantizer, getKMeansPPQuantizer) train straight from the raster as the enum overload
+// getRefinedLBGQuantizer, getMedianCutQuantizer, getKMeansPPQuantizer and its kin) train straight from the raster as the enum overload
 // does, with their refinement; any other quantizer gets the host-built vectors.
 std::pair<CompressedImage, CompressionRaport> CompressedImage::compress(const RGBImage &image,
                                                                         AbstractQuantizer &quantizer,

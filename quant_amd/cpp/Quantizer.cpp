@@ -135,19 +135,21 @@ public:
 };
 
 // k-means++ seeding on the engine (qvq_kmeanspp; par: k-means||, qvq_kmeans_par with its default
-// options), then qvq_refine from the seeds.  With no iterations the refinement is the fresh assignment
+// options; trials >= 0: greedy k-means++, qvq_kmeanspp_greedy), then qvq_refine from the seeds.  With no iterations the refinement is the fresh assignment
 // alone: the nearest seed of every row.
 class HipKMeansPPQuantizer : public AbstractQuantizer {
     uint64_t seed_ = 0;
     size_t maxIters_ = 0;
     bool fresh_ = false, reseed_ = false, par_ = false;
+    int trials_ = -1;
 
 public:
-    HipKMeansPPQuantizer(uint64_t seed, size_t maxIters, bool fresh, bool reseed, bool par = false)
-        : seed_(seed), maxIters_(maxIters), fresh_(fresh), reseed_(reseed), par_(par) {}
+    HipKMeansPPQuantizer(uint64_t seed, size_t maxIters, bool fresh, bool reseed, bool par = false, int trials = -1)
+        : seed_(seed), maxIters_(maxIters), fresh_(fresh), reseed_(reseed), par_(par), trials_(trials) {}
     quant_amd::RefineOptions options() const {
         quant_amd::RefineOptions o;
         o.maxIters = maxIters_, o.fresh = fresh_, o.reseed = reseed_, o.kmeanspp = true, o.kmeansppSeed = seed_, o.kmeansPar = par_;
+        o.kmeansppTrials = trials_;
         return o;
     }
     std::tuple<std::vector<Vector>, std::vector<size_t>, VectorType> quantize(const std::vector<Vector> &trainingSet,
@@ -172,6 +174,10 @@ public:
         if (par_)
             EngineHandle::check(qvq_kmeans_par(ctx, (uint32_t)K, seed_, nullptr, start.data(), nullptr, nullptr, nullptr, nullptr),
                                 "qvq_kmeans_par");
+        else if (trials_ >= 0)
+            EngineHandle::check(qvq_kmeanspp_greedy(ctx, (uint32_t)K, seed_, (uint32_t)trials_, start.data(), nullptr, nullptr,
+                                                    nullptr, nullptr, nullptr, nullptr),
+                                "qvq_kmeanspp_greedy");
         else
             EngineHandle::check(qvq_kmeanspp(ctx, (uint32_t)K, seed_, start.data(), nullptr, nullptr, nullptr), "qvq_kmeanspp");
         const bool fresh = fresh_ || maxIters_ == 0;
@@ -228,6 +234,12 @@ QuantizerPtr getMedianCutQuantizer(size_t refineIters, bool fresh, bool reseed) 
 QuantizerPtr getKMeansPPQuantizer(uint64_t seed, size_t refineIters, bool fresh, bool reseed) {
     if (reseed && refineIters == 0) throw std::invalid_argument("getKMeansPPQuantizer: reseed needs refineIters > 0");
     return QuantizerPtr(new HipKMeansPPQuantizer(seed, refineIters, fresh, reseed));
+}
+
+QuantizerPtr getGreedyKMeansPPQuantizer(uint64_t seed, unsigned trials, size_t refineIters, bool fresh, bool reseed) {
+    if (trials > 16) throw std::invalid_argument("getGreedyKMeansPPQuantizer: trials must be in 0 .. 16");
+    if (reseed && refineIters == 0) throw std::invalid_argument("getGreedyKMeansPPQuantizer: reseed needs refineIters > 0");
+    return QuantizerPtr(new HipKMeansPPQuantizer(seed, refineIters, fresh, reseed, false, (int)trials));
 }
 
 QuantizerPtr getKMeansParQuantizer(uint64_t seed, size_t refineIters, bool fresh, bool reseed) {

@@ -27,6 +27,7 @@ struct RefineOptions {
                               // then holds for the levels too); the refinement, if any, continues from it
     bool kmeanspp = false;    // the codebook starts from qvq_kmeanspp's seeds (kmeansppSeed); the refinement starts from
     uint64_t kmeansppSeed = 0;   // them, and with maxIters == 0 it is the fresh assignment alone
+    int kmeansppTrials = -1;  // with kmeanspp, >= 0: the seeds are qvq_kmeanspp_greedy's with that trial count (0: its default)
     bool kmeansPar = false;   // with kmeanspp: the seeds are qvq_kmeans_par's (getKMeansParQuantizer), default options
 };
 bool engine_lbg_options(const AbstractQuantizer &q, RefineOptions &out);

@@ -510,6 +510,32 @@ hipError_t launch_kmpp_init(hipStream_t s, const uint8_t *codes, uint32_t Dp, ui
 hipError_t launch_kmpp_update(hipStream_t s, const uint8_t *codes, uint32_t Dp, uint64_t N, bool first, const KmppWork &w);
 hipError_t launch_kmpp_select(hipStream_t s, const uint8_t *codes, uint32_t Dp, uint64_t N, uint32_t j, uint32_t K,
                               uint64_t seed, const KmppWork &w);
+// qvq_kmeanspp_greedy (k_kmeanspp_greedy.hip, kmeanspp_rule.hpp, kmeanspp_greedy_plan.hpp): the call's
+// own state.  All but m sit in one allocation of kmppg_layout(K, Dp).total bytes.
+struct KmppgWork {
+    uint32_t *state = nullptr;             // [0] the stop flag, [1] placed, [2] the last published round's winning trial
+    uint32_t *cand = nullptr;              // [2][16][16] the rounds' candidates as ordinals, by round parity
+    uint32_t *candrow = nullptr;           // [2][16] ... and their rows
+    uint64_t *part = nullptr;              // [16][KMPP_SEGMENTS_CAP] per trial, the segments' sums of min(m, w(., c_l))
+    uint64_t *potential = nullptr;         // [K]
+    uint64_t *trial_potential = nullptr;   // [K][16]
+    uint32_t *rows = nullptr;              // [K] the seeds' rows
+    uint32_t *trial = nullptr;             // [K] the winning trials
+    uint32_t *trial_rows = nullptr;        // [K][16]
+    uint32_t *seedcodes = nullptr;         // [K][Dp / 4] the seeds' code words as stored
+    uint32_t *m = nullptr;                 // [N] the rows' weight to their nearest seed (an allocation of its own)
+};
+KmppgWork kmppg_work(uint8_t *base, uint32_t *m, uint32_t K, uint32_t Dp);
+// A call with L trials: init(row0 = the first seed); evaluate(0, 1); for j = 1 .. K - 1: select(j),
+// evaluate(j, L); select(K), which only publishes round K - 1.  evaluate(j) applies round j - 1's
+// winner to m and sums every candidate of round j; select(j) publishes round j - 1 and draws round
+// j's candidates, a block each.  After a select has raised the stop flag the rest return at once.
+hipError_t launch_kmppg_init(hipStream_t s, const uint8_t *codes, uint32_t Dp, uint64_t N, uint32_t row0, uint32_t K,
+                             const KmppgWork &w);
+hipError_t launch_kmppg_evaluate(hipStream_t s, const uint8_t *codes, uint32_t Dp, uint64_t N, uint32_t j, uint32_t L,
+                                 const KmppgWork &w);
+hipError_t launch_kmppg_select(hipStream_t s, const uint8_t *codes, uint32_t Dp, uint64_t N, uint32_t j, uint32_t K,
+                               uint32_t L, uint64_t seed, const KmppgWork &w);
 // qvq_kmeans_par (k_kmeans_par.hip, kmeans_par_rule.hpp, kmeans_par_plan.hpp): the call's own state.
 // All but m, near and mask sit in one allocation of kmpar_layout(K, Dp, plan).total bytes (offsets in
 // bytes); the first 256 bytes are the state words and, from byte 96, potential[17].

@@ -41,6 +41,7 @@
 #include "kdtree.hpp"
 #include "kmeans_par_plan.hpp"
 #include "kmeans_par_rule.hpp"
+#include "kmeanspp_greedy_plan.hpp"
 #include "kmeanspp_plan.hpp"
 #include "mean_plan.hpp"
 #include "kmeanspp_rule.hpp"
@@ -231,6 +232,13 @@ struct qvq_ctx {
             DevBuf<uint8_t> d_work;
             uint32_t K = 0;
         } kpp;
+        // qvq_kmeanspp_greedy's own state, cached between calls: m [N] and the work of kmppg_layout
+        // (at least work_bytes).  Part of the training set as well.
+        struct KMeansPPGreedy {
+            DevBuf<uint32_t> d_m;
+            DevBuf<uint8_t> d_work;
+            uint64_t work_bytes = 0;
+        } kppg;
         // qvq_kmeans_par's own state, cached between calls: m, near [N], the rounds' join bits and the
         // work of kmpar_layout (at least work_bytes).  Part of the training set as well.
         struct KMeansPar {
@@ -4036,6 +4044,81 @@ QVQ_API qvq_status qvq_kmeanspp(qvq_ctx *ctx, uint32_t K, uint64_t seed, double 
     return QVQ_OK;
 }
 
+// Greedy k-means++ seeding on the device (the rule in qvq.h, kmeanspp_rule.hpp): L trial
+// rows a round, the one that lowers the potential most is kept.  The first seed is drawn here; then
+// K - 1 rounds of select and evaluate are queued on the stream with no host round trip, a last select
+// publishes round K - 1, and one bounded wait ends the call.  Everything the call writes on the
+// device is its own (ts.kppg): no resident state is touched.
+QVQ_API qvq_status qvq_kmeanspp_greedy(qvq_ctx *ctx, uint32_t K, uint64_t seed, uint32_t trials, double *codebook,
+                                       uint32_t *rows, uint64_t *potential, uint32_t *trial, uint32_t *trial_rows,
+                                       uint64_t *trial_potential, qvq_kmeanspp_greedy_info *info) {
+    if (!ctx) return QVQ_EINVAL;
+    GUARD(ctx);
+    if (ctx->ts.N == 0) return fail(ctx, QVQ_ESTATE, "no training set");
+    uint32_t L = 0;
+    if (!kmpp_greedy_trials(K, trials, &L)) return fail(ctx, QVQ_EINVAL, "K must be in 1 .. 2^20 and trials in 0 .. 16");
+    if (ctx->ts.exact) return fail(ctx, QVQ_EUNSUPPORTED, "k-means++ seeding of an exact-mode training set is not supported");
+    if (ctx->comm || ctx->host_ar)
+        return fail(ctx, QVQ_EUNSUPPORTED, "k-means++ seeding is not supported on a communicator (no prefix over ranks)");
+    const auto t0 = std::chrono::steady_clock::now();
+    HIPCHK(hipSetDevice(ctx->dev));
+    const uint32_t D = ctx->ts.D, Dp = ctx->ts.Dp;
+    const uint64_t N = ctx->ts.N;
+    qvq_ctx::Training::KMeansPPGreedy &kp = ctx->ts.kppg;
+    const KmppgLayout lay = kmppg_layout(K, Dp);
+    HIPCHK(kp.d_m.ensure(N));
+    if (kp.work_bytes < lay.total) {
+        kp.work_bytes = 0;
+        HIPCHK(kp.d_work.alloc(lay.total));
+        kp.work_bytes = lay.total;
+    }
+    // staged: potential | trial_potential | rows | trial | trial_rows | codes | state (the layout's order)
+    const uint64_t pB = 8ull * K, tpB = trial_potential ? pB * KMPPG_MAX_TRIALS : 0, rB = 4ull * K,
+                   trB = trial_rows ? rB * KMPPG_MAX_TRIALS : 0, cB = (uint64_t)K * Dp;
+    const uint64_t oTP = pB, oR = oTP + tpB, oT = oR + rB, oTR = oT + rB, oC = oTR + trB, oS = oC + cB;
+    HIPCHK(ctx->h_stage.ensure(oS + 8));
+    std::memset(&ctx->tm, 0, sizeof(ctx->tm));
+    const KmppgWork w = kmppg_work(kp.d_work, kp.d_m, K, Dp);
+    const uint8_t *codes = ctx->ts.d_codes;
+    HIPCHK(launch_kmppg_init(ctx->stream, codes, Dp, N, (uint32_t)kmpp_draw(seed, 0, N), K, w));
+    HIPCHK(launch_kmppg_evaluate(ctx->stream, codes, Dp, N, 0, L, w));
+    for (uint32_t j = 1; j < K; j++) {
+        HIPCHK(launch_kmppg_select(ctx->stream, codes, Dp, N, j, K, L, seed, w));
+        HIPCHK(launch_kmppg_evaluate(ctx->stream, codes, Dp, N, j, L, w));
+    }
+    HIPCHK(launch_kmppg_select(ctx->stream, codes, Dp, N, K, K, L, seed, w));
+    // results land in context-owned pinned memory and reach the caller only after the bounded wait
+    uint8_t *stage = static_cast<uint8_t *>(ctx->h_stage);
+    const uint8_t *base = kp.d_work;
+    HIPCHK(hipMemcpyAsync(stage, base + lay.potential, pB, hipMemcpyDeviceToHost, ctx->stream));
+    if (tpB) HIPCHK(hipMemcpyAsync(stage + oTP, base + lay.trial_potential, tpB, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(stage + oR, base + lay.rows, rB, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(stage + oT, base + lay.trial, rB, hipMemcpyDeviceToHost, ctx->stream));
+    if (trB) HIPCHK(hipMemcpyAsync(stage + oTR, base + lay.trial_rows, trB, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(stage + oC, base + lay.seedcodes, cB, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(stage + oS, base, 8, hipMemcpyDeviceToHost, ctx->stream));
+    qvq_status st = wait_stream(ctx);
+    if (st != QVQ_OK) return st;
+    uint32_t state[2];
+    std::memcpy(state, stage + oS, 8);
+    const uint32_t placed = state[1];
+    if (potential) std::memcpy(potential, stage, pB);
+    if (trial_potential) std::memcpy(trial_potential, stage + oTP, tpB);
+    if (rows) std::memcpy(rows, stage + oR, rB);
+    if (trial) std::memcpy(trial, stage + oT, rB);
+    if (trial_rows) std::memcpy(trial_rows, stage + oTR, trB);
+    if (codebook) {   // a seed's values are its row's, as qvq_get_vectors gives them; past placed: the zero vector
+        const uint8_t *sc = stage + oC;
+        for (uint32_t j = 0; j < K; j++)
+            for (uint32_t d = 0; d < D; d++)
+                codebook[(uint64_t)j * D + d] = j < placed ? ctx->ts.terms.v64[sc[(uint64_t)j * Dp + d]] : 0.0;
+    }
+    if (info) info->placed = placed, info->trials = L;
+    ctx->tm.levels = 0;
+    ctx->tm.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return QVQ_OK;
+}
+
 // k-means|| seeding on the device (the rule in qvq.h, kmeans_par_rule.hpp).  Candidate 0
 // is drawn here; the rounds (count, scan, scatter, update), the weights and the one-block reduction are
 // queued on the stream with no host round trip, and one bounded wait ends the call.  Everything the
@@ -4573,6 +4656,11 @@ QVQ_API qvq_status qvq_host_kmeanspp_plan(uint64_t n, qvq_kmeanspp_plan *out) {
     out->segments = p.segments;
     out->seg_rows = p.seg_rows;
     out->segments_cap = KMPP_SEGMENTS_CAP;
+    return QVQ_OK;
+}
+
+QVQ_API qvq_status qvq_host_kmpp_trials(uint32_t K, uint32_t trials, uint32_t *L) {
+    if (!L || !kmpp_greedy_trials(K, trials, L)) return QVQ_EINVAL;
     return QVQ_OK;
 }
 
